@@ -176,7 +176,7 @@ def test_bench_two_gpus_over_rccl_reports_the_exchange():
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     env["OMP_NUM_THREADS"] = "4"
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1"]
+           "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--full"]
     r = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=900)
     print(r.stdout[-3000:])
     print(r.stderr[-2000:])
@@ -200,7 +200,7 @@ def test_bench_multi_gpu_path_runs_over_rccl_in_a_world_of_one():
         env.pop(k, None)
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "2", "--global-batch", "32",
-                        "--no-cpu-baseline", "--no-clock-probe"], env=env, cwd=ROOT, capture_output=True, text=True, timeout=600)
+                        "--no-cpu-baseline", "--no-clock-probe", "--full"], env=env, cwd=ROOT, capture_output=True, text=True, timeout=600)
     print(r.stdout[-2500:])
     print(r.stderr[-2500:])
     assert r.returncode == 0, r.stderr[-2000:]

@@ -1392,3 +1392,37 @@ def test_mlm_head_compaction_matches_full_path():
     torch.cuda.synchronize()
     o2, l2, g2, n2 = O.loss_and_grads(params, cfg, tuple(b2) + tuple(aux), train=False)
     assert abs(eng.loss_values()["loss"] - float(l2)) <= 1e-2 * float(l2)
+
+
+def test_bench_plain_run_times_the_steps_and_dumps_the_last_one(tmp_path):
+    """`bench.py` without --full: the line carries the headline figures only (no roofline, phase times, CPU baseline or child
+    configs), and --dump-outputs writes the last timed step's losses and a seeded sample of the updated weights as float32 .npy files
+    under 64 MB in all; the dumped losses are the ones the line reports, and a second run with the same arguments dumps the same
+    arrays up to the step's fp32 atomic reductions."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    runs = []
+    for i in range(2):
+        out = tmp_path / ("outputs%d" % i)
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--global-batch",
+                            "32", "--dump-outputs", str(out)], cwd=root, capture_output=True, text=True, timeout=600)
+        print(r.stdout[-2000:])
+        print(r.stderr[-2000:])
+        assert r.returncode == 0, r.stderr[-2000:]
+        d = json.loads(next(l for l in reversed(r.stdout.splitlines()) if l.startswith("{")))
+        assert d["steps"] == 2 and d["warmup"] == 1 and d["ms_per_step"] > 0 and d["value"] > 0
+        assert d["roofline"] is None and d["fwd_ms"] is None and "cpu_baseline" not in d and "other_configs" not in d
+        files = sorted(p.name for p in out.iterdir())
+        assert files == ["losses.npy", "weights_sample.npy"], files
+        arrays = {f[:-4]: np.load(out / f) for f in files}
+        assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in arrays.values())
+        assert sum((out / f).stat().st_size for f in files) <= 64 << 20
+        assert abs(float(arrays["losses"].sum()) - d["loss"]) <= 1e-3
+        runs.append(arrays)
+    for k in runs[0]:
+        a, b = runs[0][k], runs[1][k]
+        err = float(np.abs(a - b).max() / max(np.abs(b).max(), 1e-30))
+        print("two runs, %s: max |a - b| / max |b| = %.3e" % (k, err))
+        assert err <= 1e-3, k

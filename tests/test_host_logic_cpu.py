@@ -301,6 +301,24 @@ def test_bench_other_configs_summarises_children_and_survives_failures(monkeypat
     assert all("error" in v and "boom" in v["error"] for v in out.values())
 
 
+def test_bench_dump_sample_is_fixed_and_spans_every_tensor():
+    """bench.sample_flat (--dump-outputs): the same seeded positions of the concatenated tensors on every call, gathered across tensor
+    boundaries (empty tensors included); the whole concatenation when it is no larger than the sample."""
+    import importlib.util
+    import os
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("vlb_bench", os.path.join(root, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    ts = [torch.arange(n, dtype=torch.float32) + 1000.0 * i for i, n in enumerate([5, 0, 17, 3, 100000])]
+    cat = torch.cat(ts)
+    got = bench.sample_flat(ts, n=1000, seed=3)
+    idx = torch.randint(0, cat.numel(), (1000,), generator=torch.Generator().manual_seed(3)).sort().values
+    assert got.dtype == torch.float32 and torch.equal(got, cat[idx]) and torch.equal(got, bench.sample_flat(ts, n=1000, seed=3))
+    small = [torch.arange(5.0), torch.zeros(0), torch.arange(3.0) * 0.5]
+    assert torch.equal(bench.sample_flat([t.to(torch.bfloat16) for t in small], n=1000), torch.cat(small))
+
+
 def test_checkpoint_parameter_order_is_the_reference_models():
     """The index order of the optimizer state in a checkpoint (common/checkpoint.reference_param_order) against the reference's own
     `named_parameters()` order, recorded from the reference's modules by oracle/make_checkpoint_golden.py (plain, pooler + relationship

@@ -21,7 +21,7 @@ K, D = 2, 6
 def trace(steps, tag):
     d = "/tmp/fill_census_%s" % tag
     subprocess.run(["rm", "-rf", d])
-    cmd = ["rocprofv3", "--kernel-trace", "-d", d, "-o", "r", "--", sys.executable, os.path.join(ROOT, "bench.py"), "--steps", str(steps),
+    cmd = ["rocprofv3", "--kernel-trace", "-d", d, "-o", "r", "--", sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", str(steps),
            "--warmup", "1", "--no-graph", "--no-cpu-baseline", "--no-phase-times", "--no-clock-probe", "--head-start", "0"] + (["--e2e"] if e2e else [])
     env = dict(os.environ, TMPDIR="/tmp")
     subprocess.run(cmd, cwd="/tmp", env=env, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, timeout=900)
@@ -45,7 +45,7 @@ for n in sorted(set(a) | set(b)):
 torchish = [r for r in rows if r[0].startswith(("at::", "__amd_rocclr", "Cijk"))]
 with open(out_path, "w") as f:
     f.write("# %s -- launches per STEADY-STATE step = (launches with %d timed steps - launches with %d) / %d; rocprofv3 --kernel-trace of\n"
-            "# python bench.py --steps N --warmup 1 --no-graph --no-cpu-baseline --no-phase-times --no-clock-probe --head-start 0%s\n"
+            "# python bench.py --full --steps N --warmup 1 --no-graph --no-cpu-baseline --no-phase-times --no-clock-probe --head-start 0%s\n"
             "# 'set-up' = launches of the shorter run that the per-step rate does not explain (allocation fills, random initialisation, warm-up extras)\n"
             % ("e2e configuration (C3)" if e2e else "headline workload (global batch 256)", K + D, K, D, " --e2e" if e2e else ""))
     f.write("%-92s %12s %12s %10s\n" % ("kernel", "per step", "us per step", "set-up"))

@@ -5,7 +5,7 @@
 #   tests            full `-m gpu` suite                        | tests:<-k expr>   a subset (quote the expression)
 #   libtests:<dir>:<-k expr>   the same subset against a saved build vl-bert_amd/csrc/<dir>/libvlbert_hip.so
 #   smoke            __graft_entry__.smoke()
-#   bench            default bench line (with other_configs + the SURVEY-form CPU baseline)
+#   bench            bench.py --full (the headline line with other_configs + the SURVEY-form CPU baseline)
 #   ab:<dir>[,...]   default bench step, tree build interleaved with saved builds vl-bert_amd/csrc/<dir>/libvlbert_hip.so and
 #                    env-switched variants given as <NAME=VALUE> items (e.g. ab:VLB_GEMM_P8_DRAIN=1,ab_d3)
 #   gemm             tools/p8_check.py bench 256 (per-shape GEMM table, tile heights + model)
@@ -39,28 +39,28 @@ for what in "$@"; do
     envtests:*) spec="${what#envtests:}"; e="${spec%%:*}"; k="${spec#*:}"       # envtests:<NAME=VALUE[,NAME=VALUE...]>:<-k expr>: a subset under environment switches
               ( time env ${e//,/ } timeout 900 python -m pytest tests -m gpu -q -x -k "$k" 2>&1 | tail -12 ) > $OUT/envtests.log 2>&1; tail -6 $OUT/envtests.log ;;
     smoke)    timeout 300 python -c "import __graft_entry__ as g; g.smoke(); print('SMOKE OK')" 2>&1 | tail -3 | tee $OUT/smoke.log ;;
-    bench)    timeout 900 python bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err; cut -c1-900 $OUT/bench_default.json; tail -2 $OUT/bench_default.err
+    bench)    timeout 900 python bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err; cut -c1-900 $OUT/bench_default.json; tail -2 $OUT/bench_default.err
               python -c "import json; d=json.load(open('$OUT/bench_default.json')); print('cpu_baseline', d.get('cpu_baseline')); print('other_configs', json.dumps(d.get('other_configs'))[:1500])" ;;
     ab:*)     IFS=, read -ra V <<< "${what#ab:}"
               for i in 1 2; do
-                unset VLB_LIB_PATH; timeout 300 python bench.py --no-cpu-baseline --no-phase-times --no-clock-probe 2>/dev/null | line tree
+                unset VLB_LIB_PATH; timeout 300 python bench.py --full --no-cpu-baseline --no-phase-times --no-clock-probe 2>/dev/null | line tree
                 for v in "${V[@]}"; do
-                  if [[ $v == *=* ]]; then env "$v" timeout 300 python bench.py --no-cpu-baseline --no-phase-times --no-clock-probe 2>/dev/null | line "$v"
-                  else VLB_LIB_PATH=$ROOT/vl-bert_amd/csrc/$v/libvlbert_hip.so timeout 300 python bench.py --no-cpu-baseline --no-phase-times --no-clock-probe 2>/dev/null | line "$v"; fi
+                  if [[ $v == *=* ]]; then env "$v" timeout 300 python bench.py --full --no-cpu-baseline --no-phase-times --no-clock-probe 2>/dev/null | line "$v"
+                  else VLB_LIB_PATH=$ROOT/vl-bert_amd/csrc/$v/libvlbert_hip.so timeout 300 python bench.py --full --no-cpu-baseline --no-phase-times --no-clock-probe 2>/dev/null | line "$v"; fi
                 done
               done 2>&1 | tee $OUT/ab.log ;;
     gemm)     timeout 600 python tools/p8_check.py bench 256 2>&1 | tee $OUT/gemm_table.txt | tail -16 ;;
     gemm:*)   IFS=, read -ra V <<< "${what#gemm:}"
               for v in "${V[@]}"; do echo "== $v"; if [[ $v == *=* ]]; then env "$v" timeout 600 python tools/p8_check.py model 256; else VLB_LIB_PATH=$ROOT/vl-bert_amd/csrc/$v/libvlbert_hip.so timeout 600 python tools/p8_check.py model 256; fi; done 2>&1 | tee $OUT/gemm_variants.txt | tail -60 ;;
-    small)    for b in 128 64 32; do timeout 300 python bench.py --no-cpu-baseline --global-batch $b --no-phase-times 2>/dev/null | tee $OUT/bench$b.json | line "batch $b"; done | tee $OUT/small.log ;;
-    modes)    run() { n=$1; shift; timeout 600 python bench.py "$@" > $OUT/$n.json 2> $OUT/$n.err; line $n < $OUT/$n.json; }
+    small)    for b in 128 64 32; do timeout 300 python bench.py --full --no-cpu-baseline --global-batch $b --no-phase-times 2>/dev/null | tee $OUT/bench$b.json | line "batch $b"; done | tee $OUT/small.log ;;
+    modes)    run() { n=$1; shift; timeout 600 python bench.py --full "$@" > $OUT/$n.json 2> $OUT/$n.err; line $n < $OUT/$n.json; }
               run f16 --precision f16 --no-cpu-baseline; run e2e --e2e --no-cpu-baseline; run large --large --no-cpu-baseline
               run large_f16 --large --precision f16 --no-cpu-baseline; run vqa --vqa --steps 5 --warmup 2 --no-cpu-baseline
               run vqa_fp32 --vqa --precision fp32 --steps 3 --warmup 1 --no-cpu-baseline; run vcr_f16 --vcr --precision f16 --steps 3 --warmup 1 --no-cpu-baseline
               run vcr --vcr --steps 3 --warmup 1 --no-cpu-baseline ;;
-    e2e)      for v in "" "--graph" ; do timeout 400 python bench.py --e2e --no-cpu-baseline --no-phase-times --no-clock-probe $v 2>/dev/null | line "e2e $v"; done | tee $OUT/e2e.log
-              VLB_VISION_WGRAD_STREAMS=1 timeout 400 python bench.py --e2e --no-cpu-baseline --no-phase-times --no-clock-probe 2>/dev/null | line "e2e 1 side stream" | tee -a $OUT/e2e.log
-              VLB_VISION_WGRAD_STREAMS=1 timeout 400 python bench.py --e2e --no-cpu-baseline --no-phase-times --no-clock-probe --graph 2>/dev/null | line "e2e 1 side stream --graph" | tee -a $OUT/e2e.log ;;
+    e2e)      for v in "" "--graph" ; do timeout 400 python bench.py --full --e2e --no-cpu-baseline --no-phase-times --no-clock-probe $v 2>/dev/null | line "e2e $v"; done | tee $OUT/e2e.log
+              VLB_VISION_WGRAD_STREAMS=1 timeout 400 python bench.py --full --e2e --no-cpu-baseline --no-phase-times --no-clock-probe 2>/dev/null | line "e2e 1 side stream" | tee -a $OUT/e2e.log
+              VLB_VISION_WGRAD_STREAMS=1 timeout 400 python bench.py --full --e2e --no-cpu-baseline --no-phase-times --no-clock-probe --graph 2>/dev/null | line "e2e 1 side stream --graph" | tee -a $OUT/e2e.log ;;
     phase)    { timeout 200 python tools/p8_phase_probe.py 256 --spread; timeout 200 python tools/p8_phase_probe.py 32; } 2>&1 | grep -v amdgpu.ids | tee $OUT/p8_phase_probe.txt ;;
     stream)   for v in "VLB_LN_BWD4=1 VLB_LN_FWD_ROWS=1" "VLB_LN_BWD4=2 VLB_LN_FWD_ROWS=2" "VLB_LN_BWD4=1 VLB_LN_FWD_ROWS=4"; do env $v timeout 200 python tools/ln_bench.py 25856 768 $( [ "$v" = "VLB_LN_BWD4=1 VLB_LN_FWD_ROWS=1" ] || echo noopt ) 2>&1 | grep -v amdgpu.ids; done | tee $OUT/stream_bench.txt ;;
     ntprobe)  { hipcc --offload-arch=gfx950 -O3 tools/nt_coherence_probe.hip -o /tmp/nt_probe && timeout 300 /tmp/nt_probe; } 2>&1 | tee $OUT/nt_coherence_probe.txt ;;
@@ -69,10 +69,10 @@ for what in "$@"; do
               VLB_LIB_PATH=$ROOT/vl-bert_amd/csrc/ab/libvlbert_hip.so timeout 400 python tools/tn8_probe.py 256 --ablate 2>&1 | grep -v amdgpu.ids | tee $OUT/tn8_probe.txt ;;
     embed)    timeout 200 python tools/embed_bench.py 2>&1 | grep -v amdgpu.ids | tee $OUT/embed_bench.txt ;;
     clock)    timeout 300 python tools/clock_probe.py 4 2>&1 | grep -v amdgpu.ids | tee $OUT/clock_probe.txt ;;
-    graphsmall) for b in 64 32; do timeout 300 python bench.py --no-cpu-baseline --global-batch $b --no-phase-times --graph 2>/dev/null | line "batch $b --graph"; done | tee $OUT/graphsmall.log ;;
-    dp2)      timeout 600 python bench.py --gpus 2 --no-cpu-baseline --steps 10 > $OUT/dp2.json 2> $OUT/dp2.err; grep '^{' $OUT/dp2.json | cut -c1-1200; grep -v Gloo $OUT/dp2.err | tail -3
+    graphsmall) for b in 64 32; do timeout 300 python bench.py --full --no-cpu-baseline --global-batch $b --no-phase-times --graph 2>/dev/null | line "batch $b --graph"; done | tee $OUT/graphsmall.log ;;
+    dp2)      timeout 600 python bench.py --full --gpus 2 --no-cpu-baseline --steps 10 > $OUT/dp2.json 2> $OUT/dp2.err; grep '^{' $OUT/dp2.json | cut -c1-1200; grep -v Gloo $OUT/dp2.err | tail -3
               grep -o '"comm": {[^}]*}' $OUT/dp2.json ;;
-    trace)    ( cd /tmp && export TMPDIR=/tmp && VLB_WGRAD_STREAM=0 timeout 600 rocprofv3 --kernel-trace --stats -d $OUT/tr -o r -- python $ROOT/bench.py --steps 3 --warmup 1 --no-graph --no-cpu-baseline --no-phase-times --no-clock-probe > $OUT/tr.log 2>&1 )
+    trace)    ( cd /tmp && export TMPDIR=/tmp && VLB_WGRAD_STREAM=0 timeout 600 rocprofv3 --kernel-trace --stats -d $OUT/tr -o r -- python $ROOT/bench.py --full --steps 3 --warmup 1 --no-graph --no-cpu-baseline --no-phase-times --no-clock-probe > $OUT/tr.log 2>&1 )
               python tools/kstats.py $OUT/tr 5 24 | tee $OUT/kstats.txt; rm -rf $OUT/tr ;;
     profiles*) t="${what#profiles}"; t="${t#:}"; VLB_COMMIT=$(cat $ROOT/.commit_stamp 2>/dev/null || echo unknown) timeout 2000 bash tools/make_profiles.sh "${t:-r05}" small; ls $ROOT/gpurun_out/summary ;;
     mirror*)  n="${what#mirror}"; n="${n#:}"; n="${n:-12}"

@@ -13,7 +13,7 @@ cd /tmp && export TMPDIR=/tmp
 # per-kernel duration in a trace; the kernel-efficiency profile (like the instrumented step inside bench.py that produces
 # roofline.achieved) serialises them.  `value` in the default bench run is measured WITH the overlap.
 export VLB_WGRAD_STREAM=0
-CMD="python $ROOT/bench.py --steps 3 --warmup 1 --no-graph --no-cpu-baseline --no-phase-times --no-clock-probe"
+CMD="python $ROOT/bench.py --full --steps 3 --warmup 1 --no-graph --no-cpu-baseline --no-phase-times --no-clock-probe"
 rocprofv3 --kernel-trace --stats -d "$OUT/final_trace" -o r -- $CMD > "$OUT/final_trace.log" 2>&1
 rocprofv3 --kernel-trace --pmc SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_VALU_MFMA_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_INST_ANY SQ_WAIT_ANY SQ_BUSY_CYCLES SQ_ACTIVE_INST_ANY -d "$OUT/final_sq" -o r -- $CMD > "$OUT/final_sq.log" 2>&1
 rocprofv3 --kernel-trace --pmc FETCH_SIZE -d "$OUT/final_fetch" -o r -- $CMD > "$OUT/final_fetch.log" 2>&1
@@ -47,16 +47,16 @@ for set in "${@:2}"; do
     small)
       for b in 64 32; do
         VLB_WGRAD_STREAM=0 one kernel_stats_batch$b 5 "per-GPU batch $b of the global-256 strong-scaling run on ONE MI355X (no communication), weight-gradient stream serialised; 1 warm-up + 3 timed + 1 instrumented step" \
-          python "$ROOT/bench.py" --global-batch $b --steps 3 --warmup 1 --no-graph --no-cpu-baseline --no-phase-times --no-clock-probe
+          python "$ROOT/bench.py" --full --global-batch $b --steps 3 --warmup 1 --no-graph --no-cpu-baseline --no-phase-times --no-clock-probe
       done
       one vqa_fp32_kernel_stats 4 "BASELINE config 4 at its named precision: bench.py --vqa --precision fp32 (fp32 encoder, fp16 build around it); 1 warm-up + 2 timed + 1 instrumented optimizer step" \
-        python "$ROOT/bench.py" --vqa --precision fp32 --steps 2 --warmup 1 --no-cpu-baseline
+        python "$ROOT/bench.py" --full --vqa --precision fp32 --steps 2 --warmup 1 --no-cpu-baseline
       VLB_WGRAD_STREAM=0 one f16_kernel_stats 5 "headline workload on the fp16 build of the library (VLB_PRECISION=f16): same kernels, IEEE fp16 as the 16-bit type" \
-        python "$ROOT/bench.py" --precision f16 --steps 3 --warmup 1 --no-graph --no-cpu-baseline --no-phase-times --no-clock-probe ;;
+        python "$ROOT/bench.py" --full --precision f16 --steps 3 --warmup 1 --no-graph --no-cpu-baseline --no-phase-times --no-clock-probe ;;
     extra)
       VLB_WGRAD_STREAM=0 one large_kernel_stats 5 "bench.py --large (24 x 1024, S = 229, batch 64), weight-gradient stream serialised" \
-        python "$ROOT/bench.py" --large --steps 3 --warmup 1 --no-graph --no-cpu-baseline --no-phase-times --no-clock-probe
-      one vcr_kernel_stats 4 "bench.py --vcr (BASELINE config 5 through the module mirror)" python "$ROOT/bench.py" --vcr --steps 2 --warmup 1 --no-cpu-baseline
-      one vqa_kernel_stats 4 "bench.py --vqa (config 4's workload, 16-bit build)" python "$ROOT/bench.py" --vqa --steps 2 --warmup 1 --no-cpu-baseline ;;
+        python "$ROOT/bench.py" --full --large --steps 3 --warmup 1 --no-graph --no-cpu-baseline --no-phase-times --no-clock-probe
+      one vcr_kernel_stats 4 "bench.py --vcr (BASELINE config 5 through the module mirror)" python "$ROOT/bench.py" --full --vcr --steps 2 --warmup 1 --no-cpu-baseline
+      one vqa_kernel_stats 4 "bench.py --vqa (config 4's workload, 16-bit build)" python "$ROOT/bench.py" --full --vqa --steps 2 --warmup 1 --no-cpu-baseline ;;
   esac
 done

@@ -73,26 +73,26 @@ def kernel_stats(trace, out_name, cmd_note, steps=steps):
 
 if glob.glob(os.path.join(src, "final_trace", "*.db")):
     kernel_stats("final_trace", tag + "_kernel_stats.txt",
-                 "# VLB_WGRAD_STREAM=0 rocprofv3 --kernel-trace --stats -- python bench.py --steps 3 --warmup 1 --no-graph --no-cpu-baseline --no-phase-times\n")
+                 "# VLB_WGRAD_STREAM=0 rocprofv3 --kernel-trace --stats -- python bench.py --full --steps 3 --warmup 1 --no-graph --no-cpu-baseline --no-phase-times\n")
 if glob.glob(os.path.join(src, "final_e2e_trace", "*.db")):
     kernel_stats("final_e2e_trace", tag + "_e2e_kernel_stats.txt",
-                 "# VLB_WGRAD_STREAM=0 VLB_VISION_WGRAD_STREAM=0 rocprofv3 --kernel-trace --stats -- python bench.py --e2e --steps 3 --warmup 1 "
+                 "# VLB_WGRAD_STREAM=0 VLB_VISION_WGRAD_STREAM=0 rocprofv3 --kernel-trace --stats -- python bench.py --full --e2e --steps 3 --warmup 1 "
                  "--no-graph --no-cpu-baseline --no-phase-times\n# (config C3: 8 images of 600x1000, ResNet-101 trunk + ROIAlign + dilated layer4 head + the VL-BERT step)\n")
 
 
 if glob.glob(os.path.join(src, "final_large_trace", "*.db")):
     kernel_stats("final_large_trace", tag + "_large_kernel_stats.txt",
-                 "# VLB_WGRAD_STREAM=0 rocprofv3 --kernel-trace --stats -- python bench.py --large --steps 3 --warmup 1 --no-graph --no-cpu-baseline "
+                 "# VLB_WGRAD_STREAM=0 rocprofv3 --kernel-trace --stats -- python bench.py --full --large --steps 3 --warmup 1 --no-graph --no-cpu-baseline "
                  "--no-phase-times\n# (VL-BERT-large shape of BASELINE configs 4-5 through the pretraining step: 24 x 1024, 128 text + 100 regions, batch 64)\n")
 if glob.glob(os.path.join(src, "final_vcr_trace", "*.db")):
     kernel_stats("final_vcr_trace", tag + "_vcr_kernel_stats.txt",
-                 "# rocprofv3 --kernel-trace --stats -- python bench.py --vcr --steps 2 --warmup 1 --no-cpu-baseline\n# (BASELINE config 5 through the "
+                 "# rocprofv3 --kernel-trace --stats -- python bench.py --full --vcr --steps 2 --warmup 1 --no-cpu-baseline\n# (BASELINE config 5 through the "
                  "module mirror: 24 x 1024 encoder, 4 samples x 4 answer choices x 256 positions + 4 images of 600x1000 per micro-batch,\n# 4 micro-batches "
                  "per optimizer step; 1 warm-up + 2 timed + 1 instrumented optimizer step = 4 steps in the process; weight-gradient streams NOT serialised)\n",
                  steps=4.0)
 if glob.glob(os.path.join(src, "final_vqa_trace", "*.db")):
     kernel_stats("final_vqa_trace", tag + "_vqa_kernel_stats.txt",
-                 "# rocprofv3 --kernel-trace --stats -- python bench.py --vqa --steps 2 --warmup 1 --no-cpu-baseline\n# (BASELINE config 4's shape through "
+                 "# rocprofv3 --kernel-trace --stats -- python bench.py --full --vqa --steps 2 --warmup 1 --no-cpu-baseline\n# (BASELINE config 4's shape through "
                  "the module mirror, bf16: 24 x 1024 encoder, 16 samples x 229 positions per micro-batch, precomputed region features,\n# 4 micro-batches "
                  "per optimizer step, AdamW; 1 warm-up + 2 timed + 1 instrumented optimizer step = 4 steps in the process; weight-gradient streams NOT serialised)\n",
                  steps=4.0)
