@@ -241,6 +241,29 @@ int vlb_bce_logits_fwd_bwd(void* logits, long ld, int rows, int A, const float* 
  * VQA head, resnet_vlbert_for_vqa.py:57-77); the same call on the gradient is its backward. */
 int vlb_dropout_bf16(const void* x, void* y, long n, float drop_p, const uint32_t* seed, uint32_t tag, vlb_stream_t stream);
 
+/* ---- RefCOCO+ region-grounding head (refcoco/modules/resnet_vlbert_for_refcoco.py:132-160, :206-225; csrc/grounding.hip) ----
+ * final_mlp = transform (dense + erf-GELU: vlb_gemm_nt_bf16 with ACT_GELU_D, g = gelu(u), gelu'(u) kept) -> Dropout -> Linear(H, 1).
+ *   vlb_ground_score_fwd : logits[b, j] (fp32, row stride ldo) = sum_c dropout(g)[r, c] * w2[c] + b2[0] for j < max_len, r = b*max_len + j
+ *                          (g: 16-bit [B*max_len, H], row stride ldg; dropout on the fly with the element index r*H + c of
+ *                          vlb_dropout_bf16; w2 [H] / b2 [1] the fp32 master parameters); -10000 for max_len <= j < origin_len.
+ *   vlb_ground_bce       : valid = boxes[b*sbb + j*sbr] > -1.5 (j < max_len; strides in floats); *loss_out = mean over the valid rows of
+ *                          BCE-with-logits(logits[b, j], label[b*ldl + j]) (NaN when none is valid); dlogit [B*max_len] fp32 =
+ *                          (sigmoid(x) - y) / n_valid on valid rows, 0 elsewhere.  Overwrites, never accumulates; n_valid stays on the device.
+ *   vlb_ground_score_bwd : s[r] = *gscale * dlogit[r] (gscale: DEVICE pointer, the upstream gradient of the loss);
+ *                          du[r, c] (16-bit) = s[r] * w2[c] * keep(r*H + c) / (1 - p) * dgelu[r, c]; dw2[c] = sum_r s[r] * x1[r, c],
+ *                          db2[0] = sum_r s[r] (fp32, overwritten, fixed summation order: bitwise reproducible).
+ *   vlb_ground_pick_box  : idx[b] = argmax_j logits[b, j] over all origin_len columns (first index on ties, NaN largest, as torch);
+ *                          pred_boxes [B, 4] = boxes[b*sbb + idx*sbr + 0..3] / (im_info[b*ldi + 2], [3], [2], [3]); idx (int64) may be NULL. */
+int vlb_ground_score_fwd(const void* g, long ldg, int H, const float* w2, const float* b2, float* logits, long ldo, int B, int max_len,
+                         int origin_len, float drop_p, const uint32_t* seed, uint32_t tag, vlb_stream_t stream);
+int vlb_ground_bce(const float* logits, long ldo, const float* boxes, long sbb, long sbr, const float* label, long ldl, int B, int max_len,
+                   float* loss_out, float* dlogit, vlb_stream_t stream);
+int vlb_ground_score_bwd(const float* gscale, const float* dlogit, int rows, const void* g, long ldg, const void* dgelu, long ldd, int H,
+                         const float* w2, void* du, long lddu, float* dw2, float* db2, float drop_p, const uint32_t* seed, uint32_t tag,
+                         vlb_stream_t stream);
+int vlb_ground_pick_box(const float* logits, long ldo, int B, int origin_len, const float* boxes, long sbb, long sbr, const float* im_info,
+                        long ldi, float* pred_boxes, int64_t* idx, vlb_stream_t stream);
+
 /* ---- optimizer over flat buffers (common/nlp/bert/optimization.py:129-187,
  *      torch.nn.utils.clip_grad_norm_ at common/trainer.py:139-145) ---------------------------
  * state: DEVICE float[8] = {lr, beta1, beta2, eps, weight_decay, step, max_norm, sumsq}.

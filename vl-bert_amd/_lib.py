@@ -108,6 +108,10 @@ _SIGS = {
     "vlb_rng_advance": "ps",
     "vlb_roi_align_fwd": "pppiiiiiifis",
     "vlb_roi_align_bwd": "pppiiiiiiifis",
+    "vlb_ground_score_fwd": "plippp" "liiifpus",
+    "vlb_ground_bce": "plpllpliipps",
+    "vlb_ground_score_bwd": "ppiplpli" "pplppfpus",
+    "vlb_ground_pick_box": "pliipllplpps",
     # RCCL exchange for a C / C++ host (csrc/comm.hip; this Python host issues its collectives through torch.distributed)
     "vlb_comm_unique_id": "p",
     "vlb_comm_init": "iipp",

@@ -2,6 +2,7 @@
 
     python -m vl-bert_amd.vqa.train_end2end --cfg cfgs/vqa/large_4x16G_fp32.yaml [--dist] [--steps N]      (vqa/train_end2end.py:12-60)
     python -m vl-bert_amd.vcr.train_end2end --cfg cfgs/vcr/large_q2a_4x16G_fp16.yaml [--dist] [--steps N]  (vcr/train_end2end.py)
+    python -m vl-bert_amd.refcoco.train_end2end --cfg cfgs/refcoco/base_gt_boxes_4x16G.yaml [--dist] [--steps N]  (refcoco/train_end2end.py)
 
 Same command line as the reference's scripts (--cfg / --model-dir / --log-dir / --dist / --slurm / --do-test / --cudnn-off /
 --partial-pretrain).  The YAML is read as it is; the keys the training loop consumes follow vqa/function/train.py:96-330 and
@@ -14,7 +15,7 @@ vcr/function/train.py:96-335:
   * per step: GRAD_ACCUMULATE_STEPS micro-batches of loss / accumulate, clip_grad_norm_(CLIP_GRAD_NORM), optimizer step
     (common/trainer.py:101-189); TRAIN.FP16 -> the fp16 build + static loss scale FP16_LOSS_SCALE ("--compute cfg").
 Not reproduced: the data side (datasets, tokeniser, image decoding: batches are synthetic in the collated layouts of
-vqa/data/collate_batch.py / vcr/data/collate_batch.py), validation / test-set csv writing, tensorboard.  No CPU path: without a GPU the
+vqa/data/collate_batch.py / vcr/data/collate_batch.py / refcoco/data/collate_batch.py), validation / test-set csv writing, tensorboard.  No CPU path: without a GPU the
 program stops with an error unless --dry-run is given.
 """
 import argparse
@@ -66,7 +67,11 @@ DEFAULTS = {"vqa": {"RNG_SEED": 12345, "MODULE": "ResNetVLBERT", "LOG_FREQUENT":
                     "DATASET": {"ANSWER_VOCAB_SIZE": 3129}, "NETWORK": dict(_NET, IMAGE_FEAT_PRECOMPUTED=True), "TRAIN": _TRAIN},
             # vcr/function/config.py:113: the VCR model reads the pooled output
             "vcr": {"RNG_SEED": 12345, "MODULE": "ResNetVLBERT", "LOG_FREQUENT": 100, "SCALES": (600, 1000), "MODEL_PREFIX": "",
-                    "DATASET": {"TASK": "Q2A"}, "NETWORK": dict(_NET, VLBERT=dict(_NET["VLBERT"], with_pooler=True)), "TRAIN": _TRAIN}}
+                    "DATASET": {"TASK": "Q2A"}, "NETWORK": dict(_NET, VLBERT=dict(_NET["VLBERT"], with_pooler=True)), "TRAIN": _TRAIN},
+            # refcoco/function/config.py: image branch, CLASSIFIER_DROPOUT 0.1, SGD (the shared _TRAIN keys); ADD_IMAGE_AS_A_BOX
+            "refcoco": {"RNG_SEED": 12345, "MODULE": "ResNetVLBERT", "LOG_FREQUENT": 50, "SCALES": (600, 1000), "MODEL_PREFIX": "",
+                        "DATASET": {"DATASET": "refcoco+", "ADD_IMAGE_AS_A_BOX": True}, "NETWORK": dict(_NET, IMAGE_FEAT_PRECOMPUTED=False),
+                        "TRAIN": _TRAIN}}
 
 
 def load_config(task, path):
@@ -214,6 +219,8 @@ def main(task, argv=None):
         seed = 1000 * rank + i
         if task == "vqa":
             return syn.make_vqa_batch(B, 100, 124, seed, dev, answers=int(config.DATASET.ANSWER_VOCAB_SIZE))
+        if task == "refcoco":
+            return syn.make_refcoco_batch(B, 20, 12, Hi, Wi, seed, dev, precomputed=r["precomputed"])
         return syn.make_vcr_batch(B, 4, 55, 80, 117, Hi, Wi, seed, dev)
     if rank == 0:
         print("%s/train_end2end: %s | %d GPU(s) x batch %d x accumulate %d | %s lr %.3e wd %.1e clip %.1f | schedule %s warmup %d | compute %s" %
@@ -229,6 +236,9 @@ def main(task, argv=None):
             if task == "vqa":
                 boxes, im_info, question, label = b
                 outputs, loss = net(None, boxes, im_info, question, label)
+            elif task == "refcoco":
+                image, boxes, im_info, expression, label = b
+                outputs, loss = net(image, boxes, im_info, expression, label)
             else:
                 image, boxes, masks, question, answers, label, im_info = b
                 outputs, loss = net(image, boxes, masks, question, None, answers, None, label, im_info)

@@ -422,6 +422,51 @@ def bce_logits_fwd_bwd(logits, A, label, loss_out, gscale=1.0, logits_copy=None,
               float(pos_weight), _p(loss_out, torch.float32), _p(logits_copy, BF16), _ld(logits_copy), _stream())
 
 
+def _aligned(t):
+    assert t.data_ptr() % 16 == 0, "16-byte aligned tensor expected"
+    return t
+
+
+def ground_score_fwd(g, w2, b2, logits, B, max_len, drop_p=0.0, seed=None, tag=0):
+    """logits fp32 [B, >=origin_len] <- dropout(g) . w2 + b2 per row of g (16-bit [B*max_len, H]); -10000 in columns max_len..origin_len-1
+    (origin_len = logits.shape[1]); w2 fp32 [H] (or [1, H]), b2 fp32 [1]: the master parameters (vlb_ground_score_fwd)."""
+    H = g.shape[1]
+    assert g.shape[0] == B * max_len and w2.numel() == H and b2.numel() == 1 and w2.is_contiguous()
+    _lib.call("vlb_ground_score_fwd", _p(_aligned(g), BF16), _ld(g), H, _p(_aligned(w2), torch.float32), _p(b2, torch.float32),
+              _p(logits, torch.float32), _ld(logits), B, max_len, logits.shape[1], float(drop_p), _p(seed), int(tag), _stream())
+    return logits
+
+
+def ground_bce(logits, boxes, label, max_len, loss_out, dlogit):
+    """Masked BCE-with-logits of the grounding head (vlb_ground_bce): mask = boxes[:, :max_len, 0] > -1.5; loss_out[0] <- mean over the
+    valid boxes (NaN when there is none); dlogit fp32 [B*max_len] <- (sigmoid(x) - y) / n_valid on valid rows, 0 elsewhere."""
+    B = boxes.shape[0]
+    assert boxes.dim() == 3 and label.dim() == 2 and label.stride(1) == 1 and logits.shape[0] == B and dlogit.numel() >= B * max_len
+    _lib.call("vlb_ground_bce", _p(logits, torch.float32), _ld(logits), _p(boxes, torch.float32), boxes.stride(0), boxes.stride(1),
+              _p(label, torch.float32), label.stride(0), B, max_len, _p(loss_out, torch.float32), _p(dlogit, torch.float32), _stream())
+
+
+def ground_score_bwd(gscale, dlogit, g, dgelu, w2, du, dw2, db2, drop_p=0.0, seed=None, tag=0):
+    """du (16-bit, [rows, H]) <- gscale * dlogit[r] * w2 * keep / (1 - p) * dgelu; dw2 fp32 [H] / db2 fp32 [1] overwritten with the
+    fixed-order row sums (vlb_ground_score_bwd).  gscale: fp32 device scalar (the upstream gradient of the loss)."""
+    rows, H = g.shape
+    assert dgelu.shape == g.shape and du.shape == g.shape and w2.numel() == H and dw2.numel() == H and dlogit.numel() >= rows
+    _lib.call("vlb_ground_score_bwd", _p(gscale, torch.float32), _p(dlogit, torch.float32), rows, _p(_aligned(g), BF16), _ld(g),
+              _p(_aligned(dgelu), BF16), _ld(dgelu), H, _p(w2, torch.float32), _p(_aligned(du), BF16), _ld(du), _p(dw2, torch.float32),
+              _p(db2, torch.float32), float(drop_p), _p(seed), int(tag), _stream())
+    return du
+
+
+def ground_pick_box(logits, boxes, im_info, pred_boxes, idx=None):
+    """pred_boxes fp32 [B, 4] <- boxes[b, argmax_j logits[b, j], :4] / (w_ratio, h_ratio, w_ratio, h_ratio); idx int64 [B] (optional)
+    receives the argmax (first index on ties) -- vlb_ground_pick_box."""
+    B, L = logits.shape
+    assert boxes.dim() == 3 and boxes.shape[0] == B and boxes.shape[1] >= L and boxes.stride(2) == 1 and im_info.stride(1) == 1
+    _lib.call("vlb_ground_pick_box", _p(logits, torch.float32), _ld(logits), B, L, _p(boxes, torch.float32), boxes.stride(0),
+              boxes.stride(1), _p(im_info, torch.float32), im_info.stride(0), _p(pred_boxes, torch.float32), _p(idx, torch.int64), _stream())
+    return pred_boxes
+
+
 def dropout_bf16(x, y, drop_p, seed, tag):
     _lib.call("vlb_dropout_bf16", _p(x, BF16), _p(y, BF16), x.numel(), float(drop_p), _p(seed), int(tag), _stream())
     return y

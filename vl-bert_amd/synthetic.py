@@ -121,3 +121,33 @@ def make_vcr_batch(B, C, R, Lq, La, Hi, Wi, seed, device):
     label = torch.randint(0, C, (B,), generator=g)
     im_info = torch.tensor([[Wi, Hi, 1.0, 1.0, float(i)] for i in range(B)])
     return [t.to(device) for t in (image, boxes, masks, question, answers, label, im_info)]
+
+
+def make_refcoco_batch(B, R, L, Hi, Wi, seed, device, precomputed=False):
+    """One collated RefCOCO+ micro-batch (refcoco/data/collate_batch.py layout): image [B,3,Hi,Wi] (None when precomputed), boxes [B,R,4]
+    ([B,R,4+2048] when precomputed; box 0 = the whole image, ragged counts, pad rows -2), im_info [B,4] = (w, h, w_ratio, h_ratio) with
+    non-unit ratios, expression ids [B,L] (zero-padded), label [B,R] float 0/1 per box (several positives possible; pad -1)."""
+    g = torch.Generator().manual_seed(seed)
+    nbox = torch.randint(max(2, R // 2), R + 1, (B,), generator=g)
+    nbox[0] = R
+    x1 = torch.rand(B, R, generator=g) * (Wi - 64)
+    y1 = torch.rand(B, R, generator=g) * (Hi - 64)
+    w = 16 + torch.rand(B, R, generator=g) * 48
+    h = 16 + torch.rand(B, R, generator=g) * 48
+    boxes = torch.stack((x1, y1, x1 + w, y1 + h), -1)
+    boxes[:, 0] = torch.tensor([0.0, 0.0, Wi - 1.0, Hi - 1.0])
+    if precomputed:
+        boxes = torch.cat((boxes, torch.randn(B, R, 2048, generator=g).abs()), -1)
+    pad = torch.arange(R)[None, :] >= nbox[:, None]
+    boxes[pad] = -2.0
+    ratio = 0.5 + torch.rand(B, 2, generator=g)
+    im_info = torch.cat((torch.tensor([[float(Wi), float(Hi)]]).repeat(B, 1), ratio), 1)
+    expression = torch.randint(1000, 30522, (B, L), generator=g)
+    elen = torch.randint(max(1, L // 2), L + 1, (B,), generator=g)
+    elen[0], elen[-1] = L, max(1, L // 2)             # the collator pads to the longest expression of the batch
+    expression[torch.arange(L)[None, :] >= elen[:, None]] = 0
+    label = (torch.rand(B, R, generator=g) < 0.25).float()
+    label[:, 1] = 1.0                                   # at least one positive per sample; more are possible (IoU > 0.5, refcoco.py:200-203)
+    label[pad] = -1.0
+    image = None if precomputed else torch.randn(B, 3, Hi, Wi, generator=g) * 50.0
+    return [t.to(device) if t is not None else None for t in (image, boxes, im_info, expression, label)]
