@@ -81,6 +81,16 @@ def coordinate_embeddings(boxes6, dim=256):
     return torch.cat((arg.sin(), arg.cos()), dim=-1)
 
 
+def dropout(x, prob, hook, site, **where):
+    """F.dropout(x, prob, training=True) as the reference calls it.  `hook` (test infrastructure, default None = torch's RNG) lets
+    the caller supply the mask instead: hook(site, prob, shape, **where) returns the keep mask already multiplied by the inverted-
+    dropout scale, broadcastable to x.  `site` names the reference's dropout module -- "embedding", "attention_probs",
+    "attention_output", "ffn_output" (with layer=l) or "obj_downsample" (with inds = the box_mask.nonzero() rows of x)."""
+    if hook is None:
+        return F.dropout(x, prob, True)
+    return x * hook(site, prob, tuple(x.shape), **where).to(x.dtype)
+
+
 def soft_cross_entropy(logits, target):
     """common/utils/misc.py:124-151, reduction='mean': rows are valid iff
     |sum(target)-1| < 0.1; mean over valid rows of -sum(log_softmax * target)."""
@@ -93,7 +103,7 @@ def soft_cross_entropy(logits, target):
 # --------------------------------------------------------------------------- #
 # a2: FastRCNN precomputed-feature branch
 # --------------------------------------------------------------------------- #
-def fast_rcnn_precomputed(p, cfg, boxes, box_mask, im_info, train, gen=None):
+def fast_rcnn_precomputed(p, cfg, boxes, box_mask, im_info, train, gen=None, drop_hook=None):
     """common/fast_rcnn.py:136-142,165-187.  boxes [B,R,4+2048] (features already
     mask-overwritten by the caller).  Returns obj_reps [B,R,H] zero-padded."""
     B, R = box_mask.shape
@@ -103,7 +113,7 @@ def fast_rcnn_precomputed(p, cfg, boxes, box_mask, im_info, train, gen=None):
         torch.cat((boxes[inds[:, 0], inds[:, 1]][:, :4], im_info[inds[:, 0], :2]), 1), 256)
     x = torch.cat((coord.reshape(coord.shape[0], -1), feats), -1)
     if train and cfg.obj_downsample_dropout > 0:
-        x = F.dropout(x, cfg.obj_downsample_dropout, True)
+        x = dropout(x, cfg.obj_downsample_dropout, drop_hook, "obj_downsample", inds=inds)
     y = F.relu(linear(x, p, "image_feature_extractor.obj_downsample.1"))
     out = y.new_zeros((B, R, y.shape[-1]))
     out[inds[:, 0], inds[:, 1]] = y   # == pad_sequence for prefix masks (common/utils/pad_sequence.py:4-17)
@@ -114,7 +124,7 @@ def fast_rcnn_precomputed(p, cfg, boxes, box_mask, im_info, train, gen=None):
 # a3: embedding with seamless [text || objects || END] concatenation
 # --------------------------------------------------------------------------- #
 def vl_embedding(p, cfg, text_ids, text_type_ids, text_visual, text_mask, obj_vl, obj_mask,
-                 train):
+                 train, drop_hook=None):
     """common/visual_linguistic_bert.py:173-241 (visual_ln=True, obj_pos_id_relative=True,
     position_padding_idx=-1, visual_size == hidden_size)."""
     H = cfg.hidden_size
@@ -150,7 +160,7 @@ def vl_embedding(p, cfg, text_ids, text_type_ids, text_visual, text_mask, obj_vl
         + F.embedding(type_ids, p[pre + "token_type_embeddings.weight"])
     emb = bert_layer_norm(emb, p[pre + "embedding_LayerNorm.weight"], p[pre + "embedding_LayerNorm.bias"])
     if train and cfg.hidden_dropout_prob > 0:
-        emb = F.dropout(emb, cfg.hidden_dropout_prob, True)
+        emb = dropout(emb, cfg.hidden_dropout_prob, drop_hook, "embedding")
     mask = (grid_pos <= obj_end)
     return emb, mask, is_text, is_obj
 
@@ -158,7 +168,7 @@ def vl_embedding(p, cfg, text_ids, text_type_ids, text_visual, text_mask, obj_vl
 # --------------------------------------------------------------------------- #
 # a5-a10: encoder
 # --------------------------------------------------------------------------- #
-def bert_layer(p, cfg, pre, x, ext_mask, train):
+def bert_layer(p, cfg, pre, x, ext_mask, train, drop_hook=None, layer=None):
     """external/pytorch_pretrained_bert/modeling.py:290-319 (self-attention),
     :329-333 (self-output), :361-364 (intermediate), :374-378 (output)."""
     B, S, H = x.shape
@@ -174,30 +184,30 @@ def bert_layer(p, cfg, pre, x, ext_mask, train):
     scores = torch.matmul(q, k.transpose(-1, -2)) / math.sqrt(d) + ext_mask
     probs = torch.softmax(scores, dim=-1)
     if train and cfg.attention_probs_dropout_prob > 0:
-        probs = F.dropout(probs, cfg.attention_probs_dropout_prob, True)
+        probs = dropout(probs, cfg.attention_probs_dropout_prob, drop_hook, "attention_probs", layer=layer)
     ctx = torch.matmul(probs, v).permute(0, 2, 1, 3).reshape(B, S, H)
 
     a = linear(ctx, p, pre + "attention.output.dense")
     if train and cfg.hidden_dropout_prob > 0:
-        a = F.dropout(a, cfg.hidden_dropout_prob, True)
+        a = dropout(a, cfg.hidden_dropout_prob, drop_hook, "attention_output", layer=layer)
     a = bert_layer_norm(a + x, p[pre + "attention.output.LayerNorm.weight"],
                         p[pre + "attention.output.LayerNorm.bias"])
     i = gelu(linear(a, p, pre + "intermediate.dense"))
     o = linear(i, p, pre + "output.dense")
     if train and cfg.hidden_dropout_prob > 0:
-        o = F.dropout(o, cfg.hidden_dropout_prob, True)
+        o = dropout(o, cfg.hidden_dropout_prob, drop_hook, "ffn_output", layer=layer)
     return bert_layer_norm(o + a, p[pre + "output.LayerNorm.weight"], p[pre + "output.LayerNorm.bias"])
 
 
-def vlbert_forward(p, cfg, text_ids, text_type_ids, text_visual, text_mask, obj_vl, obj_mask, train):
+def vlbert_forward(p, cfg, text_ids, text_type_ids, text_visual, text_mask, obj_vl, obj_mask, train, drop_hook=None):
     """common/visual_linguistic_bert.py:95-171 with output_all_encoded_layers=False,
     output_text_and_object_separately=True (as called from :356-365)."""
     emb, mask, is_text, is_obj = vl_embedding(p, cfg, text_ids, text_type_ids, text_visual, text_mask,
-                                              obj_vl, obj_mask, train)
+                                              obj_vl, obj_mask, train, drop_hook)
     ext = (1.0 - mask.to(emb.dtype)).unsqueeze(1).unsqueeze(2) * -10000.0
     x = emb
     for l in range(cfg.num_hidden_layers):
-        x = bert_layer(p, cfg, "vlbert.encoder.layer.%d." % l, x, ext, train)
+        x = bert_layer(p, cfg, "vlbert.encoder.layer.%d." % l, x, ext, train, drop_hook, l)
     pooled = None
     if cfg.with_pooler:
         pooled = torch.tanh(linear(x[:, 0], p, "vlbert.pooler.dense"))   # modeling.py:430-436
@@ -227,13 +237,13 @@ def mvrc_head(p, x):
 # a1: the pre-training module
 # --------------------------------------------------------------------------- #
 def pretrain_forward(p, cfg, boxes, im_info, text, relationship_label, mlm_labels, mvrc_ops, mvrc_labels,
-                     train=False, image=None, vision_params=None, image_num_layers=101):
+                     train=False, image=None, vision_params=None, image_num_layers=101, drop_hook=None):
     """pretrain/modules/resnet_vlbert_for_pretraining.py:93-216.  image=None: precomputed-feature
     configuration.  image [B,3,H,W] + vision_params (oracle/vision_oracle.py, torchvision-style names): the e2e
     configuration -- box features come from the ResNet trunk / ROIAlign / layer4 head (common/fast_rcnn.py:144-156)
     and, as the raw pixels were masked by the dataset, no mask embedding is substituted (:114-127 passes
     mask_visual_embed=None).  Returns (outputs dict, loss) with the reference's shapes (logits re-padded to
-    the original lengths with -10000)."""
+    the original lengths with -10000).  drop_hook: see `dropout` (train=True only)."""
     boxes = boxes.clone()                                   # the reference mutates its input (:115-117)
     box_mask = boxes[:, :, 0] > -1.5
     origin_len = boxes.shape[1]
@@ -249,7 +259,7 @@ def pretrain_forward(p, cfg, boxes, im_info, text, relationship_label, mlm_label
         feats = boxes[:, :, 4:].clone()
         feats[mvrc_ops == 1] = p["object_mask_visual_embedding.weight"][0]
     boxes = torch.cat((boxes[:, :, :4], feats), -1)
-    obj_reps = fast_rcnn_precomputed(p, cfg, boxes, box_mask, im_info, train)
+    obj_reps = fast_rcnn_precomputed(p, cfg, boxes, box_mask, im_info, train, drop_hook=drop_hook)
 
     text_mask = text > 0
     text_visual = obj_reps[:, 0:1].expand(-1, text.shape[1], -1)     # tags all 0 (:132-135, :74-91)
@@ -259,7 +269,7 @@ def pretrain_forward(p, cfg, boxes, im_info, text, relationship_label, mlm_label
     obj_vl = torch.cat((obj_reps, ling), -1)
 
     text_out, obj_out, pooled, seq = vlbert_forward(p, cfg, text, torch.zeros_like(text), text_visual, text_mask,
-                                                    obj_vl, box_mask, train)
+                                                    obj_vl, box_mask, train, drop_hook)
     mlm_logits = mlm_head(p, text_out)
     mvrc_logits = mvrc_head(p, obj_out)
 
@@ -291,7 +301,8 @@ def pretrain_forward(p, cfg, boxes, im_info, text, relationship_label, mlm_label
 
 
 def pretrain_multitask_forward(p, cfg, boxes, im_info, text, relationship_label, mlm_labels, mvrc_ops, mvrc_labels,
-                               aux_text, aux_mlm_labels, train=False, image=None, vision_params=None, image_num_layers=101):
+                               aux_text, aux_mlm_labels, train=False, image=None, vision_params=None, image_num_layers=101,
+                               drop_hook=None):
     """pretrain/modules/resnet_vlbert_for_pretraining_multitask.py:96-290 (one auxiliary text-only dataset): the aux captions
     are appended as extra samples without objects whose text-visual embedding is the learned `aux_text_visual_embedding`; MLM
     loss is split into the with-visual-content and aux parts.  image=None: precomputed features (:132-135); image + vision_params:
@@ -311,7 +322,7 @@ def pretrain_multitask_forward(p, cfg, boxes, im_info, text, relationship_label,
         feats = boxes[:, :, 4:].clone()
         feats[mvrc_ops == 1] = p["object_mask_visual_embedding.weight"][0]
     boxes = torch.cat((boxes[:, :, :4], feats), -1)
-    obj_reps = fast_rcnn_precomputed(p, cfg, boxes, box_mask, im_info, train)
+    obj_reps = fast_rcnn_precomputed(p, cfg, boxes, box_mask, im_info, train, drop_hook=drop_hook)
     B, R = box_mask.shape
     Ba = aux_text.shape[0]
     H = cfg.hidden_size
@@ -332,7 +343,7 @@ def pretrain_multitask_forward(p, cfg, boxes, im_info, text, relationship_label,
     box_mask_multi[:B] = box_mask
 
     text_out, obj_out, pooled, seq = vlbert_forward(p, cfg, text_multi, torch.zeros_like(text_multi), tv, text_multi > 0,
-                                                    obj_vl_multi, box_mask_multi, train)
+                                                    obj_vl_multi, box_mask_multi, train, drop_hook)
     mlm_logits = mlm_head(p, text_out)
     mvrc_logits = mvrc_head(p, obj_out)[:B]
     labels_multi = mlm_labels.new_full((B + Ba, T), -1)
@@ -441,12 +452,12 @@ def init_params(cfg, seed=0, dtype=torch.float32, randomize_all=True):
     return p
 
 
-def loss_and_grads(p, cfg, batch, train=False):
+def loss_and_grads(p, cfg, batch, train=False, drop_hook=None):
     """Forward + autograd backward.  Returns (outputs, loss, {name: grad}, global L2 grad norm)
-    -- the tied MLM decoder weight is counted once (SURVEY.md §8c pitfall v)."""
+    -- the tied MLM decoder weight is counted once (SURVEY.md §8c pitfall v).  drop_hook: see `dropout`."""
     leaves = {k: v.detach().clone().requires_grad_(True) for k, v in p.items()}
     fwd = pretrain_multitask_forward if len(batch) == 9 else pretrain_forward
-    outputs, loss = fwd(leaves, cfg, *batch, train=train)
+    outputs, loss = fwd(leaves, cfg, *batch, train=train, drop_hook=drop_hook)
     loss.backward()
     grads = {k: (v.grad if v.grad is not None else torch.zeros_like(v)) for k, v in leaves.items()}
     norm = torch.sqrt(sum((g.double() ** 2).sum() for g in grads.values())).item()

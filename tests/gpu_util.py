@@ -84,3 +84,77 @@ def keep_mask(seed, tag, idx, thr):
     h = _pair_hash(idx >> np.uint64(1), key)
     bits = np.where((idx & np.uint64(1)) == 1, h >> np.uint64(16), h & np.uint64(0xFFFF))
     return bits >= np.uint64(thr)
+
+
+def rng_advance(seed):
+    """vlb_rng_advance (vl-bert_amd/csrc/optim.hip:255): seed <- hash32(seed + 0x9E3779B9) | 1, as uint32."""
+    return int(_hash32(np.array([(int(seed) + 0x9E3779B9) & 0xFFFFFFFF], dtype=np.uint64))[0]) | 1
+
+
+def device_seed(eng):
+    """The engine's device-resident dropout seed (an int32 tensor) as the uint32 the kernels read."""
+    return int(eng.seed.item()) & 0xFFFFFFFF
+
+
+# ---- the engine's dropout layout: which (tag, element index) every dropout site draws ---------------------------------------
+TAG_EMBED, TAG_DOWNSAMPLE = 1000, 1001          # vl-bert_amd/engine.py:30
+
+
+class EngineDropoutMasks:
+    """`drop_hook` for oracle/vlbert_oracle.py (see its `dropout`): the keep mask x device scale the engine regenerates at each
+    dropout site, restated from keep_mask(seed, tag, idx, thr) and placed in the oracle's tensor layout.
+
+    S is the engine's packed length T + R + 1 (the oracle's sequence is only max_length long: the engine-layout index is sliced to
+    it); Bt = B + B_aux with the aux samples after the caption samples, as both lay them out.  Sp: the fp32 encoder's padded key
+    stride (its softmax writes rows of Sp, vl-bert_amd/csrc/f32_path.hip:430,452), None for the 16-bit attention kernel.
+
+      embedding         (b*S + s)*H + c        tag TAG_EMBED      embed_fwd / embed_bwd (engine.py:651,1036; csrc/embed.hip)
+      attention_probs   ((b*nh + h)*S + q)*Sk + k, Sk = S or Sp  tag l*8+0   attention.hip:349 / f32_path.hip:430
+      attention_output  m*H + n, m = b*S + s   tag l*8+1          gemm_p8.hip:167 (EPI 3/6), gemm.hip:190, f32_path.hip:230;
+      ffn_output        m*H + n                tag l*8+2          backward: layernorm dx_drop (engine.py:949,957, f32_path.hip:363)
+      obj_downsample    (b*R + r)*4096 + e     tag TAG_DOWNSAMPLE obj_prep_fwd (embed.hip:99); masked_colsum row_elems 4096,
+                                                                  col_off 2048 (engine.py:1064); vision.hip:867 in the e2e path
+    """
+
+    def __init__(self, seed, S, R, nh, Sp=None):
+        self.seed, self.S, self.R, self.nh, self.Sp = int(seed) & 0xFFFFFFFF, S, R, nh, Sp
+        self.sites = []              # (site, layer) in call order: what the oracle asked for
+
+    @staticmethod
+    def thr(prob):
+        return drop_thr(float(np.float32(prob)))     # vlb_drop_thr reads a float
+
+    @staticmethod
+    def scale(thr):
+        return float(np.float32(65536.0) / np.float32(65536.0 - thr)) if thr else 1.0     # vlb_drop_scale (fp32 division)
+
+    def index(self, site, shape, layer=None, inds=None):
+        """(tag, uint64 element-index array of `shape`) for one site."""
+        S, R, nh = self.S, self.R, self.nh
+        ar = lambda n: np.arange(n, dtype=np.int64)
+        if site == "embedding":
+            b, s, H = shape
+            return TAG_EMBED, (ar(b)[:, None, None] * S + ar(s)[None, :, None]) * H + ar(H)
+        if site == "attention_probs":
+            b, h, q, k = shape
+            assert h == nh
+            Sk = S if self.Sp is None else self.Sp
+            row = (ar(b)[:, None, None] * nh + ar(h)[None, :, None]) * S + ar(q)[None, None, :]
+            return layer * 8 + 0, row[..., None] * Sk + ar(k)
+        if site in ("attention_output", "ffn_output"):
+            b, s, H = shape
+            m = ar(b)[:, None] * S + ar(s)[None, :]
+            return layer * 8 + (1 if site == "attention_output" else 2), m[..., None] * H + ar(H)
+        if site == "obj_downsample":
+            K, E = shape
+            assert E == 4096
+            rows = inds[:, 0].numpy().astype(np.int64) * R + inds[:, 1].numpy().astype(np.int64)
+            return TAG_DOWNSAMPLE, rows[:, None] * E + ar(E)
+        raise ValueError("unknown dropout site %r" % (site,))
+
+    def __call__(self, site, prob, shape, layer=None, inds=None):
+        tag, idx = self.index(site, shape, layer, inds)
+        thr = self.thr(prob)
+        self.sites.append((site, layer))
+        keep = keep_mask(self.seed, tag, idx.reshape(-1), thr).reshape(idx.shape)
+        return torch.from_numpy(keep.astype(np.float32) * np.float32(self.scale(thr)))

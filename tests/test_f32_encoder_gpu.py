@@ -226,7 +226,7 @@ def test_softmax_f32_mask_dropout_fwd_bwd():
     assert _rel(dg[:, :S], ref) < 1e-5 and float(dg[:, S:].abs().max()) == 0.0
 
 
-def _engine_case(layers, large, B, T, R, seed, tag):
+def _engine_case(layers, large, B, T, R, seed, tag, train=False):
     from tests.test_engine_gpu import _per_layer_report, check_against_oracle
     syn = pkg("synthetic")
     kw = dict(hidden_size=1024, num_attention_heads=16, intermediate_size=4096) if large else {}
@@ -238,7 +238,8 @@ def _engine_case(layers, large, B, T, R, seed, tag):
     # roundings are 2^-9 each and the same code sits at ~6e-3
     bar = 1e-3 if f16 else 8e-3
     eng = check_against_oracle(tag, cfg, params, batch, grad_tol=2e-2 if f16 else 6e-2, logit_rtol=bar, logit_fro_tol=bar,
-                               engine_kw=dict(encoder_fp32=True), loss_tol=1e-3, norm_tol=1e-3 if f16 else 5e-3)
+                               engine_kw=dict(encoder_fp32=True), loss_tol=1e-3, norm_tol=1e-3 if f16 else 5e-3, train=train,
+                               front_tol=0.12 if train else None)
     rows = _per_layer_report(tag, eng, eng.oracle_result[2], eng.oracle_result[3], layers)
     assert max(e for _, e in rows) <= (2e-3 if f16 else 2e-2), rows
     return eng
@@ -247,6 +248,16 @@ def _engine_case(layers, large, B, T, R, seed, tag):
 def test_engine_fp32_encoder_base_2_layers_vs_oracle():
     """In-process (whatever build the suite runs on): the fp32 encoder inside the engine, 2 base layers."""
     _engine_case(2, False, 3, 32, 10, 301, "fp32-encoder base 2-layer")
+
+
+def test_engine_fp32_encoder_base_2_layers_train_mode_vs_oracle():
+    """The same case with dropout on: the fp32 encoder's own mask sites -- softmax_f32 on rows of the padded key stride Sp, the
+    _linear dropout epilogues and layernorm_f32_bwd's dx_drop (vl-bert_amd/encoder_f32.py:157-206) -- against the oracle under the
+    masks the engine regenerates, the fp32 bars of the eval test.  The 16-bit front end's few-box tensors (FRONT_TENSORS of
+    tests/test_engine_gpu.py: ReLU flips of obj_downsample, not the encoder; measured 6.8e-2 here, 6.6e-2 with the bf16 encoder on the
+    same batch) are bounded as in the other train-mode tests."""
+    eng = _engine_case(2, False, 3, 32, 10, 301, "fp32-encoder base 2-layer train", train=True)
+    assert eng.enc32.Sp > eng.S          # S = 43 -> Sp = 64: the padded stride is what the index uses
 
 
 def test_engine_fp32_encoder_training_step_runs():

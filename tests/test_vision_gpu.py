@@ -17,7 +17,8 @@ import torch.nn.functional as F
 from oracle import roi_align_oracle as RA
 from oracle import vision_oracle as VO
 from oracle import vlbert_oracle as O
-from tests.gpu_util import bf, dev, drop_scale, drop_thr, keep_mask, pkg, report, to_gpu_bf16
+from tests.gpu_util import bf, dev, device_seed, drop_scale, drop_thr, keep_mask, pkg, report, rng_advance, to_gpu_bf16
+from tests.test_engine_gpu import WRONG_SEED_FACTOR, oracle_masks, parity_line
 
 pytestmark = pytest.mark.gpu
 
@@ -444,10 +445,12 @@ def _vision_grad_errors(eng, Po, names):
     return errs, (num / rn) ** 0.5, abs(gn ** 0.5 - rn ** 0.5) / rn ** 0.5
 
 
-@pytest.mark.parametrize("empty_sample", [False, True])
-def test_engine_e2e_step_vs_oracle(empty_sample):
+@pytest.mark.parametrize("empty_sample,train", [(False, False), (True, False), (True, True)], ids=["False", "True", "train"])
+def test_engine_e2e_step_vs_oracle(empty_sample, train):
     """One e2e pretraining step (image -> CNN -> VL-BERT -> losses -> gradients) of the engine against the composed oracle.
-    empty_sample: the second image has no valid box at all (every RoI slot padded)."""
+    empty_sample: the second image has no valid box at all (every RoI slot padded).  train: dropout on in both, the oracle under the
+    masks the engine regenerates -- the obj_downsample mask reaches the CNN through vision.backward / avgpool_rows_bwd instead of
+    masked_colsum; same bars, and the oracle under another seed's masks must miss them."""
     E, syn = pkg("engine"), pkg("synthetic")
     z, nl, P = _vision_fixture()
     img, boxes4 = torch.from_numpy(z["img"]), torch.from_numpy(z["boxes"]).clone()
@@ -464,20 +467,27 @@ def test_engine_e2e_step_vs_oracle(empty_sample):
     batch[5][pad] = 0                                                     # mvrc_ops / labels of the padded box
     batch[6][pad] = 0
     mc = E.ModelConfig(num_hidden_layers=1, e2e=True, image_num_layers=nl)
-    eng = E.PretrainEngine(mc, B, T, R, device="cuda:0", train=False, keep_logits=True, image_size=tuple(img.shape[2:]))
+    eng = E.PretrainEngine(mc, B, T, R, device="cuda:0", train=train, keep_logits=True, image_size=tuple(img.shape[2:]))
     sd = {k: v.to(dev()) for k, v in params.items()}
     sd.update({k: v.to(dev()) for k, v in _prefixed(P).items()})
     eng.load_state_dict(sd)
     eng.set_batch(*[t.to(dev()) for t in batch], image=img.to(dev()))
+    seed = device_seed(eng)
     eng.zero_grad()
-    eng.forward(False)
-    eng.backward(False)
+    eng.forward(train)
+    eng.backward(train)
     torch.cuda.synchronize()
     frozen = VO.frozen_names(P)
-    leaves = {k: v.clone().requires_grad_(True) for k, v in params.items()}
-    Po = {k: v.clone().requires_grad_(k not in frozen) for k, v in P.items()}
-    out, loss = O.pretrain_forward(leaves, cfg, *batch, train=False, image=img, vision_params=Po, image_num_layers=nl)
-    loss.backward()
+
+    def oracle(s):
+        leaves = {k: v.clone().requires_grad_(True) for k, v in params.items()}
+        Po = {k: v.clone().requires_grad_(k not in frozen) for k, v in P.items()}
+        hook = oracle_masks(eng, s) if train else None
+        out, loss = O.pretrain_forward(leaves, cfg, *batch, train=train, image=img, vision_params=Po, image_num_layers=nl, drop_hook=hook)
+        loss.backward()
+        return leaves, Po, out
+
+    leaves, Po, out = oracle(seed)
     lv = eng.loss_values()
     print("e2e losses: hip mlm %.5f mvrc %.5f | oracle mlm %.5f mvrc %.5f" % (lv["mlm_loss"], lv["mvrc_loss"], float(out["mlm_loss"].detach()),
                                                                               float(out["mvrc_loss"].detach())))
@@ -495,6 +505,15 @@ def test_engine_e2e_step_vs_oracle(empty_sample):
         e = rel_fro(eng.g32[k], leaves[k].grad)
         print("  %s rel-fro %.3e" % (k, e))
         assert e < 5e-2, k
+    if train:      # tells masks apart: the oracle under the next seed's masks misses the bars by >= WRONG_SEED_FACTOR
+        wl, wPo, _ = oracle(rng_advance(seed))
+        werrs, _, _ = _vision_grad_errors(eng, wPo, names)
+        wmed = float(np.median([e for e, _ in werrs]))
+        wk = {k: rel_fro(eng.g32[k], wl[k].grad) for k in ("image_feature_extractor.obj_downsample.1.weight",
+                                                           "vlbert.encoder.layer.0.output.dense.weight")}
+        parity_line("e2e train", "e2e train: wrong-seed masks: conv weight gradients median rel-fro %.3e (bar 5.5e-2); %s" % (
+            wmed, "  ".join("%s %.3e (bar 5e-2)" % kv for kv in wk.items())))
+        assert wmed >= WRONG_SEED_FACTOR * 5.5e-2 or max(wk.values()) >= WRONG_SEED_FACTOR * 5e-2, (wmed, wk)
     # one optimizer step moves the trainable convolutions and leaves the frozen stages / BatchNorm alone
     before = eng.vision.state_dict()
     eng.optimizer_step()
