@@ -172,7 +172,8 @@ int vlb_masked_colsum(const void* src, long lds, const int64_t* sel, int rows, i
 /* fused embedding forward: word/visual/linguistic sum + position + token-type -> LayerNorm -> dropout.
  * text_vis / obj_vis / obj_ling are bf16 with element strides (batch, position); when obj_ling_idx
  * (int64 [B,R]) is non-NULL obj_ling is a table [n,H] indexed by it.  Saves `pre` (bf16 pre-LN sum)
- * and stats for backward. */
+ * and stats for backward.  Out-of-range ids are clamped, identically in forward and backward: token ids to [0, V-1], position ids to
+ * [0, P-1], text token-type ids (text_type, NULL = all 0) to the 3-row table [0, 2]. */
 int vlb_embed_fwd(const int32_t* code, const int32_t* text_len, const int64_t* text_ids, const int64_t* text_type,
                   const void* word_emb, const void* pos_emb, const void* type_emb, const void* end_emb,
                   const void* text_vis, long tv_sb, long tv_st, const void* obj_vis, long ov_sb, long ov_sr,

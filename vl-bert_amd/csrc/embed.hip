@@ -175,6 +175,10 @@ struct EmbedParams {
   uint32_t drop_thr; float drop_scale; const uint32_t* seed; uint32_t tag;
 };
 
+// token-type id of a text token, clamped to the 3-row table [0, 2] -- the SAME clamp in forward and backward (the backward used to
+// fold every id outside {0, 1} into row 2 while the forward indexed the table with the raw id, i.e. read past it for id > 2)
+__device__ __forceinline__ int clamp_type_id(int64_t t) { return t < 0 ? 0 : (t > 2 ? 2 : (int)t); }
+
 __device__ __forceinline__ void add_row_bf16(const bf16_t* src, int H, int lane, float (*acc)[4]) {
 #pragma unroll
   for (int i = 0; i < EMB_MAX_IT; ++i) {
@@ -203,7 +207,7 @@ __global__ __launch_bounds__(256) void embed_fwd_kernel(const EmbedParams p) {
     id = id < 0 ? 0 : (id >= p.V ? p.V - 1 : id);
     add_row_bf16(p.word_emb + id * H, H, lane, acc);
     add_row_bf16(p.text_vis + b * p.tv_sb + idx * p.tv_st, H, lane, acc);
-    type_id = p.text_type ? (int)p.text_type[b * p.T + idx] : 0;
+    type_id = p.text_type ? clamp_type_id(p.text_type[b * p.T + idx]) : 0;
   } else if (kind == KIND_OBJ) {
     add_row_bf16(p.obj_vis + b * p.ov_sb + idx * p.ov_sr, H, lane, acc);
     if (p.obj_ling_idx)
@@ -398,7 +402,7 @@ __global__ __launch_bounds__(512) void embed_bwd_kernel(const EmbedBwdParams p) 
       long id = p.text_ids[b * p.T + idx];
       id = id < 0 ? 0 : (id >= p.V ? p.V - 1 : id);
       w_dst = p.d_word + id * H;
-      type_id = p.text_type ? (int)p.text_type[b * p.T + idx] : 0;
+      type_id = p.text_type ? clamp_type_id(p.text_type[b * p.T + idx]) : 0;
       if (p.d_text_vis && p.dtv_st != 0) v_dst = p.d_text_vis + b * p.dtv_sb + idx * p.dtv_st;      // (dtv_st == 0: per-sample sum, below)
     } else if (kind == KIND_OBJ) {
       type_id = 2;
@@ -426,7 +430,7 @@ __global__ __launch_bounds__(512) void embed_bwd_kernel(const EmbedBwdParams p) 
           if (ukind == KIND_TEXT) {
             if (utype == 0) t0[i][k] += d[k];
             else if (utype == 1) t1[i][k] += d[k];
-            else {                                                                       // (a text token of type 2: no caller produces one)
+            else {                                                                       // (a text token of type 2, or clamped to it)
               atomicAdd(l_type + 2 * LWD + (i * 4 + k) * 64 + lane, d[k]);
               if (p.d_text_vis && p.dtv_st == 0) atomicAdd(l_tv + (i * 4 + k) * 64 + lane, d[k]);
             }
