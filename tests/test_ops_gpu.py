@@ -1338,3 +1338,115 @@ def test_layernorm_bwd_deferred_parameter_gradients_batched(ops):
     assert ops.layernorm_bwd(dy, x, stats, gamma, dgamma=dg, dbeta=db, workspace=ws, defer=True) == 0
     torch.cuda.synchronize()
     assert float((db - dy.float().sum(0)).abs().max()) < 1e-2
+
+
+# ------------------------------------------------------------------------------------ ranged copy, scale, casts
+def test_copy_ranges_pack_unpack(ops):
+    """vlb_copy_ranges_f32 (pack / unpack of the fp32-read parameters of the sharded optimizer): lengths below, at and above the
+    1024-float block of block_start, unordered and non-adjacent offsets, 16-byte aligned on both sides / one side / neither (the
+    kernel takes a vector or a scalar path per thread).  Equal to the plain indexed copy, everything outside the ranges untouched,
+    pack + inverse unpack restores the source, an empty table launches nothing."""
+    rows = [(9000, 17, 1), (0, 7000, 1023), (4003, 100, 1024), (2000, 3000, 1025), (10000, 9001, 5000)]      # (src, dst, length)
+    n = 16000
+    src = torch.randn(n, generator=torch.Generator().manual_seed(70))
+    want = torch.full((n,), -7.0)
+    for s, d, ln in rows:
+        want[d:d + ln] = src[s:s + ln]
+    srcg = src.to(dev())
+    dst = torch.full((n,), -7.0, device=dev())
+    pack = ops.CopyRanges(rows + [(5, 6, 0)], dev())           # (an empty row is dropped on the host)
+    assert pack.n == len(rows) and pack.total == 1 + 1 + 1 + 2 + 5
+    pack.run(srcg, dst)
+    assert torch.equal(dst.cpu(), want)
+    assert torch.equal(srcg.cpu(), src)
+    back = torch.full((n,), -9.0, device=dev())
+    ops.CopyRanges([(d, s, ln) for s, d, ln in rows], dev()).run(dst, back)
+    restored = torch.full((n,), -9.0)
+    for s, d, ln in rows:
+        restored[s:s + ln] = src[s:s + ln]
+    assert torch.equal(back.cpu(), restored)
+    empty = ops.CopyRanges([], dev())
+    assert empty.n == 0 and empty.total == 0
+    empty.run(srcg, back)
+    ops.CopyRanges([(1, 2, 0)], dev()).run(srcg, back)
+    assert torch.equal(back.cpu(), restored)
+
+
+@pytest.mark.parametrize("off", [0, 1])
+@pytest.mark.parametrize("n", [1, 3, 1024, 4099])
+def test_scale_f32_exact(ops, n, off):
+    """x *= alpha is one fp32 multiply per element: bit-identical to torch's, for a view that starts 16-byte aligned or not; the
+    elements around the view keep their contents."""
+    alpha = float(np.float32(0.3))
+    x = torch.randn(n + off + 5, generator=torch.Generator().manual_seed(71 + n)) * 100
+    want = x.clone()
+    want[off:off + n] = x[off:off + n] * torch.tensor(alpha, dtype=torch.float32)
+    buf = x.to(dev())
+    ops.scale_f32(buf[off:off + n], alpha)
+    assert torch.equal(buf.cpu(), want), "max diff %g" % float((buf.cpu() - want).abs().max())
+
+
+def _cast_specials():
+    """fp32 inputs at which a conversion to the library's 16-bit type can go wrong."""
+    fi = torch.finfo(act_dtype())
+    eps, big, tiny = fi.eps, fi.max, fi.tiny                   # 16-bit: spacing at 1, largest finite, smallest normal
+    sub = tiny * eps                                           # smallest 16-bit subnormal
+    f32 = lambda v: torch.tensor(v, dtype=torch.float64).float()
+    nxt = lambda v, d: torch.nextafter(f32(v), f32(d))
+    ulp_big = big * eps / (2.0 - eps)                          # 16-bit spacing below `big` = (2 - eps) 2^emax
+    vals = [f32(1.0 + eps / 2), f32(-(1.0 + eps / 2)),         # ties: 1 (even) | 1 + eps -> down to 1
+            f32(1.0 + 1.5 * eps), f32(-(1.0 + 1.5 * eps)),     # ties: 1 + eps | 1 + 2 eps (even) -> up
+            nxt(1.0 + eps / 2, 2.0), nxt(1.0 + eps / 2, 0.0),  # just above / below a tie
+            nxt(1.0 + 1.5 * eps, 2.0), nxt(1.0 + 1.5 * eps, 0.0),
+            f32(0.0), f32(-0.0),
+            f32(big), f32(-big), nxt(big, float("inf")), nxt(-big, float("-inf")),      # largest finite and the first fp32 beyond it
+            f32(big + ulp_big / 2), nxt(big + ulp_big / 2, 0.0),                        # tie between `big` (odd) and 2^emax: -> inf | just below: big
+            f32(tiny), nxt(tiny, 0.0), f32(sub), f32(-sub), f32(sub / 2), nxt(sub / 2, 1.0), f32(1.5 * sub), f32(2.5 * sub), f32(0.75 * sub),
+            f32(1e-40), f32(-1e-40), f32(1.4e-45),                                       # fp32 subnormals
+            f32(float("inf")), f32(float("-inf")), f32(float("nan"))]
+    return torch.stack(vals)
+
+
+@pytest.mark.parametrize("n", [1, 7, 8, 4099])
+def test_cast_f32_to_16bit_rounds_like_torch(ops, n):
+    """vlb_cast_f32_bf16 == x.to(the 16-bit type): round to nearest even, bit for bit (+-0 included), NaN stays NaN; every special
+    value visits the vector body and the scalar tail of the kernel (n = 7: one of each; 4099: three tail elements); the buffer behind
+    the n elements is untouched."""
+    sp = _cast_specials()
+    g = torch.Generator().manual_seed(72)
+    pool = torch.cat((sp, torch.randn(61, generator=g), torch.randn(32, generator=g) * 1e-3, torch.randn(32, generator=g) * 3e4))
+    for shift in range(0, len(sp) + 3, 3 if n > 1 else 1):
+        x = pool[(torch.arange(n) + shift - n // 4 * 4) % len(pool)]          # pool[shift:] starts the scalar tail (if n has one)
+        want = x.to(act_dtype())
+        dst = torch.full((n + 9,), -3.0, dtype=act_dtype(), device=dev())
+        ops.cast_f32_bf16(x.to(dev()), dst[:n])
+        got = dst.cpu()
+        nan = torch.isnan(want)
+        assert torch.equal(torch.isnan(got[:n]), nan), "shift %d: NaN positions differ" % shift
+        gb, wb = got[:n].view(torch.int16)[~nan], want.view(torch.int16)[~nan]
+        bad = (gb != wb).nonzero().flatten()
+        assert bad.numel() == 0, "shift %d: %d differ, first: fp32 %r -> %r, torch %r" % (
+            shift, bad.numel(), float(x[~nan][bad[0]]), float(got[:n][~nan][bad[0]]), float(want[~nan][bad[0]]))
+        assert float((got[n:].float() + 3.0).abs().max()) == 0.0, "elements past n were written"
+
+
+def test_cast_16bit_to_f32_every_pattern(ops):
+    """vlb_cast_bf16_f32 over all 65 536 bit patterns of the 16-bit type: every finite one (subnormals, +-0 included) equals .float()
+    bit for bit, infinities keep their sign and NaNs stay NaN; short odd lengths from an odd start; the buffer tail stays untouched."""
+    pat = torch.arange(65536, dtype=torch.int32).to(torch.int16).view(act_dtype())
+    want = pat.float()
+    src = pat.to(dev())
+    dst = torch.full((65536 + 8,), -3.0, device=dev())
+    ops.cast_bf16_f32(src, dst[:65536])
+    got = dst.cpu()
+    nan = torch.isnan(want)
+    assert int(torch.isfinite(want).sum()) > 63000 and torch.equal(torch.isnan(got[:65536]), nan)
+    assert torch.equal(got[:65536].view(torch.int32)[~nan], want.view(torch.int32)[~nan])
+    assert float((got[65536:] + 3.0).abs().max()) == 0.0
+    for n in (1, 7, 8, 4099):
+        lo = 0x3001                                            # odd element offset; finite patterns in both 16-bit types
+        dst = torch.full((n + 8,), -3.0, device=dev())
+        ops.cast_bf16_f32(src[lo:lo + n], dst[:n])
+        got = dst.cpu()
+        assert torch.equal(got[:n].view(torch.int32), want[lo:lo + n].view(torch.int32)), n
+        assert float((got[n:] + 3.0).abs().max()) == 0.0, n

@@ -7,6 +7,7 @@ Tolerances: bf16 activations (2^-8 per rounding) through up to 19 Bottlenecks: f
 weight gradients by relative Frobenius error per tensor (ReLU sign flips of bf16-vs-fp32 pre-activations near 0 add gradient
 noise that is not a kernel error, cf. tests/test_engine_gpu.py).
 """
+import functools
 import os
 
 import numpy as np
@@ -17,7 +18,7 @@ import torch.nn.functional as F
 from oracle import roi_align_oracle as RA
 from oracle import vision_oracle as VO
 from oracle import vlbert_oracle as O
-from tests.gpu_util import bf, dev, device_seed, drop_scale, drop_thr, keep_mask, pkg, report, rng_advance, to_gpu_bf16
+from tests.gpu_util import act_dtype, bf, dev, device_seed, drop_scale, drop_thr, keep_mask, pkg, report, rng_advance, to_gpu_bf16
 from tests.test_engine_gpu import WRONG_SEED_FACTOR, oracle_masks, parity_line
 
 pytestmark = pytest.mark.gpu
@@ -351,6 +352,289 @@ def test_conv3x3_forward_dgrad_wgrad_vs_autograd(ops, dil):
     g32 = torch.zeros((O, 9 * I), device=dev())
     ops.conv_wgrad_finalize(dwf, scale, g32, accumulate=True)
     report("conv3x3 d%d wgrad of the master weight" % dil, g32.view(O, 3, 3, I).permute(0, 3, 1, 2), wq.grad * scale.cpu().view(O, 1, 1, 1), 1e-3, 2e-3)
+
+
+# ---- row-scaled weight gradients: what VisionStack._wgrad calls (the frozen-BatchNorm scale applied by the split-K slab reduce) -----
+def _round_up(n, m):
+    return (n + m - 1) // m * m
+
+
+def _random_rowscale(Mo, seed):
+    """0.25 + 1.5 * rand with a few negative rows: a missing, doubled or misplaced scale is far outside any rounding tolerance."""
+    rs = 0.25 + 1.5 * torch.rand(Mo, generator=torch.Generator().manual_seed(seed))
+    rs[1::max(Mo // 3, 2)] *= -1.0
+    return rs
+
+
+def _pow2_rowscale(Mo):
+    """rs[m] = +-2^k, k = (7 m) % 5 - 2, the sign flipped on every third row: multiplying by it is exact in fp32."""
+    m = torch.arange(Mo)
+    return torch.pow(2.0, ((7 * m) % 5 - 2).float()) * torch.where(m % 3 == 2, -1.0, 1.0)
+
+
+def _wgrad_workspace(ops, Mo, No, R):
+    """What vlb_wgrad_workspace_floats asks for, at least the one slab a row scale forces; NaN-filled: a slab element that is read
+    without having been written shows in the result."""
+    n = max(ops.wgrad_workspace_floats(Mo, No, _round_up(R, 64)), Mo * _round_up(No, 4), 4)
+    return torch.full((n,), float("nan"), dtype=torch.float32, device=dev())
+
+
+class _tn8_mode:
+    """Large-tile weight-gradient core on (what VLB_GEMM_TN8 says, default 1) or off for the calls inside the block."""
+
+    def __init__(self, mode):
+        self.mode = mode
+
+    def __enter__(self):
+        if self.mode is not None:
+            pkg("_lib").gemm_set_option("tn8_mode", self.mode)
+
+    def __exit__(self, *exc):
+        if self.mode is not None:
+            pkg("_lib").gemm_set_option("tn8_mode", int(os.environ.get("VLB_GEMM_TN8", "1")))
+
+
+# (R, Mo, No, tn8).  The first three stay on the 128x128 TN kernel (R = 7840 = 40 boxes x 14 x 14 is not a multiple of 128).  So do
+# (4096, 768, 768) and (2560, 1000, 520): the large-tile core's own cost model picks 8 / 10 K slices for them, 72 / 120 work items,
+# fewer than the 128 it wants.  The last two do run on the large-tile core (240 / 150 items): (4096, 30522, 64) from
+# test_wgrad_tn_lds_transpose_reads and (2560, 1500, 1030), ragged in both output dimensions with No % 4 == 2; tn8 = 0 sends the
+# same shapes through the 128x128 kernel.
+WGRAD_ROWSCALE_SHAPES = [(300, 70, 198, None), (64, 128, 128, None), (7840, 512, 1024, None), (4096, 768, 768, None),
+                         (2560, 1000, 520, None), (4096, 30522, 64, None), (4096, 30522, 64, 0), (2560, 1500, 1030, None),
+                         (2560, 1500, 1030, 0)]
+
+
+def _wgrad_rowscale_buffers(R, Mo, No, dY, X):
+    """Device operands as column slices of wider buffers whose padding holds junk (9.0 / 7.0), and an fp32 output buffer with
+    junk (5.0) pad columns: lda = round64(Mo), ldb = round8(No), ldc = round4(No)."""
+    dYg = torch.full((R, _round_up(Mo, 64)), 9.0, dtype=act_dtype(), device=dev())
+    Xg = torch.full((R, _round_up(No, 8)), 7.0, dtype=act_dtype(), device=dev())
+    dYg[:, :Mo] = dY
+    Xg[:, :No] = X
+    C = torch.full((Mo, _round_up(No, 4)), 5.0, dtype=torch.float32, device=dev())
+    return dYg[:, :Mo], Xg[:, :No], C
+
+
+@functools.lru_cache(maxsize=1)
+def _wgrad_rowscale_case(R, Mo, No):
+    """Host operands and the fp64 reference of one shape, shared by the runs of that shape on either core (read-only)."""
+    dY, X = rnd(R, Mo, seed=18), rnd(R, No, seed=19, scale=0.2)
+    rs = _random_rowscale(Mo, 21)
+    base = torch.randn(Mo, No, generator=torch.Generator().manual_seed(20))
+    return dY, X, rs, base, rs.double()[:, None] * (dY.double().t() @ X.double())
+
+
+@pytest.mark.parametrize("R,Mo,No,tn8", WGRAD_ROWSCALE_SHAPES)
+def test_wgrad_tn_rowscale_vs_fp64(ops, R, Mo, No, tn8):
+    """vlb_wgrad_tn_rowscale_bf16 (every 1x1 weight gradient of the vision path that is not deferred into a table launch) against
+    rs[:, None] * (dY^T X) in fp64 on the same 16-bit operands: accumulate on a random base, overwrite of a 3.0-filled buffer,
+    overwrite twice (bit-identical), pad columns of C untouched.  The bound is the unscaled product's (test_wgrad_tn_lds_transpose_reads):
+    the scale adds one fp32 multiply."""
+    dY, X, rs, base, ref = _wgrad_rowscale_case(R, Mo, No)
+    a, b, C = _wgrad_rowscale_buffers(R, Mo, No, to_gpu_bf16(dY), to_gpu_bf16(X))
+    ws = _wgrad_workspace(ops, Mo, No, R)
+    rsg = rs.to(dev())
+    tag = "wgrad TN rowscale %dx%dx%d%s" % (R, Mo, No, "" if tn8 is None else " tn8=%d" % tn8)
+    with _tn8_mode(tn8):
+        C[:, :No] = base.to(dev())
+        ops.wgrad_tn_rowscale(a, b, C[:, :No], rsg, ws, accumulate=True)
+        report(tag + " accumulate", C[:, :No], base.double() + ref, 1e-3, 2e-5)
+        C[:, :No] = 3.0
+        ops.wgrad_tn_rowscale(a, b, C[:, :No], rsg, ws, accumulate=False)
+        report(tag + " overwrite", C[:, :No], ref, 1e-3, 2e-5)
+        first = C.clone()
+        ops.wgrad_tn_rowscale(a, b, C[:, :No], rsg, ws, accumulate=False)
+        torch.cuda.synchronize()
+    assert torch.equal(C, first), "overwrite mode is not idempotent"
+    if C.shape[1] > No:
+        assert float((C[:, No:] - 5.0).abs().max()) == 0.0, "pad columns of C were written"
+
+
+@pytest.mark.parametrize("R,Mo,No,tn8", WGRAD_ROWSCALE_SHAPES)
+def test_wgrad_tn_rowscale_power_of_two_scale_is_exact(ops, R, Mo, No, tn8):
+    """With rs[m] = +-2^k the scaled result must equal rs[:, None] * U (overwrite) and base + rs[:, None] * U (accumulate) BIT FOR BIT,
+    U = the unscaled vlb_wgrad_tn_bf16 on the same operands and workspace: the split plan takes shapes only, a one-slice slab adds
+    nothing, and an FMA of an exact product rounds like the two operations.  A scale read from another row, applied per slab, or a
+    slab walked with the wrong leading dimension cannot hide in a tolerance here."""
+    g = torch.Generator(device=dev()).manual_seed(1000 + R)
+    dY = torch.randn((R, Mo), generator=g, device=dev()).to(act_dtype())
+    X = (torch.randn((R, No), generator=g, device=dev()) * 0.2).to(act_dtype())
+    base = torch.randn((Mo, No), generator=g, device=dev())
+    a, b, C = _wgrad_rowscale_buffers(R, Mo, No, dY, X)
+    ws = _wgrad_workspace(ops, Mo, No, R)
+    rs = _pow2_rowscale(Mo).to(dev())
+    with _tn8_mode(tn8):
+        ops.wgrad_tn(a, b, C[:, :No], workspace=ws, accumulate=False)
+        U = C[:, :No].clone()
+        C[:, :No] = 3.0
+        ops.wgrad_tn_rowscale(a, b, C[:, :No], rs, ws, accumulate=False)
+        over = C[:, :No].clone()
+        C[:, :No] = base
+        ops.wgrad_tn_rowscale(a, b, C[:, :No], rs, ws, accumulate=True)
+        torch.cuda.synchronize()
+    assert float(U.abs().max()) > 1.0 and bool(torch.isfinite(U).all())
+    want = rs[:, None] * U
+    assert torch.equal(over, want), "overwrite: %d elements differ, max %g" % (int((over != want).sum()), float((over - want).abs().max()))
+    want = base + rs[:, None] * U
+    got = C[:, :No]
+    assert torch.equal(got, want), "accumulate: %d elements differ, max %g" % (int((got != want).sum()), float((got - want).abs().max()))
+    if C.shape[1] > No:
+        assert float((C[:, No:] - 5.0).abs().max()) == 0.0, "pad columns of C were written"
+
+
+@pytest.mark.parametrize("Mo,No", [(128, 128), (128, 126)])
+def test_wgrad_tn_rowscale_refuses_a_short_workspace(ops, Mo, No):
+    """A row scale always goes through a slab: one float less than Mo * round4(No) is refused on the host, nothing is launched."""
+    R = 64
+    a, b, C = _wgrad_rowscale_buffers(R, Mo, No, to_gpu_bf16(rnd(R, Mo, seed=18)), to_gpu_bf16(rnd(R, No, seed=19)))
+    rs = _random_rowscale(Mo, 21).to(dev())
+    ws = torch.zeros(Mo * _round_up(No, 4) - 1, device=dev())
+    with pytest.raises(RuntimeError, match="rowscale needs a workspace"):
+        ops.wgrad_tn_rowscale(a, b, C[:, :No], rs, ws, accumulate=False)
+    torch.cuda.synchronize()
+    assert float((C - 5.0).abs().max()) == 0.0 and float(ws.abs().max()) == 0.0
+    ops.wgrad_tn_rowscale(a, b, C[:, :No], rs, torch.zeros(Mo * _round_up(No, 4), device=dev()), accumulate=False)      # exactly enough
+    assert float((C[:, :No] - 5.0).abs().min()) > 0.0
+
+
+def _im2col_3x3_cpu(x, dil):
+    """[N,C,H,W] -> [N*H*W, 9C], tap-major (the layout test_im2col_nhwc derives): 3x3, stride 1, padding = dilation."""
+    N, C, H, W = x.shape
+    return F.unfold(x, 3, dilation=dil, padding=dil).view(N, C, 9, H * W).permute(0, 3, 2, 1).reshape(N * H * W, 9 * C)
+
+
+# (N, C, O, H, W, dil, taps that lie outside the map for EVERY pixel)
+CONV_WGRAD_ROWSCALE_CASES = [(2, 128, 128, 14, 11, 1, 0), (2, 128, 128, 14, 11, 2, 0), (3, 128, 72, 5, 4, 2, 0), (2, 128, 64, 2, 3, 2, 6),
+                             (4, 128, 64, 1, 1, 1, 8), (40, 512, 512, 14, 14, 2, 0)]
+
+
+@pytest.mark.parametrize("N,C,O,H,W,dil,ndead", CONV_WGRAD_ROWSCALE_CASES)
+def test_conv3x3_wgrad_tn_rowscale_vs_fp64(ops, N, C, O, H, W, dil, ndead):
+    """vlb_conv3x3_wgrad_tn_bf16 with a row scale (every 3x3 weight gradient of the implicit path) against rs[:, None] * (dy^T col) in
+    fp64, col = the im2col image built on the host; accumulate and overwrite.  Then the exact form: with a power-of-two scale the
+    result equals rs[:, None] * U (+ base) bit for bit, U = the same call with rowscale=None (itself pinned bit-for-bit to wgrad_tn over
+    the explicit im2col image by test_conv3x3_implicit_equals_explicit_at_size).  Row counts that are no multiple of 64, O that is no
+    multiple of 64 behind a junk-padded lddy = 128 slice with a padded lddw, maps no larger than the dilation (2x3 at dilation 2: six
+    taps are outside for every pixel; 1x1: all but the centre) whose dead column blocks must stay exactly base / 0, and the layer4
+    geometry of the step.  The one-pixel and the 2x3 maps are computed, not rejected: no argument check excludes them."""
+    M = N * H * W
+    x = rnd(N, C, H, W, seed=50)
+    dy = rnd(M, O, seed=51)
+    col = _im2col_3x3_cpu(x, dil)
+    live = (_im2col_3x3_cpu(torch.ones(1, 1, H, W), dil).view(H * W, 9) != 0).any(0)          # per tap: inside the map for some pixel
+    assert int((~live).sum()) == ndead
+    prod = dy.double().t() @ col.double()
+    dead_cols = (~live)[:, None].expand(9, C).reshape(-1)
+    if ndead:
+        assert float(prod[:, dead_cols].abs().max()) == 0.0
+    xg = to_gpu_bf16(nhwc(x))
+    lddy = _round_up(O, 64) if O % 64 else O
+    dyb = torch.full((M, lddy), 9.0, dtype=act_dtype(), device=dev())
+    dyb[:, :O] = to_gpu_bf16(dy)
+    dyg = dyb[:, :O]
+    pad = 4 if O % 64 else 0
+    dWb = torch.full((O, 9 * C + pad), 5.0, dtype=torch.float32, device=dev())
+    dW = dWb[:, :9 * C]
+    ws = _wgrad_workspace(ops, O, 9 * C, M)
+    base = torch.randn(O, 9 * C, generator=torch.Generator().manual_seed(52))
+    tag = "conv3x3 wgrad rowscale N%d C%d O%d %dx%d d%d" % (N, C, O, H, W, dil)
+    rs = _random_rowscale(O, 53)
+    ref = rs.double()[:, None] * prod
+    dW.copy_(base)
+    ops.conv3x3_wgrad_tn(dyg, xg, dW, N, H, W, C, dil, workspace=ws, accumulate=True, rowscale=rs.to(dev()))
+    report(tag + " accumulate", dW, base.double() + ref, 1e-3, 2e-5)
+    if ndead:
+        assert torch.equal(dW.cpu()[:, dead_cols], base[:, dead_cols]), "a tap outside the map changed its gradient block"
+    dW.fill_(3.0)
+    ops.conv3x3_wgrad_tn(dyg, xg, dW, N, H, W, C, dil, workspace=ws, accumulate=False, rowscale=rs.to(dev()))
+    report(tag + " overwrite", dW, ref, 1e-3, 2e-5)
+    if ndead:
+        assert float(dW[:, dead_cols.to(dev())].abs().max()) == 0.0, "a tap outside the map has a non-zero gradient block"
+    # exact form
+    p2 = _pow2_rowscale(O).to(dev())
+    ops.conv3x3_wgrad_tn(dyg, xg, dW, N, H, W, C, dil, workspace=ws, accumulate=False)
+    U = dW.clone()
+    report(tag + " unscaled", U, prod, 1e-3, 2e-5)
+    dW.fill_(3.0)
+    ops.conv3x3_wgrad_tn(dyg, xg, dW, N, H, W, C, dil, workspace=ws, accumulate=False, rowscale=p2)
+    over = dW.clone()
+    dW.copy_(base)
+    ops.conv3x3_wgrad_tn(dyg, xg, dW, N, H, W, C, dil, workspace=ws, accumulate=True, rowscale=p2)
+    torch.cuda.synchronize()
+    want = p2[:, None] * U
+    assert torch.equal(over, want), "overwrite: %d elements differ, max %g" % (int((over != want).sum()), float((over - want).abs().max()))
+    want = base.to(dev()) + p2[:, None] * U
+    assert torch.equal(dW, want), "accumulate: %d elements differ, max %g" % (int((dW != want).sum()), float((dW - want).abs().max()))
+    if pad:
+        assert float((dWb[:, 9 * C:] - 5.0).abs().max()) == 0.0, "pad columns of dW were written"
+
+
+def test_conv_prepare_batch_equals_single_item_kernel_and_fp64_fold(ops):
+    """vlb_conv_weight_prepare_batched (what refresh_weights runs after every optimizer step) on one table whose items straddle the
+    1024-element blocks of block_start: a 7x7 stem (kf = 192 > 147, no dgrad operand), a 1x1, a 3x3 with the dgrad operand and a padded
+    kf, a 3x3 without BatchNorm, a 1x1 of exactly 1024 elements, and a 3x3 with O, I multiples of 32 (the LDS-tile branch every
+    trainable convolution of the network takes).  Every output bit-identical to the single-item vlb_conv_weight_prepare, pad columns of
+    wf untouched, values against the fp64 fold w * gamma / sqrt(var + eps) within one 16-bit rounding, scale / shift within 1e-6, and a
+    second run after one master weight changed updates that item only."""
+    g = torch.Generator().manual_seed(60)
+    specs = [(64, 49, 3, 192, False, True), (24, 1, 16, 16, True, True), (24, 9, 16, 9 * 16 + 8, True, True), (24, 9, 16, 9 * 16, True, False),
+             (64, 1, 16, 16, True, True), (64, 9, 32, 9 * 32 + 8, True, True)]          # (O, taps, I, kf, wb?, bn?)
+    starts = np.cumsum([0] + [(O * T * I + 1023) // 1024 for O, T, I, _, _, _ in specs])
+    assert list(starts[:6]) == [0, 10, 11, 15, 19, 20] and specs[4][0] * specs[4][2] == 1024
+
+    def outputs(O, T, I, kf, with_wb):
+        wf = torch.full((O, kf), 7.0, dtype=act_dtype(), device=dev())
+        wb = torch.full((I, T * O), 7.0, dtype=act_dtype(), device=dev()) if with_wb else None
+        return wf, wb, torch.full((O,), 7.0, device=dev()), torch.full((O,), 7.0, device=dev())
+
+    host, items = [], []
+    for O, T, I, kf, with_wb, with_bn in specs:
+        w = torch.randn(O, T, I, generator=g)
+        bn = [0.5 + torch.rand(O, generator=g), torch.randn(O, generator=g), torch.randn(O, generator=g), 0.5 + torch.rand(O, generator=g)] \
+            if with_bn else None
+        host.append((w, bn))
+        items.append((w.to(dev()), [t.to(dev()) for t in bn] if with_bn else None) + outputs(O, T, I, kf, with_wb))
+    batch = ops.ConvPrepareBatch(items, dev())
+    assert batch.n == len(specs) and batch.total == int(starts[-1])
+    batch.run()
+    torch.cuda.synchronize()
+
+    def same_as_single(k):
+        O, T, I, kf, with_wb, _ = specs[k]
+        w, bn, wf, wb, scale, shift = items[k]
+        one = outputs(O, T, I, kf, with_wb)
+        ops.conv_weight_prepare(w, bn, *one)
+        for name, got, want in zip(("wf", "wb", "scale", "shift"), (wf, wb, scale, shift), one):
+            assert (got is None and want is None) or torch.equal(got, want), "item %d: %s differs from vlb_conv_weight_prepare" % (k, name)
+
+    for k, (O, T, I, kf, with_wb, with_bn) in enumerate(specs):
+        same_as_single(k)
+        (w, bn), (_, _, wf, wb, scale, shift) = host[k], items[k]
+        if kf > T * I:
+            assert float((wf[:, T * I:].float() - 7.0).abs().max()) == 0.0, "item %d: pad columns of wf were written" % k
+        s = bn[0].double() / torch.sqrt(bn[3].double() + 1e-5) if with_bn else torch.ones(O, dtype=torch.float64)
+        folded = w.double() * s[:, None, None]
+        report("prepare batch item %d wf" % k, wf[:, :T * I], folded.reshape(O, -1), 0, 4e-3)
+        if with_wb:
+            report("prepare batch item %d wb" % k, wb, folded.flip(1).permute(2, 1, 0).reshape(I, T * O), 0, 4e-3)
+        report("prepare batch item %d scale" % k, scale, s, 1e-6, 1e-6)
+        report("prepare batch item %d shift" % k, shift, bn[1].double() - bn[2].double() * s if with_bn else torch.zeros(O), 1e-6, 1e-6)
+    # one master weight changes: the next run updates that item and nothing else
+    before = [[None if t is None else t.clone() for t in it[2:]] for it in items]
+    items[2][0].mul_(-2.0)
+    batch.run()
+    torch.cuda.synchronize()
+    for k in range(len(specs)):
+        same_as_single(k)
+        for name, now, was in zip(("wf", "wb", "scale", "shift"), items[k][2:], before[k]):
+            if now is None:
+                continue
+            if k == 2 and name in ("wf", "wb"):
+                kreal = specs[k][1] * specs[k][2]
+                a, b = (now[:, :kreal], was[:, :kreal]) if name == "wf" else (now, was)
+                assert torch.equal(a.float(), -2.0 * b.float()), "item 2: %s does not follow its master weight" % name      # (x -2 is exact)
+            else:
+                assert torch.equal(now, was), "item %d: %s changed although its inputs did not" % (k, name)
 
 
 # ------------------------------------------------------------------------------------------------------------------
