@@ -24,13 +24,22 @@ import torch
 import torch.nn as nn
 
 from .. import ops
+from .heads import Linear16, cfg_get as _get
 
 VIS_DIM = 2048
 _TAG = 1001     # dropout site tag of the downsample input (engine.TAG_DOWNSAMPLE)
 
 
-def _get(obj, name, default=None):
-    return getattr(obj, name, default) if not isinstance(obj, dict) else obj.get(name, default)
+def _downsample_bwd(module, st, idx, g):
+    """g = d(obj_reps) -> dy (ReLU undone, no gradient from padded boxes) in st["dy"], (d weight, d bias) of obj_downsample.1"""
+    H = module.final_dim
+    g = g.contiguous().float().view(-1, H)
+    ops.relu_bwd_cast(g, st["y"], st["dy_all"])
+    ops.gather_rows(st["dy_all"], idx, st["dy"])
+    gw = torch.zeros_like(module._w16.weight)
+    gb = torch.zeros((H,), dtype=torch.float32, device=g.device)
+    ops.wgrad_tn(st["dy"], st["a"], gw, colsum=gb, workspace=None)
+    return gw, gb
 
 
 class _Fn(torch.autograd.Function):
@@ -40,11 +49,11 @@ class _Fn(torch.autograd.Function):
         H = weight.shape[0]
         d = boxes.device
         st = module._state(B, R, d)
-        module._sync_weights()
+        module._w16.sync()
         memb = mask_embed.detach().float().reshape(-1) if mask_embed is not None else module._zero_embed
         p = module.drop_p if train else 0.0
         ops.obj_prep_fwd(boxes, im_info, sel, memb, st["a"], drop_p=p, seed=module._seed, tag=_TAG)
-        ops.gemm_nt(st["a"], module._w16, st["y"], bias=bias.detach(), act=ops.ACT_RELU)
+        ops.gemm_nt(st["a"], module._w16.W, st["y"], bias=bias.detach(), act=ops.ACT_RELU)
         ops.gather_rows(st["y"], idx, st["out"])                 # rows of padded boxes -> 0
         ctx.module, ctx.st, ctx.sel, ctx.idx, ctx.p = module, st, sel, idx, p
         ctx.has_embed = mask_embed is not None
@@ -54,17 +63,11 @@ class _Fn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         module, st = ctx.module, ctx.st
-        H = module._w16.shape[0]
-        g = g.contiguous().float().view(-1, H)
-        ops.relu_bwd_cast(g, st["y"], st["dy_all"])
-        ops.gather_rows(st["dy_all"], ctx.idx, st["dy"])         # no gradient from padded boxes
-        gw = torch.zeros_like(module._master_w)
-        gb = torch.zeros((H,), dtype=torch.float32, device=g.device)
-        ops.wgrad_tn(st["dy"], st["a"], gw, colsum=gb, workspace=None)
+        gw, gb = _downsample_bwd(module, st, ctx.idx, g)
         g_embed = None
         if ctx.has_embed:     # d(feature half of the GEMM input), summed over the masked regions (through their dropout)
-            ops.gemm_nt(st["dy"], module._wT[VIS_DIM:], st["dfeat"])
-            ge = torch.zeros((VIS_DIM,), dtype=torch.float32, device=g.device)
+            ops.gemm_nt(st["dy"], module._w16.Wt[VIS_DIM:], st["dfeat"])
+            ge = torch.zeros((VIS_DIM,), dtype=torch.float32, device=gw.device)
             ops.masked_colsum(st["dfeat"], ctx.sel, ge, drop_p=ctx.p, seed=module._seed, tag=_TAG, row_elems=2 * VIS_DIM,
                               col_off=VIS_DIM)
             g_embed = ge.view(ctx.embed_shape)
@@ -82,12 +85,12 @@ class _FnE2E(torch.autograd.Function):
         B, R = boxes_full.shape[0], boxes_full.shape[1]
         H = weight.shape[0]
         st = module._state(B, R, boxes_full.device)
-        module._sync_weights()
+        module._w16.sync()
         module._sync_vision(vs)
         vs.forward(images, boxes_full, segms)                    # fills boxes_full[:, :, 4:] with post_roialign
         p = module.drop_p if train else 0.0
         ops.obj_prep_fwd(boxes_full, im_info, None, module._zero_embed, st["a"], drop_p=p, seed=module._seed, tag=_TAG)
-        ops.gemm_nt(st["a"], module._w16, st["y"], bias=bias.detach(), act=ops.ACT_RELU)
+        ops.gemm_nt(st["a"], module._w16.W, st["y"], bias=bias.detach(), act=ops.ACT_RELU)
         ops.gather_rows(st["y"], idx, st["out"])
         ctx.module, ctx.vs, ctx.st, ctx.idx, ctx.p, ctx.boxes = module, vs, st, idx, p, boxes_full
         return st["out"].view(B, R, H).float()
@@ -95,14 +98,8 @@ class _FnE2E(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         module, vs, st = ctx.module, ctx.vs, ctx.st
-        H = module._w16.shape[0]
-        g = g.contiguous().float().view(-1, H)
-        ops.relu_bwd_cast(g, st["y"], st["dy_all"])
-        ops.gather_rows(st["dy_all"], ctx.idx, st["dy"])
-        gw = torch.zeros_like(module._master_w)
-        gb = torch.zeros((H,), dtype=torch.float32, device=g.device)
-        ops.wgrad_tn(st["dy"], st["a"], gw, colsum=gb, workspace=None)
-        ops.gemm_nt(st["dy"], module._wT[VIS_DIM:], st["dfeat"])      # d(feature half of the GEMM input)
+        gw, gb = _downsample_bwd(module, st, ctx.idx, g)
+        ops.gemm_nt(st["dy"], module._w16.Wt[VIS_DIM:], st["dfeat"])      # d(feature half of the GEMM input)
         for t in module._conv_grads.values():
             t.zero_()
         vs.backward(st["dfeat"], ctx.boxes, drop_p=ctx.p, seed=module._seed, tag=_TAG)
@@ -131,11 +128,10 @@ class FastRCNN(nn.Module):
         down.register_parameter("bias", nn.Parameter(torch.zeros((final_dim,), device=dev)))
         self.obj_downsample = nn.Module()
         self.obj_downsample.add_module("1", down)              # Sequential(Dropout, Linear, ReLU): the Linear is entry "1"
-        self._w16 = torch.zeros((final_dim, 2 * VIS_DIM), dtype=ops.BF16, device=dev)
-        self._wT = torch.zeros((2 * VIS_DIM, final_dim), dtype=ops.BF16, device=dev)
+        self._w16 = Linear16(down)                             # 16-bit working copy of the Linear and its transpose
         self._zero_embed = torch.zeros((VIS_DIM,), dtype=torch.float32, device=dev)
         self._seed = torch.tensor([ops.rank_seed(20011)], dtype=torch.int32, device=dev)
-        self._version, self._states = None, OrderedDict()
+        self._states = OrderedDict()
         self._stacks, self._conv_params, self._conv_grads, self._vbuffers, self._vversion = OrderedDict(), {}, {}, {}, 0
         if self.e2e:
             from .. import vision as _vision
@@ -212,10 +208,6 @@ class FastRCNN(nn.Module):
             vs.refresh_weights()
             vs._mirror_weights = ver
 
-    @property
-    def _master_w(self):
-        return getattr(self.obj_downsample, "1").weight
-
     def init_weight(self):
         """common/fast_rcnn.py:111-118: normal(0, 0.01) weight, zero bias."""
         lin = getattr(self.obj_downsample, "1")
@@ -225,13 +217,6 @@ class FastRCNN(nn.Module):
 
     def bn_eval(self):
         pass                                                   # no BatchNorm on the precomputed branch
-
-    def _sync_weights(self):
-        w = self._master_w
-        if self._version != w._version:
-            ops.cast_f32_bf16(w.detach().contiguous(), self._w16)
-            ops.transpose(self._w16, self._wT)
-            self._version = w._version
 
     def _state(self, B, R, dev):
         def make():

@@ -24,6 +24,7 @@ import torch.nn.functional as F
 
 from .. import engine as _engine
 from .. import ops
+from .heads import cfg_get as _get
 
 _PREFIX = "vlbert."
 _MAX_S = 256      # longest packed sequence the attention kernels cover (attention.hip: ATT_SP_MAX)
@@ -55,10 +56,6 @@ def lru_get(cache, key, make):
     while len(cache) > shape_buckets()[2]:
         cache.popitem(last=False)
     return cache[key]
-
-
-def _get(obj, name, default=None):
-    return getattr(obj, name, default) if not isinstance(obj, dict) else obj.get(name, default)
 
 
 class _CoreFn(torch.autograd.Function):

@@ -30,11 +30,8 @@ import torch.nn.functional as F
 
 from ... import engine as _engine
 from ... import ops
+from ...common.heads import cfg_get as _get
 from ...common.visual_linguistic_bert import bucketed, lru_get
-
-
-def _get(obj, name, default=None):
-    return getattr(obj, name, default) if not isinstance(obj, dict) else obj.get(name, default)
 
 
 class _HipLoss(torch.autograd.Function):

@@ -13,22 +13,16 @@ as a row dot product with the classifier dropout applied on the fly, the masked 
 inference box pick.  No host synchronisation inside the node.
 Unsupported (NotImplementedError, as in the VQA mirror): BLIND, NO_GROUNDING, ENABLE_CNN_REG_LOSS, object_word_embed_mode != 2.
 """
-import sys
-
 import torch
 import torch.nn as nn
 
 from ... import ops
-from ...common.fast_rcnn import FastRCNN
-from ...common.visual_linguistic_bert import VisualLinguisticBert
+from ...common.heads import Linear16, cfg_get
+from ...common.module import Module
 
 F32 = torch.float32
 CLS, SEP = 101, 102          # ids of '[CLS]', '[SEP]' in the BERT vocabularies (tokenizer lookups in the reference, :96)
 _TAG = 2003                  # dropout site of final_mlp.1
-
-
-def _get(obj, name, default=None):
-    return getattr(obj, name, default) if not isinstance(obj, dict) else obj.get(name, default)
 
 
 class _HeadFn(torch.autograd.Function):
@@ -39,10 +33,10 @@ class _HeadFn(torch.autograd.Function):
     def forward(ctx, hs, boxes, label, module, train, w1, b1, w2, b2):
         B, R, H = hs.shape
         st = module._head_state(B * R, hs.device)
-        module._sync_head()
+        module._w1.sync()
         p = module.cls_drop if train else 0.0
         ops.cast_f32_bf16(hs.detach().contiguous(), st["x"])
-        ops.gemm_nt(st["x"], module._w1, st["g"], bias=b1.detach(), act=ops.ACT_GELU_D, pre=st["dg"])
+        ops.gemm_nt(st["x"], module._w1.W, st["g"], bias=b1.detach(), act=ops.ACT_GELU_D, pre=st["dg"])
         logits = torch.empty((B, boxes.shape[1]), dtype=F32, device=hs.device)
         ops.ground_score_fwd(st["g"], w2.detach().view(-1), b2.detach(), logits, B, R, drop_p=p, seed=module._seed, tag=_TAG)
         loss = torch.empty((), dtype=F32, device=hs.device)
@@ -65,7 +59,7 @@ class _HeadFn(torch.autograd.Function):
         ops.ground_score_bwd(gl, st["dlogit"], st["g"], st["dg"], w2.detach().view(-1), st["du"], gw2.view(-1), gb2, drop_p=p,
                              seed=module._seed, tag=_TAG)
         ops.wgrad_tn(st["du"], st["x"], gw1, colsum=gb1, workspace=None)
-        ops.gemm_nt(st["du"], module._w1T, st["dx"])
+        ops.gemm_nt(st["du"], module._w1.Wt, st["dx"])
         d_hs = torch.empty((B * R, H), dtype=F32, device=gl.device)
         ops.cast_bf16_f32(st["dx"], d_hs)
         if p > 0:
@@ -73,51 +67,25 @@ class _HeadFn(torch.autograd.Function):
         return d_hs.view(B, R, H), None, None, None, None, gw1, gb1, gw2, gb2
 
 
-class ResNetVLBERT(nn.Module):
-    def __init__(self, config, device=None):
-        super().__init__()
-        self.config = config
-        net = _get(config, "NETWORK")
-        vl = _get(net, "VLBERT")
-        if _get(net, "BLIND", False) or _get(net, "NO_GROUNDING", False) or _get(net, "ENABLE_CNN_REG_LOSS", False):
-            raise NotImplementedError("BLIND / NO_GROUNDING / ENABLE_CNN_REG_LOSS are not supported")
-        if _get(vl, "object_word_embed_mode", 2) != 2:
-            raise NotImplementedError("object_word_embed_mode must be 2 (one shared object word embedding)")
-        if not torch.cuda.is_available():
-            raise RuntimeError("ResNetVLBERT (HIP) needs an MI355X: there is no CPU fallback")
-        dev = torch.device(device or ("cuda:%d" % torch.cuda.current_device()))
-        self.device_ = dev
-        H = _get(vl, "hidden_size")
-        if H % 64:
-            raise NotImplementedError("hidden_size must be a multiple of 64 (GEMM tile width)")
-        self.H = H
-        self.initializer_range = float(_get(vl, "initializer_range", 0.02))
-        self.cls_drop = float(_get(net, "CLASSIFIER_DROPOUT", 0.1))
-        self.image_feature_extractor = FastRCNN(config, average_pool=True, final_dim=_get(net, "IMAGE_FINAL_DIM", 768),
-                                                enable_cnn_reg_loss=False, device=dev)
-        self.object_linguistic_embeddings = nn.Embedding(1, H).to(dev)
-        from ...common import language_pretrained as _lp
-        self.language_pretrained_model_path = _lp.resolve_path(net)                    # (:27-37)
-        if self.language_pretrained_model_path is None:
-            print("Warning: no pretrained language model found, training from scratch!!!", file=sys.stderr)   # (the reference prints to stdout)
-        self.vlbert = VisualLinguisticBert(vl, language_pretrained_model_path=self.language_pretrained_model_path, device=dev)
+class ResNetVLBERT(Module):
+    SEED = 40013
 
-        def lin(o, i):
-            m = nn.Module()
-            m.register_parameter("weight", nn.Parameter(torch.empty((o, i), device=dev)))
-            m.register_parameter("bias", nn.Parameter(torch.zeros((o,), device=dev)))
-            return m
+    def _check_config(self, net, vl):
+        if cfg_get(net, "BLIND", False) or cfg_get(net, "NO_GROUNDING", False) or cfg_get(net, "ENABLE_CNN_REG_LOSS", False):
+            raise NotImplementedError("BLIND / NO_GROUNDING / ENABLE_CNN_REG_LOSS are not supported")
+        if cfg_get(vl, "object_word_embed_mode", 2) != 2:
+            raise NotImplementedError("object_word_embed_mode must be 2 (one shared object word embedding)")
+
+    def _build_heads(self, net, vl):
+        if self.H % 64:
+            raise NotImplementedError("hidden_size must be a multiple of 64 (GEMM tile width)")
+        self.initializer_range = float(cfg_get(vl, "initializer_range", 0.02))
         mlp = nn.Module()                      # Sequential(VisualLinguisticBertMVRCHeadTransform, Dropout, Linear(H, 1))  (:41-47)
-        tr = nn.Module()
-        tr.add_module("dense", lin(H, H))
-        mlp.add_module("0", tr)
-        mlp.add_module("2", lin(1, H))
+        mlp.add_module("0", self._transform())
+        mlp.add_module("2", self._lin(1, self.H))
         self.final_mlp = mlp
-        zb = lambda *s: torch.zeros(s, dtype=ops.BF16, device=dev)
-        self._w1, self._w1T = zb(H, H), zb(H, H)          # transform dense weight and its transpose (16-bit working copies)
-        self._seed = torch.tensor([ops.rank_seed(40013)], dtype=torch.int32, device=dev)
-        self._head_version, self._states = None, {}
-        self.init_weight()
+        self._w1 = Linear16(getattr(mlp, "0").dense)          # the transform's dense weight; the Linear(H, 1) runs in csrc/grounding.hip
+        self._states = {}
 
     # -- parameters ---------------------------------------------------------------------------------
     def _head_params(self):
@@ -134,18 +102,6 @@ class ResNetVLBERT(nn.Module):
                     nn.init.xavier_uniform_(q)
                 else:
                     q.zero_()
-
-    def fix_params(self):
-        pass
-
-    def _sync_head(self):
-        w1 = self._head_params()[0]
-        ver = w1._version
-        if ver == self._head_version:
-            return
-        ops.cast_f32_bf16(w1.detach().contiguous(), self._w1)
-        ops.transpose(self._w1, self._w1T)
-        self._head_version = ver
 
     def _head_state(self, n, dev):
         if n not in self._states:
@@ -167,16 +123,9 @@ class ResNetVLBERT(nn.Module):
         return ids, ids.new_zeros(ids.shape), ids > 0
 
     def _features(self, image, boxes, im_info, expression):
-        box_mask = boxes[:, :, 0] > -1.5
-        max_len = int(box_mask.sum(1).max())                       # (:81; the one host read of the step, as in the reference)
-        box_mask, trimmed = box_mask[:, :max_len], boxes[:, :max_len].contiguous()
-        obj = self.image_feature_extractor(images=image, boxes=trimmed, box_mask=box_mask, im_info=im_info, classes=None, segms=None)
+        reps, obj_vl, box_mask, max_len = self._object_inputs(image, boxes, im_info, copy_boxes=True)      # (:80-86)
         ids, types, text_mask = self._prepare_text(expression)
-        reps = obj["obj_reps"]
         text_visual = reps[:, 0:1].expand(-1, ids.shape[1], -1)
-        B, R = box_mask.shape
-        ling = self.object_linguistic_embeddings.weight[0].expand(B, R, -1)
-        obj_vl = torch.cat((reps, ling), -1)
         _, hs, _ = self.vlbert(ids, types, text_visual, text_mask, obj_vl, box_mask, output_all_encoded_layers=False,
                                output_text_and_object_separately=True)
         return hs, max_len
@@ -203,7 +152,3 @@ class ResNetVLBERT(nn.Module):
         idx = torch.empty((boxes.shape[0],), dtype=torch.int64, device=boxes.device)
         ops.ground_pick_box(logits, boxes, im_info.to(F32).contiguous(), pred, idx)
         return {"label_logits": logits, "pred_boxes": pred, "pred_index": idx}
-
-    def forward(self, *inputs, **kwargs):
-        """common/module.py:19-24"""
-        return self.train_forward(*inputs, **kwargs) if self.training else self.inference_forward(*inputs, **kwargs)

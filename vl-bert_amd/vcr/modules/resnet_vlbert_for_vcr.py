@@ -19,28 +19,17 @@ over the choices) are one autograd node on the library as well (`_AnswerFn`).
 Built as input plumbing: BLIND, NO_GROUNDING, NO_OBJ_ATTENTION, ANSWER_FIRST, QA_ONE_SENT.  Not built: object_word_embed_mode 3, IMAGE_SEMANTIC, the
 bottom-of-the-CNN form of the regulariser (CNN_LOSS_TOP false), mask_position / mask_label (asserted off in the reference too).
 """
-import sys
-
 import torch
 import torch.nn as nn
-import torch.nn.functional as F
 
 from ... import ops
-from ...common.fast_rcnn import FastRCNN
-from ...common.visual_linguistic_bert import VisualLinguisticBert
+from ...common.heads import Drop, Head, Linear, Linear16, cfg_get, run_head
+from ...common.module import Module
 
 F32 = torch.float32
 CLS, SEP = 101, 102          # ids of '[CLS]', '[SEP]' in the BERT vocabularies (tokenizer lookups in the reference)
 _TAG_REG, _TAG_A0, _TAG_A1 = 3001, 3002, 3003
 NUM_OBJ_CLASSES = 81         # COCO detector classes of the VCR annotations (:26,38)
-
-
-def _get(obj, name, default=None):
-    return getattr(obj, name, default) if not isinstance(obj, dict) else obj.get(name, default)
-
-
-def _ru(x, m):
-    return (x + m - 1) // m * m
 
 
 class TimeDistributed(nn.Module):
@@ -66,273 +55,112 @@ class TimeDistributed(nn.Module):
         raise ValueError("Not support!")
 
 
-class _ObjClsFn(torch.autograd.Function):
-    """x [n,H] fp32 (final hidden states of the valid objects), labels [n] -> CE loss of Linear(GELU(Linear(x))) (`cnn_loss_reg`,
-    :33-37,391-394) on the device: two bf16 GEMMs with fused epilogues, vlb_ce_fwd_bwd (loss and d(logits) in one pass),
-    hand-scheduled backward."""
+def one_column_wgrad(K, dev):
+    """TN weight gradient of a Linear(<=K, 1) whose d(logits) lives in column 0 of a [rows, 64] buffer (the rest exactly zero): the GEMM
+    runs on all 64 columns into fp32 staging, row 0 is the gradient."""
+    gwp, gbp = torch.zeros((64, K), dtype=F32, device=dev), torch.zeros((64,), dtype=F32, device=dev)
 
-    @staticmethod
-    def forward(ctx, x, labels, module, train, w1, b1, w2, b2):
-        n, H = x.shape
-        st = module._reg_state(n, x.device)
-        module._sync_reg()
-        p = module.reg_drop if train else 0.0
-        ops.cast_f32_bf16(x.detach().contiguous(), st["x0"])
-        ops.gemm_nt(st["x0"], module._rw1, st["u"], bias=b1.detach(), act=ops.ACT_GELU_D, pre=st["du_act"])
-        x1 = ops.dropout_bf16(st["u"], st["x1"], p, module._seed, _TAG_REG) if p > 0 else st["u"]
-        ops.gemm_nt(x1, module._rw2, st["logits"][:, :NUM_OBJ_CLASSES], bias=b2.detach())
-        st["loss"].zero_()
-        ops.ce_fwd_bwd(st["logits"], NUM_OBJ_CLASSES, labels.contiguous(), st["count"], st["loss"], logits_copy=st["logits_copy"])
-        ctx.module, ctx.st, ctx.p, ctx.x1, ctx.labels = module, st, p, x1, labels
-        return st["loss"][0].clone()
-
-    @staticmethod
-    def backward(ctx, g_loss):
-        module, st, p = ctx.module, ctx.st, ctx.p
-        g = float(g_loss)
-        if g != 1.0:      # upstream scale (CNN_LOSS_WEIGHT, gradient accumulation): re-derive d(logits) from the kept logits
-            st["logits"].copy_(st["logits_copy"])
-            st["loss"].zero_()
-            ops.ce_fwd_bwd(st["logits"], NUM_OBJ_CLASSES, ctx.labels.contiguous(), st["count"], st["loss"], gscale=g)
-        w1, b1, w2, b2 = module._reg_params()
-        gw1, gb1, gw2, gb2 = (torch.zeros_like(q, dtype=F32) for q in (w1, b1, w2, b2))
-        ops.wgrad_tn(st["logits"][:, :NUM_OBJ_CLASSES], ctx.x1, gw2, colsum=gb2, workspace=None)
-        ops.gemm_nt(st["logits"], module._rw2T, st["dx1"])                     # K = the padded class dimension (zero columns)
-        dh = ops.dropout_bf16(st["dx1"], st["dh"], p, module._seed, _TAG_REG) if p > 0 else st["dx1"]
-        ops.mul_bf16(dh, st["du_act"], st["dpre"])
-        ops.wgrad_tn(st["dpre"], st["x0"], gw1, colsum=gb1, workspace=None)
-        ops.gemm_nt(st["dpre"], module._rw1T, st["dx0"])
-        dx = torch.empty(st["dx0"].shape, dtype=F32, device=st["dx0"].device)
-        ops.cast_bf16_f32(st["dx0"], dx)
-        if p > 0:
-            ops.rng_advance(module._seed)
-        return dx, None, None, None, gw1, gb1, gw2, gb2
+    def wgrad(dz, x, gw, gb):
+        gwp.zero_()
+        gbp.zero_()
+        ops.wgrad_tn(dz, x, gwp[:, :gw.shape[1]], colsum=gbp, workspace=None)
+        gw.copy_(gwp[:1, :gw.shape[1]]); gb.copy_(gbp[:1])
+    return wgrad
 
 
-class _AnswerFn(torch.autograd.Function):
-    """pooled [B,C,H] fp32 (BertPooler output per answer choice), answer_label [B] -> (label_logits [B,C], ans_loss): `final_mlp`
-    (Dropout -> Linear(H,1) | Dropout -> Linear(H,hc) -> ReLU -> Dropout -> Linear(hc,1), :62-82) and the answer loss -- the weighted
-    sigmoid BCE with the (w+1)/(2w) rescale, or the softmax CE over the choices (:333-345) -- on the device: bf16 GEMMs with fused
-    bias / ReLU epilogues, counter-RNG dropout, vlb_bce_logits_fwd_bwd / vlb_ce_fwd_bwd (loss and d(logits) in one pass),
-    hand-scheduled backward."""
+def answer_loss(answer_label, B, C, sigmoid, pos_weight, count):
+    """The answer loss over the [B*C, 64] logits buffer of the classifier (column 0 live), as a Head loss: the weighted sigmoid BCE
+    with the (w+1)/(2w) rescale, mean over the B*C logits (:344-356), or the softmax CE over the C choices of a sample (:358) through a
+    [B, 64] staging buffer.  count: fp32 [1] scratch of vlb_ce_fwd_bwd."""
+    n = B * C
 
-    @staticmethod
-    def forward(ctx, pooled, answer_label, module, train, *params):
-        B, C, H = pooled.shape
-        n = B * C
-        st = module._cls_state(n, B, pooled.device)
-        module._sync_cls()
-        p = module.cls_drop if train else 0.0
-        ops.cast_f32_bf16(pooled.detach().contiguous().view(n, H), st["x_in"])
-        x0 = ops.dropout_bf16(st["x_in"], st["x0"], p, module._seed, _TAG_A0) if p > 0 else st["x_in"]
-        if module.classifier == "1fc":
-            x1 = x0
-            ops.gemm_nt(x0, module._cw2, st["z"][:, :1], bias=params[1].detach())
-        else:
-            ops.gemm_nt(x0, module._cw1, st["u"], bias=params[1].detach(), act=ops.ACT_RELU)
-            x1 = ops.dropout_bf16(st["u"], st["x1"], p, module._seed, _TAG_A1) if p > 0 else st["u"]
-            ops.gemm_nt(x1, module._cw2, st["z"][:, :1], bias=params[3].detach())
-        logits = st["z"][:, 0].float().view(B, C)                 # (glue: the [B,C] fp32 tensor the outputs dict carries)
-        st["loss"].zero_()
-        ctx.has_label = answer_label is not None
-        if ctx.has_label:
-            _AnswerFn._loss(module, st, answer_label, B, C, 1.0)
-        ctx.module, ctx.st, ctx.p, ctx.x0, ctx.x1, ctx.label, ctx.shape = module, st, p, x0, x1, answer_label, (B, C, H)
-        ctx.mark_non_differentiable(logits)
-        return logits, st["loss"][0].clone()
-
-    @staticmethod
-    def _loss(module, st, answer_label, B, C, g):
-        """loss value into st["loss"], g * d(loss)/d(logit) into column 0 of st["z"] (the kept logits live in st["z_copy"])."""
-        n = B * C
-        if module.sigmoid:      # mean over the B*C logits of w * BCE, times (w+1)/(2w)
-            rescale = (module.pos_weight + 1.0) / (2.0 * module.pos_weight)
-            lab = st["lab"]
-            lab.zero_()
+    def loss_fn(z, z_copy, loss, g, fresh):
+        if sigmoid:
+            rescale = (pos_weight + 1.0) / (2.0 * pos_weight)
+            lab = torch.zeros((n,), dtype=F32, device=z.device)
             lab.view(B, C).scatter_(1, answer_label.long().view(B, 1), 1.0)          # one-hot of the right answer (index plumbing)
-            ops.bce_logits_fwd_bwd(st["z"], 1, lab.view(n, 1), st["loss"], gscale=g * rescale, logits_copy=st["z_copy"],
-                                   pos_weight=module.pos_weight)
-            st["loss"].mul_(rescale)
-        else:                   # softmax cross entropy over the C choices of a sample
-            st["z_copy"].copy_(st["z"])
-            zc = st["zc"]
-            zc.zero_()
-            zc[:, :C].copy_(st["z"][:, 0].view(B, C))
-            ops.ce_fwd_bwd(zc, C, answer_label.long().contiguous().view(-1), st["count"], st["loss"], gscale=g)
-            st["z"].zero_()
-            st["z"][:, 0].copy_(zc[:, :C].reshape(-1))
-
-    @staticmethod
-    def backward(ctx, _g_logits, g_loss):
-        module, st, p = ctx.module, ctx.st, ctx.p
-        B, C, H = ctx.shape
-        n = B * C
-        params = module._cls_params()
-        grads = [torch.zeros_like(q, dtype=F32) for q in params]
-        if not ctx.has_label:
-            return (torch.zeros((B, C, H), dtype=F32, device=st["z"].device), None, None, None) + tuple(grads)
-        g = float(g_loss)
-        if g != 1.0:      # upstream scale (ANS_LOSS_WEIGHT, gradient accumulation): re-derive d(logits) from the kept logits
-            st["z"].copy_(st["z_copy"])
-            st["loss"].zero_()
-            _AnswerFn._loss(module, st, ctx.label, B, C, g)
-        dz = st["z"]                                                        # [n, 64]: column 0 live, the rest exactly zero
-        gw2p = st["gw2p"]
-        gw2p.zero_()
-        st["gb2p"].zero_()
-        if module.classifier == "1fc":
-            gw2, gb2 = grads
-            ops.wgrad_tn(dz, ctx.x1, gw2p[:, :H], colsum=st["gb2p"], workspace=None)
-            gw2.copy_(gw2p[:1, :H]); gb2.copy_(st["gb2p"][:1])
-            ops.gemm_nt(dz, module._cw2T, st["dx0"])                         # K = 64 (one live column)
+            ops.bce_logits_fwd_bwd(z, 1, lab.view(n, 1), loss, gscale=g * rescale, logits_copy=z_copy, pos_weight=pos_weight)
+            loss.mul_(rescale)
         else:
-            gw1, gb1, gw2, gb2 = grads
-            hc = module.hc
-            ops.wgrad_tn(dz, ctx.x1, gw2p[:, :hc], colsum=st["gb2p"], workspace=None)
-            gw2.copy_(gw2p[:1, :hc]); gb2.copy_(st["gb2p"][:1])
-            ops.gemm_nt(dz, module._cw2T, st["dx1"], act=ops.ACT_RELU_MASK, aux=st["u"])
-            du = ops.dropout_bf16(st["dx1"], st["du"], p, module._seed, _TAG_A1) if p > 0 else st["dx1"]
-            ops.wgrad_tn(du, ctx.x0, gw1, colsum=gb1, workspace=None)
-            ops.gemm_nt(du, module._cw1T, st["dx0"])
-        dx = ops.dropout_bf16(st["dx0"], st["dxin"], p, module._seed, _TAG_A0) if p > 0 else st["dx0"]
-        d_pooled = torch.empty((n, H), dtype=F32, device=dx.device)
-        ops.cast_bf16_f32(dx.contiguous(), d_pooled)
-        if p > 0:
-            ops.rng_advance(module._seed)
-        return (d_pooled.view(B, C, H), None, None, None) + tuple(grads)
+            z_copy.copy_(z)
+            zc = torch.zeros((B, 64), dtype=z.dtype, device=z.device)
+            zc[:, :C].copy_(z[:, 0].view(B, C))
+            ops.ce_fwd_bwd(zc, C, answer_label.long().contiguous().view(-1), count, loss, gscale=g)
+            z.zero_()
+            z[:, 0].copy_(zc[:, :C].reshape(-1))
+    return loss_fn
 
 
-class ResNetVLBERT(nn.Module):
-    def __init__(self, config, device=None):
-        super().__init__()
-        self.config = config
-        net = _get(config, "NETWORK")
-        vl = _get(net, "VLBERT")
+class ResNetVLBERT(Module):
+    SEED = 40011
+
+    def _check_config(self, net, vl):
         for flag in ("FOR_MASK_VL_MODELING_PRETRAIN", "IMAGE_SEMANTIC"):
-            if _get(net, flag, False):
+            if cfg_get(net, flag, False):
                 raise NotImplementedError("NETWORK.%s is not supported" % flag)
         # ablation switches of the reference's forward (:253-330): all of them are input plumbing in front of the same encoder
-        self.blind = bool(_get(net, "BLIND", False))                      # no visual input at all: zero features, no object positions
-        self.no_grounding = bool(_get(net, "NO_GROUNDING", False))        # every token tagged with box 0 (the whole image)
-        self.no_obj_attention = bool(_get(net, "NO_OBJ_ATTENTION", False))      # objects feed the token embeddings but are not attended
-        self.answer_first = bool(_get(net, "ANSWER_FIRST", False))        # [CLS] answer [SEP] question [SEP]
-        self.qa_one_sent = bool(_get(net, "QA_ONE_SENT", False))          # [CLS] question answer [SEP], one segment
+        self.blind = bool(cfg_get(net, "BLIND", False))                      # no visual input at all: zero features, no object positions
+        self.no_grounding = bool(cfg_get(net, "NO_GROUNDING", False))        # every token tagged with box 0 (the whole image)
+        self.no_obj_attention = bool(cfg_get(net, "NO_OBJ_ATTENTION", False))      # objects feed the token embeddings but are not attended
+        self.answer_first = bool(cfg_get(net, "ANSWER_FIRST", False))        # [CLS] answer [SEP] question [SEP]
+        self.qa_one_sent = bool(cfg_get(net, "QA_ONE_SENT", False))          # [CLS] question answer [SEP], one segment
         if self.answer_first and self.qa_one_sent:
             raise NotImplementedError("ANSWER_FIRST with QA_ONE_SENT (the reference raises as well, :276-277)")
-        if self.blind and _get(net, "ENABLE_CNN_REG_LOSS", False):
+        if self.blind and cfg_get(net, "ENABLE_CNN_REG_LOSS", False):
             raise NotImplementedError("BLIND with ENABLE_CNN_REG_LOSS: there are no object positions to classify")
-        self.embed_mode = int(_get(vl, "object_word_embed_mode", 2))
+        self.embed_mode = int(cfg_get(vl, "object_word_embed_mode", 2))
         if self.embed_mode not in (1, 2):
             raise NotImplementedError("object_word_embed_mode must be 1 (81 class embeddings) or 2 (one shared embedding)")
-        self.enable_cnn_reg_loss = bool(_get(net, "ENABLE_CNN_REG_LOSS", False))
-        self.cnn_loss_top = bool(_get(net, "CNN_LOSS_TOP", False))
+        self.NUM_OBJECT_WORDS = NUM_OBJ_CLASSES if self.embed_mode == 1 else 1
+        self.enable_cnn_reg_loss = bool(cfg_get(net, "ENABLE_CNN_REG_LOSS", False))
+        self.cnn_loss_top = bool(cfg_get(net, "CNN_LOSS_TOP", False))
         if self.enable_cnn_reg_loss and not self.cnn_loss_top:
             raise NotImplementedError("ENABLE_CNN_REG_LOSS needs CNN_LOSS_TOP (the form of the shipped cfgs/vcr/*.yaml)")
-        self.classifier = _get(net, "CLASSIFIER_TYPE", "2fc")
+        self.classifier = cfg_get(net, "CLASSIFIER_TYPE", "2fc")
         if self.classifier not in ("1fc", "2fc"):
             raise ValueError("Not support classifier type: {}!".format(self.classifier))
-        if not torch.cuda.is_available():
-            raise RuntimeError("ResNetVLBERT (HIP) needs an MI355X: there is no CPU fallback")
-        dev = torch.device(device or ("cuda:%d" % torch.cuda.current_device()))
-        self.device_ = dev
-        H = int(_get(vl, "hidden_size"))
-        self.H = H
-        self.sigmoid = bool(_get(net, "CLASSIFIER_SIGMOID", False))
-        self.pos_weight = float(_get(net, "CLASSIFIER_SIGMOID_LOSS_POSITIVE_WEIGHT", 1.0))
-        self.cls_drop = float(_get(net, "CLASSIFIER_DROPOUT", 0.1))
-        self.reg_drop = float(_get(net, "CNN_REG_DROPOUT", 0.0))
-        self.ans_loss_weight = float(_get(net, "ANS_LOSS_WEIGHT", 1.0))
-        self.cnn_loss_weight = float(_get(net, "CNN_LOSS_WEIGHT", 1.0))
-        self.image_feature_extractor = FastRCNN(config, average_pool=True, final_dim=_get(net, "IMAGE_FINAL_DIM", 768),
-                                                enable_cnn_reg_loss=False, device=dev)
-        self.object_linguistic_embeddings = nn.Embedding(NUM_OBJ_CLASSES if self.embed_mode == 1 else 1, H).to(dev)
-        from ...common import language_pretrained as _lp
-        self.language_pretrained_model_path = _lp.resolve_path(net)                    # (vcr/modules/resnet_vlbert_for_vcr.py:49-58)
-        if self.language_pretrained_model_path is None:
-            print("Warning: no pretrained language model found, training from scratch!!!", file=sys.stderr)   # (the reference prints to stdout; bench.py owns stdout)
-        self.vlbert = TimeDistributed(VisualLinguisticBert(vl, language_pretrained_model_path=self.language_pretrained_model_path, device=dev))
 
-        def lin(o, i):
-            m = nn.Module()
-            m.register_parameter("weight", nn.Parameter(torch.empty((o, i), device=dev)))
-            m.register_parameter("bias", nn.Parameter(torch.zeros((o,), device=dev)))
-            return m
-        mlp = nn.Module()
-        if self.classifier == "1fc":
-            mlp.add_module("1", lin(1, H))
-        else:
-            hc = int(_get(net, "CLASSIFIER_HIDDEN_SIZE", 1024))
-            mlp.add_module("1", lin(hc, H))
-            mlp.add_module("4", lin(1, hc))
-        self.final_mlp = mlp
-        if self.enable_cnn_reg_loss:
-            reg = nn.Module()
-            tr = nn.Module()
-            tr.add_module("dense", lin(H, H))
-            reg.add_module("0", tr)
-            reg.add_module("2", lin(NUM_OBJ_CLASSES, H))
-            self.cnn_loss_reg = reg
-            zb = lambda *s: torch.zeros(s, dtype=ops.BF16, device=dev)
-            self.Cp = _ru(NUM_OBJ_CLASSES, 64)
-            self._rw1, self._rw1T = zb(H, H), zb(H, H)
-            self._rw2, self._rw2T = zb(NUM_OBJ_CLASSES, H), zb(H, self.Cp)
-        # bf16 working copies of the classifier: first Linear [hc,H] (2fc) and the 1-output Linear padded to 64 rows (+ transposes)
-        zc = lambda *s: torch.zeros(s, dtype=ops.BF16, device=dev)
-        self.hc = int(_get(net, "CLASSIFIER_HIDDEN_SIZE", 1024)) if self.classifier != "1fc" else H
+    def _wrap_encoder(self, vlbert):
+        return TimeDistributed(vlbert)
+
+    def _build_heads(self, net, vl):
+        H = self.H
+        self.sigmoid = bool(cfg_get(net, "CLASSIFIER_SIGMOID", False))
+        self.pos_weight = float(cfg_get(net, "CLASSIFIER_SIGMOID_LOSS_POSITIVE_WEIGHT", 1.0))
+        self.reg_drop = float(cfg_get(net, "CNN_REG_DROPOUT", 0.0))
+        self.ans_loss_weight = float(cfg_get(net, "ANS_LOSS_WEIGHT", 1.0))
+        self.cnn_loss_weight = float(cfg_get(net, "CNN_LOSS_WEIGHT", 1.0))
+        self.hc = int(cfg_get(net, "CLASSIFIER_HIDDEN_SIZE", 1024)) if self.classifier != "1fc" else H
         if self.hc % 64:
             raise NotImplementedError("CLASSIFIER_HIDDEN_SIZE must be a multiple of 64")
-        self._cw1, self._cw1T = (zc(self.hc, H), zc(H, self.hc)) if self.classifier != "1fc" else (None, None)
-        self._cw2, self._cw2T = zc(1, self.hc), zc(self.hc, 64)
-        self._cls_version, self._cls_states = None, {}
-        self._seed = torch.tensor([ops.rank_seed(40011)], dtype=torch.int32, device=dev)
-        self._reg_version, self._states = None, {}
-        self.init_weight()
-
-    # -- parameters ---------------------------------------------------------------------------------
-    def _cls_params(self):
-        m = self.final_mlp
+        # final_mlp (:62-82): Dropout -> Linear(H,1) | Dropout -> Linear(H,hc) -> ReLU -> Dropout -> Linear(hc,1); the 1-output Linear's
+        # W^T is [hc, 64] with one live column
+        mlp = nn.Module()
+        wgrad = one_column_wgrad(max(H, self.hc), self.device_)
+        self._count = torch.zeros((1,), dtype=F32, device=self.device_)
         if self.classifier == "1fc":
-            l = getattr(m, "1")
-            return [l.weight, l.bias]
-        a, b = getattr(m, "1"), getattr(m, "4")
-        return [a.weight, a.bias, b.weight, b.bias]
-
-    def _sync_cls(self):
-        params = self._cls_params()
-        ver = tuple(q._version for q in params)
-        if ver == self._cls_version:
-            return
-        w2 = params[0] if self.classifier == "1fc" else params[2]
-        ops.cast_f32_bf16(w2.detach().contiguous(), self._cw2)
-        self._cw2T.zero_()
-        self._cw2T[:, 0].copy_(self._cw2[0])                           # [hc, 64] with one live column (index plumbing)
-        if self.classifier != "1fc":
-            ops.cast_f32_bf16(params[0].detach().contiguous(), self._cw1)
-            ops.transpose(self._cw1, self._cw1T)
-        self._cls_version = ver
-
-    def _cls_state(self, n, B, dev):
-        if (n, B) not in self._cls_states:
-            zb = lambda *s: torch.zeros(s, dtype=ops.BF16, device=dev)
-            zf = lambda *s: torch.zeros(s, dtype=F32, device=dev)
-            H, hc = self.H, self.hc
-            self._cls_states[(n, B)] = dict(x_in=zb(n, H), x0=zb(n, H), u=zb(n, hc), x1=zb(n, hc), z=zb(n, 64), z_copy=zb(n, 64), zc=zb(B, 64),
-                                            dx1=zb(n, hc), du=zb(n, hc), dx0=zb(n, H), dxin=zb(n, H), lab=zf(n), gw2p=zf(64, max(H, hc)),
-                                            gb2p=zf(64), loss=zf(1), count=zf(1))
-        return self._cls_states[(n, B)]
-
-    def _reg_params(self):
-        r = self.cnn_loss_reg
-        t, c = getattr(r, "0"), getattr(r, "2")
-        return [t.dense.weight, t.dense.bias, c.weight, c.bias]
-
+            mlp.add_module("1", self._lin(1, H))
+            stages = [Drop(_TAG_A0), Linear(Linear16(getattr(mlp, "1")), wgrad=wgrad)]
+        else:
+            mlp.add_module("1", self._lin(self.hc, H))
+            mlp.add_module("4", self._lin(1, self.hc))
+            stages = [Drop(_TAG_A0), Linear(Linear16(getattr(mlp, "1")), "relu"), Drop(_TAG_A1), Linear(Linear16(getattr(mlp, "4")), wgrad=wgrad)]
+        self.final_mlp = mlp
+        self._cls_head = Head(stages, self._seed)
+        if self.enable_cnn_reg_loss:              # transform (Linear + GELU) -> Dropout -> Linear(H, 81)  (:33-37); n changes per batch
+            reg = nn.Module()
+            reg.add_module("0", self._transform())
+            reg.add_module("2", self._lin(NUM_OBJ_CLASSES, H))
+            self.cnn_loss_reg = reg
+            self._reg_head = Head([Linear(Linear16(getattr(reg, "0").dense), "gelu"), Drop(_TAG_REG), Linear(Linear16(getattr(reg, "2")))],
+                                  self._seed, row_cap=64)
     def init_weight(self):
         """:84-97: N(0, 0.02) object word embeddings and regulariser head, xavier-uniform classifier, zero biases."""
         with torch.no_grad():
             self.image_feature_extractor.init_weight()
             self.object_linguistic_embeddings.weight.normal_(0.0, 0.02)
             if self.enable_cnn_reg_loss:
-                for q in self._reg_params():
+                for q in self._reg_head.params():
                     if q.dim() == 2:
                         q.normal_(0.0, 0.02)
                     else:
@@ -340,9 +168,6 @@ class ResNetVLBERT(nn.Module):
             for m in self.final_mlp.children():
                 nn.init.xavier_uniform_(m.weight)
                 m.bias.zero_()
-
-    def fix_params(self):
-        pass
 
     def train(self, mode=True):
         super().train(mode)
@@ -361,27 +186,6 @@ class ResNetVLBERT(nn.Module):
         if strict and (missing or res.unexpected_keys):
             raise RuntimeError("Error(s) in loading state_dict for ResNetVLBERT: missing %s, unexpected %s" % (missing, res.unexpected_keys))
         return res
-
-    def _sync_reg(self):
-        params = self._reg_params()
-        ver = tuple(q._version for q in params)
-        if ver == self._reg_version:
-            return
-        ops.cast_f32_bf16(params[0].detach().contiguous(), self._rw1)
-        ops.cast_f32_bf16(params[2].detach().contiguous(), self._rw2)
-        ops.transpose(self._rw1, self._rw1T)
-        ops.transpose(self._rw2, self._rw2T)          # [H, 81] into the zero-padded [H, Cp] image
-        self._reg_version = ver
-
-    def _reg_state(self, n, dev):
-        cap = _ru(n, 64)
-        if cap not in self._states:
-            zb = lambda *s: torch.zeros(s, dtype=ops.BF16, device=dev)
-            H, Cp = self.H, self.Cp
-            self._states[cap] = dict(x0=zb(cap, H), u=zb(cap, H), du_act=zb(cap, H), x1=zb(cap, H), logits=zb(cap, Cp),
-                                     logits_copy=zb(cap, Cp), dx1=zb(cap, H), dh=zb(cap, H), dpre=zb(cap, H), dx0=zb(cap, H),
-                                     loss=torch.zeros((1,), dtype=F32, device=dev), count=torch.zeros((1,), dtype=F32, device=dev))
-        return {k: (v[:n] if v.dim() == 2 else v) for k, v in self._states[cap].items()}
 
     # -- text preparation: index plumbing (prepare_text_from_qa / _qa_onesent / _aq, :136-224) ------------------------
     @staticmethod
@@ -457,9 +261,18 @@ class ResNetVLBERT(nn.Module):
         return pooled, obj_out, objects, box_mask
 
     def _classify(self, pooled, answer_label=None):
-        """-> (label_logits [B,C], ans_loss | None) through the HIP head (_AnswerFn)."""
-        logits, loss = _AnswerFn.apply(pooled.float(), answer_label, self, self.training, *self._cls_params())
+        """-> (label_logits [B,C], ans_loss | None): `final_mlp` and the answer loss, one autograd node on the library."""
+        B, C, H = pooled.shape
+        loss_fn = answer_loss(answer_label, B, C, self.sigmoid, self.pos_weight, self._count) if answer_label is not None else None
+        z, loss = run_head(self._cls_head, pooled.float().reshape(B * C, H), self.cls_drop if self.training else 0.0, loss_fn)
+        logits = z[:, 0].float().view(B, C)                 # (glue: the [B,C] fp32 tensor the outputs dict carries)
         return logits, (loss if answer_label is not None else None)
+
+    def _regularize(self, x, labels):
+        """x [n,H] fp32 (final hidden states of the valid objects), labels [n] -> CE loss of `cnn_loss_reg` (:391-394), one autograd node"""
+        def ce(logits, logits_copy, loss, g, fresh):
+            ops.ce_fwd_bwd(logits, NUM_OBJ_CLASSES, labels.contiguous(), self._count, loss, gscale=g, logits_copy=logits_copy if fresh else None)
+        return run_head(self._reg_head, x, self.reg_drop if self.training else 0.0, ce)[1]
 
     def train_forward(self, image, boxes, masks, question, question_align_matrix, answer_choices, answer_align_matrix, answer_label,
                       im_info, mask_position=None, mask_type=None, mask_label=None):
@@ -477,7 +290,7 @@ class ResNetVLBERT(nn.Module):
             R = box_mask.shape[1]
             sel = box_mask[:, None].expand(B, C, R)
             labels = objects[:, None].expand(B, C, R)[sel].long()
-            reg_loss = _ObjClsFn.apply(obj_out[sel].float(), labels, self, self.training, *self._reg_params())
+            reg_loss = self._regularize(obj_out[sel].float(), labels)
             loss = loss + reg_loss * self.cnn_loss_weight
             outputs["cnn_regularization_loss"] = reg_loss
         return outputs, loss
@@ -486,7 +299,3 @@ class ResNetVLBERT(nn.Module):
         im_info = args[-1]
         pooled, _, _, _ = self._encode(image, boxes, masks, question, answer_choices, im_info)
         return {"label_logits": self._classify(pooled)[0]}
-
-    def forward(self, *inputs, **kwargs):
-        """common/module.py:19-24"""
-        return self.train_forward(*inputs, **kwargs) if self.training else self.inference_forward(*inputs, **kwargs)
