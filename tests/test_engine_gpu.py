@@ -914,9 +914,40 @@ def test_fast_rcnn_mirror_mask_embedding_gradient():
     assert rel_fro(getattr(fr.obj_downsample, "1").weight.grad, p["image_feature_extractor.obj_downsample.1.weight"].grad) <= 3e-2
 
 
-def test_side_stream_weight_gradients_match_serial_and_bucket_hook_order():
+@pytest.mark.parametrize("n_side", [1, 2])
+def test_side_stream_helper_makes_the_writer_wait_for_its_readers(n_side):
+    """side_streams.SideStreams alone: side launches that are still busy when the main stream wants to overwrite the buffer they read.
+    Each first enqueues a few milliseconds of unrelated work (eight 2048^2 products), then sums `a` (2^20 ones); the main stream calls
+    before_write(a) and zeroes it.  With the wait every sum is exactly 2^20; with one reader on each of two streams both are."""
+    hz = pkg("side_streams").SideStreams()
+    a = torch.ones(1 << 20, dtype=torch.float32, device=dev())
+    m = torch.ones((2048, 2048), dtype=torch.float32, device=dev())
+    sides = [torch.cuda.Stream(device=dev()) for _ in range(n_side)]
+    b = [torch.zeros((), dtype=torch.float32, device=dev()) for _ in sides]
+    torch.cuda.synchronize()
+
+    def reader(out):
+        def fn():
+            for _ in range(8):
+                torch.mm(m, m)
+            torch.sum(a, dim=0, out=out)
+        return fn
+    for s, out in zip(sides, b):
+        hz.run(s, reader(out), reads=[a])
+    hz.before_write(a)
+    a.zero_()
+    hz.join(sides)
+    torch.cuda.synchronize()
+    assert [float(t) for t in b] == [float(2 ** 20)] * n_side
+    assert float(a.sum()) == 0.0 and hz._pending == {}
+
+
+@pytest.mark.parametrize("pairs", ["1", "0"])
+def test_side_stream_weight_gradients_match_serial_and_bucket_hook_order(pairs, monkeypatch):
     """The weight gradients run on a second stream; (a) the result equals the serialised schedule, (b) the
-    data-parallel hook sees complete gradients: at every on_layer_done the bucket it would all-reduce is final."""
+    data-parallel hook sees complete gradients: at every on_layer_done the bucket it would all-reduce is final.
+    pairs = "1": layer 2 goes out as a grouped launch, layers 1 and 0 as one table launch; "0" (VLB_WGRAD_PAIRS=0): grouped only."""
+    monkeypatch.setenv("VLB_WGRAD_PAIRS", pairs)
     syn = pkg("synthetic")
     cfg = O.VLBertConfig(num_hidden_layers=3)
     params = O.init_params(cfg, seed=12)

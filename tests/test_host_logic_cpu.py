@@ -488,3 +488,16 @@ def test_traffic_stamp_hash_is_the_same_function_in_bench_and_profile_report():
     ns = {"os": os, "__file__": os.path.join(root, "tools", "profile_report.py")}
     exec(compile(ast.Module(body=[fn], type_ignores=[]), "profile_report.py", "exec"), ns)
     assert ns["gemm_sources_sha"]() == bench.gemm_sources_sha() and len(bench.gemm_sources_sha()) == 12
+
+
+def test_side_stream_helper_without_a_stream_runs_inline_and_records_nothing():
+    """stream=None is the serial schedule: fn runs exactly once, at the call, and later before_write / join([]) have nothing to wait
+    for (no device call: this runs without a GPU)."""
+    hz = pkg("side_streams").SideStreams()
+    a, calls = torch.ones(4), []
+    assert hz.run(None, lambda: calls.append(len(calls)), [a]) is None
+    assert calls == [0]
+    assert hz._pending == {}
+    hz.before_write(a, None)
+    hz.join([])
+    assert calls == [0] and hz._pending == {}

@@ -715,6 +715,34 @@ def test_vision_stack_matches_reference_golden():
         assert e < (3e-2 if "roi_head" in short else 8e-2), short
 
 
+def test_vision_side_stream_weight_gradients_match_serial():
+    """Two VisionStacks on the golden fixture, one with its side streams switched off on the live object: same weights, forward,
+    zero_grad and backward -> every weight gradient agrees (rel-fro < 1e-5, the bound of the engine's serial-versus-side test)."""
+    V = pkg("vision")
+    z, nl, P = _vision_fixture()
+    img, boxes4 = torch.from_numpy(z["img"]), torch.from_numpy(z["boxes"])
+    N, R = boxes4.shape[:2]
+    Wr = to_gpu_bf16(torch.from_numpy(z["Wr"]).view(N * R, -1))
+    grads = []
+    for side in (True, False):
+        vs = V.VisionStack(N, img.shape[2], img.shape[3], R, device=dev(), num_layers=nl)
+        assert vs.side is not None
+        if not side:
+            vs.side = None
+        vs.load_state_dict({k: v.to(dev()) for k, v in _prefixed(P).items()})
+        boxes = torch.zeros((N, R, 4 + 2048), device=dev())
+        boxes[:, :, :4] = boxes4.to(dev())
+        vs.forward(img.to(dev()), boxes)
+        vs.zero_grad()
+        vs.backward(Wr, boxes)
+        torch.cuda.synchronize()
+        grads.append(vs.grads())
+    assert len(grads[0]) > 0 and set(grads[0]) == set(grads[1])
+    worst = max((rel_fro(grads[0][k], grads[1][k]), k) for k in grads[0])
+    print("vision side-stream vs serial weight gradients: worst rel-fro difference %.3e (%s)" % worst)
+    assert worst[0] < 1e-5, worst
+
+
 def _vision_grad_errors(eng, Po, names):
     """per-tensor rel-Frobenius errors of the trainable convolution gradients, the rel-Frobenius error of their concatenation and
     the relative difference of the global gradient norm over the vision parameters."""

@@ -75,6 +75,7 @@ class EncoderF32:
         # VQA-large micro-batch (3 664 rows) the step is 193.7 ms with it and 190.9 without -- the 128 x 128-only TN kernel loses more
         # on the under-filled 1024 x 1024 outputs than the 23 ms of transposes it removes (DESIGN.md, fp32 path)
         self.tn = os.environ.get("VLB_F32_TN", "0") == "1"
+        self.w = [self._w(l) for l in range(L)]      # views into the engine's flat buffers (never rebound), built once
 
     # -- parameters ---------------------------------------------------------------------------------------------------
     def _w(self, l):
@@ -100,7 +101,7 @@ class EncoderF32:
         """W^T copies of the current fp32 master weights (after load / every optimizer step)."""
         H, I = self.H, self.I
         for l in range(self.L):
-            w, t = self._w(l), self.wT[l]
+            w, t = self.w[l], self.wT[l]
             ops.transpose_f32(w["wqkv"], H, t["qkv"], 3 * H, 3 * H, H, 3 * H)
             ops.transpose_f32(w["wo"], H, t["ao"], H, H, H, H)
             ops.transpose_f32(w["w1"], H, t["f1"], I, I, H, I)
@@ -147,7 +148,7 @@ class EncoderF32:
         ops.cast_bf16_f32(e.X[0], self.X[0])
         bh = (Bt, nh)
         for l in range(L):
-            w = self._w(l)
+            w = self.w[l]
             x, qkv = self.X[l], self.QKV[l]
             self._linear(x, H, w["wqkv"], 3 * H, qkv, bias=w["bqkv"])
             # scores = Q . K^T / sqrt(64) per (sample, head)
@@ -176,7 +177,7 @@ class EncoderF32:
         dx = self.dx[0]
         ops.cast_bf16_f32(dx16, dx)
         for l in reversed(range(L)):
-            w, t = self._w(l), self.wT[l]
+            w, t = self.w[l], self.wT[l]
             dx_next = self.dx[1] if dx is self.dx[0] else self.dx[0]
             qkv = self.QKV[l]
             # LayerNorm 2 -> dZ2 (residual branch) and its dropout-masked copy into output.dense

@@ -20,10 +20,12 @@ import math
 import os
 from collections import OrderedDict
 from dataclasses import dataclass
+from types import SimpleNamespace
 
 import torch
 
 from . import ops
+from .side_streams import SideStreams
 
 F32 = torch.float32
 VIS_DIM = 2048            # hard-coded in the reference (common/fast_rcnn.py:107, resnet_vlbert_for_pretraining.py:25)
@@ -258,6 +260,8 @@ class PretrainEngine:
         if cfg.with_rel_loss:
             self.wT["vlbert.relationsip_head.caption_image_relationship.weight"] = zb(H, 64)   # K padded to one 64-wide tile
 
+        self.layer = [self._layer_record(l) for l in range(L)]
+
         # device-resident step state
         # odd (the advance kernel keeps it odd) and injective in `seed`: `seed | 1` collapsed ranks 2k / 2k+1 of a
         # seed = RNG_SEED + rank launch onto one dropout stream
@@ -310,8 +314,7 @@ class PretrainEngine:
         # in fp32 from (Z, mean, rstd, gamma, beta) inside the GEMM epilogue, so nothing on the residual path is ever rounded to
         # bf16 -- only the GEMM operands are.  At 12 layers this takes the logits' error against the fp32 reference from 1.3e-2 to
         # ~6e-3 (relative Frobenius; 5e-3 of it is the bf16 rounding of the weights).  VLB_RESIDUAL_STREAM=bf16: the old behaviour.
-        import os as _os0
-        self.hp_res = _os0.environ.get("VLB_RESIDUAL_STREAM", "f16ln") != "bf16"
+        self.hp_res = os.environ.get("VLB_RESIDUAL_STREAM", "f16ln") != "bf16"
         zdt = torch.float16 if self.hp_res else ops.BF16
         zz = lambda *s: torch.zeros(s, dtype=zdt, device=d)
         self.Z1, self.ST1, self.Y1 = [zz(M, H) for _ in range(L)], [zf(M, 2) for _ in range(L)], [zbm(H) for _ in range(L)]
@@ -336,9 +339,8 @@ class PretrainEngine:
         # positions rounded up to 256; a batch that exceeds it raises (the
         # device flag is checked at loss_values(); labels handed over as CPU tensors are counted exactly and such a batch simply
         # takes the full path).  Off with keep_logits (the module mirrors return every logit) and in module-API mode.
-        import os as _os1
         cap = min(self.BTp, max(256, _ru(int(math.ceil(0.20 * BT)), 256)))
-        want = _os1.environ.get("VLB_MLM_COMPACT", "1") != "0" and not keep_logits and not core and cap < BT
+        want = os.environ.get("VLB_MLM_COMPACT", "1") != "0" and not keep_logits and not core and cap < BT
         self.mlm_cap = cap if want else None
         self._mlm_compact_now = want
         if want:
@@ -358,17 +360,13 @@ class PretrainEngine:
         # Round 6: the weight gradients of TWO layers go out as one table launch of full-K work items (216 items for 256 CUs like the
         # grouped launch of one layer, but no K slices: no fp32 slabs, no reduce launch) -- the upper layer of a pair keeps its operands
         # until the lower one is done, so there are four sets (layer & 3) instead of two.  VLB_WGRAD_PAIRS=0: one grouped launch per layer.
-        self._pairs = os.environ.get("VLB_WGRAD_PAIRS", "1") != "0" and os.environ.get("VLB_WGRAD_TN", "1") != "0"
+        self._pairs = os.environ.get("VLB_WGRAD_PAIRS", "1") != "0"
         self._pair_tables = {}
         nset = 4 if self._pairs else 2
         self.dD2, self.dD1 = [zbm(H) for _ in range(nset)], [zbm(H) for _ in range(nset)]
         self.dU2 = [zbm(I) for _ in range(nset)]
         self.dQKV2 = [zbm(3 * H) for _ in range(nset)]
         self.dCTX = zb(M, H)
-        self.tG = zb(max(3 * H, I), self.Mp)       # transposed gradients (zero padded columns persist)
-        self.tA = zb(max(H, I), self.Mp)           # transposed activations
-        self.tG_bt, self.tA_bt = zb(max(self.Vp, H), self.BTp), zb(H, self.BTp)
-        self.tG_br, self.tA_br = zb(max(self.Cp, H), self.BRp), zb(max(H, 2 * VIS_DIM), self.BRp)
         self.d_mlm_h, self.d_mlm_g, self.d_mlm_u = zb(BT, H), zb(BT, H), zb(BT, H)
         self.d_text_out, self.d_obj_out = zb(BT, H), zb(BR, H)
         self.d_mvrc_u = zb(BR, H)
@@ -395,20 +393,18 @@ class PretrainEngine:
         # Hazards: a wgrad reads the gradient buffer the main stream produced (event after the producer) and the main
         # stream must not overwrite that buffer before the wgrad is done (event recorded after it, waited by the
         # next writer -- a full layer later thanks to the dD / dDb double buffer).  VLB_WGRAD_STREAM=0 serialises.
-        import os as _os
-        self.side = torch.cuda.Stream(device=d) if (d.type == "cuda" and _os.environ.get("VLB_WGRAD_STREAM", "1") != "0") else None
+        self.side = torch.cuda.Stream(device=d) if (d.type == "cuda" and os.environ.get("VLB_WGRAD_STREAM", "1") != "0") else None
         self.wg_ws_main = zf(max(need_dec, 4)) if self.side is not None else self.wg_ws    # decoder dgrad split-K (main stream)
-        self._pending = {}
+        self._hazards = SideStreams()
         self.ln_ws = zf(ops.ln_bwd_workspace_floats(H))     # per-workgroup partial dgamma/dbeta sums of the LayerNorm backward
         # The encoder's LayerNorm backwards (2 per layer + the MLM head's) leave their partial sums in a workspace slice of their
         # own; one batched launch (ops.ln_param_finalize_batch) adds them into the gradients when those are next needed -- a
         # bucket's all-reduce, or the end of backward -- instead of a 7-10 us finalize launch behind each of the 25 calls.
-        n_slices = min(2 * L + 1, 32) if _os0.environ.get("VLB_LN_DEFER", "1") != "0" else 0
+        n_slices = min(2 * L + 1, 32) if os.environ.get("VLB_LN_DEFER", "1") != "0" else 0
         self._ln_slices = list(zf(n_slices, ops.ln_bwd_workspace_floats(H)).unbind(0)) if n_slices else []
         self._ln_pending = []
         self.graph = None
         self._weights_dirty = True
-        self.use_tn_wgrad = os.environ.get("VLB_WGRAD_TN", "1") != "0"
         self.buckets = None
         # sharded optimizer: the weight gather of the last update may still be in flight (forward waits per bucket); the transposed /
         # folded weight copies are refreshed once it has landed (backward / the next forward of the vision path)
@@ -442,6 +438,22 @@ class PretrainEngine:
     # ------------------------------------------------------------------------------------------
     # parameters
     # ------------------------------------------------------------------------------------------
+    def _layer_record(self, l):
+        """Views of encoder layer l's parameters in the flat buffers, built once (nothing rebinds P.master / P.grad / P.w16): per Linear
+        (qkv = the fused [3H,H] operand, ao, f1, f2) w (16-bit) / b (fp32) / gw / gb / wT, per LayerNorm (ln1, ln2) g / b / gg / gb."""
+        P, H, p = self.P, self.cfg.hidden_size, "vlbert.encoder.layer.%d." % l
+        q = p + "attention.self.query."
+        rec = SimpleNamespace(qkv=SimpleNamespace(
+            w=P.view(P.w16, q + "weight", (3 * H, H), span=3), b=P.view(P.master, q + "bias", (3 * H,), span=3),
+            gw=P.view(P.grad, q + "weight", (3 * H, H), span=3), gb=P.view(P.grad, q + "bias", (3 * H,), span=3), wT=self.wT[p + "qkv"]))
+        for k, n in (("ao", "attention.output.dense."), ("f1", "intermediate.dense."), ("f2", "output.dense.")):
+            setattr(rec, k, SimpleNamespace(w=self.w16[p + n + "weight"], b=self.w32[p + n + "bias"], gw=self.g32[p + n + "weight"],
+                                            gb=self.g32[p + n + "bias"], wT=self.wT[p + n + "weight"]))
+        for k, n in (("ln1", "attention.output.LayerNorm."), ("ln2", "output.LayerNorm.")):
+            setattr(rec, k, SimpleNamespace(g=self.w32[p + n + "weight"], b=self.w32[p + n + "bias"], gg=self.g32[p + n + "weight"],
+                                            gb=self.g32[p + n + "bias"]))
+        return rec
+
     def load_state_dict(self, sd):
         """sd: {reference state_dict name: tensor}.  The tied decoder key is accepted and ignored."""
         vis = self._vision_names()
@@ -494,14 +506,7 @@ class PretrainEngine:
     def _refresh_transposes(self):
         """bf16 W^T copies for the dgrad GEMMs (dX = dY W as an NT product): all ~50 of them in one launch."""
         if self._tbatch is None:
-            H, L = self.cfg.hidden_size, self.cfg.num_hidden_layers
-            pairs = []
-            for l in range(L):
-                p = "vlbert.encoder.layer.%d." % l
-                wqkv = self.P.view(self.P.w16, p + "attention.self.query.weight", (3 * H, H), span=3)
-                pairs.append((wqkv, self.wT[p + "qkv"]))
-                for n in ("attention.output.dense.weight", "intermediate.dense.weight", "output.dense.weight"):
-                    pairs.append((self.w16[p + n], self.wT[p + n]))
+            pairs = [(lin.w, lin.wT) for r in self.layer for lin in (r.qkv, r.ao, r.f1, r.f2)]
             extra = [n for n in ("vlbert.pooler.dense.weight", "vlbert.relationsip_head.caption_image_relationship.weight")
                      if n in self.wT]
             for n in ["vlbert.mlm_head.predictions.transform.dense.weight", "vlbert.word_embeddings.weight",
@@ -660,34 +665,25 @@ class PretrainEngine:
         if self.enc32 is not None:
             self.enc32.forward(p_h, p_a)
         for l in range(L if self.enc32 is None else 0):
-            p = "vlbert.encoder.layer.%d." % l
-            x = self.X[l]
+            r, x = self.layer[l], self.X[l]
             if stale:
                 self.buckets.wait_params(l)
-            wqkv = self.P.view(self.P.w16, p + "attention.self.query.weight", (3 * H, H), span=3)
-            bqkv = self.P.view(self.P.master, p + "attention.self.query.bias", (3 * H,), span=3)
-            ops.gemm_nt(x, wqkv, self.QKV[l], bias=bqkv)
+            ops.gemm_nt(x, r.qkv.w, self.QKV[l], bias=r.qkv.b)
             ops.attention_fwd(self.QKV[l], mask, self.CTX[l], self.LSE[l], Bt, S, H, nh, drop_p=p_a, seed=seed, tag=l * 8 + 0)
             if self.hp_res and l > 0:    # residual = LayerNorm(Z2[l-1]) in fp32 (layer 0: the bf16 embedding output, one rounding)
-                pp = "vlbert.encoder.layer.%d." % (l - 1)
-                res_kw = dict(res=self.Z2[l - 1], res_ln=(self.ST2[l - 1], w32[pp + "output.LayerNorm.weight"], w32[pp + "output.LayerNorm.bias"]))
+                ln = self.layer[l - 1].ln2
+                res_kw = dict(res=self.Z2[l - 1], res_ln=(self.ST2[l - 1], ln.g, ln.b))
             else:
                 res_kw = dict(res=x)
-            ops.gemm_nt(self.CTX[l], w16[p + "attention.output.dense.weight"], self.Z1[l], bias=w32[p + "attention.output.dense.bias"],
-                        drop_p=p_h, seed=seed, tag=l * 8 + 1, **res_kw)
-            ops.layernorm_fwd(self.Z1[l], w32[p + "attention.output.LayerNorm.weight"], w32[p + "attention.output.LayerNorm.bias"],
-                              self.Y1[l], self.ST1[l])
-            ops.gemm_nt(self.Y1[l], w16[p + "intermediate.dense.weight"], self.G[l], bias=w32[p + "intermediate.dense.bias"],
-                        act=ops.ACT_GELU_D, pre=self.U[l])
+            ops.gemm_nt(self.CTX[l], r.ao.w, self.Z1[l], bias=r.ao.b, drop_p=p_h, seed=seed, tag=l * 8 + 1, **res_kw)
+            ops.layernorm_fwd(self.Z1[l], r.ln1.g, r.ln1.b, self.Y1[l], self.ST1[l])
+            ops.gemm_nt(self.Y1[l], r.f1.w, self.G[l], bias=r.f1.b, act=ops.ACT_GELU_D, pre=self.U[l])
             if self.hp_res:
-                res_kw = dict(res=self.Z1[l], res_ln=(self.ST1[l], w32[p + "attention.output.LayerNorm.weight"],
-                                                      w32[p + "attention.output.LayerNorm.bias"]))
+                res_kw = dict(res=self.Z1[l], res_ln=(self.ST1[l], r.ln1.g, r.ln1.b))
             else:
                 res_kw = dict(res=self.Y1[l])
-            ops.gemm_nt(self.G[l], w16[p + "output.dense.weight"], self.Z2[l], bias=w32[p + "output.dense.bias"],
-                        drop_p=p_h, seed=seed, tag=l * 8 + 2, **res_kw)
-            ops.layernorm_fwd(self.Z2[l], w32[p + "output.LayerNorm.weight"], w32[p + "output.LayerNorm.bias"], self.X[l + 1],
-                              self.ST2[l])
+            ops.gemm_nt(self.G[l], r.f2.w, self.Z2[l], bias=r.f2.b, drop_p=p_h, seed=seed, tag=l * 8 + 2, **res_kw)
+            ops.layernorm_fwd(self.Z2[l], r.ln2.g, r.ln2.b, self.X[l + 1], self.ST2[l])
         # --- heads ---------------------------------------------------------------------------------------
         if stale:
             self.buckets.wait_params("heads")
@@ -752,51 +748,28 @@ class PretrainEngine:
     # ------------------------------------------------------------------------------------------
     # backward (explicit; weight gradients are ACCUMULATED into the flat fp32 grad buffer)
     # ------------------------------------------------------------------------------------------
-    def _wgrad(self, dy, x, gw, gb, tG, tA, rows_p):
-        """gw[N,K] += dy^T x ; gb[N] += colsum(dy) through zero-padded transposes."""
-        if self.use_tn_wgrad:   # straight from the row-major operands (LDS transpose reads), bias gradient fused
-            if self.side is None:
-                ops.wgrad_tn(dy, x, gw, colsum=gb, workspace=self.wg_ws, accumulate=not self._fresh_grads)
-                return
-            ready = torch.cuda.Event()
-            ready.record()                                   # everything the operands depend on is enqueued on the main stream
-            with torch.cuda.stream(self.side):
-                self.side.wait_event(ready)
-                ops.wgrad_tn(dy, x, gw, colsum=gb, workspace=self.wg_ws, accumulate=not self._fresh_grads)
-                done = torch.cuda.Event()
-                done.record()
-            self._pending[dy.data_ptr()] = done              # whoever overwrites `dy` next must wait for this
-            return
-        N, K = dy.shape[1], x.shape[1]
-        tg, ta = tG[:N, :rows_p], tA[:K, :rows_p]
-        ops.transpose(dy, tg, colsum=gb)
-        ops.transpose(x, ta)
-        ops.wgrad_nt(tg, ta, gw, workspace=self.wg_ws)
+    def _on_side(self, launch, items):
+        """launch() on the side stream (inline without one); whoever overwrites a gradient operand `dy` of `items` next waits for it."""
+        self._hazards.run(self.side, launch, [dy for dy, _, _, _ in items])
+
+    def _wgrad(self, dy, x, gw, gb):
+        """gw[N,K] (+)= dy^T x ; gb[N] += colsum(dy), straight from the row-major operands (LDS transpose reads), bias gradient fused."""
+        acc = not self._fresh_grads
+        self._on_side(lambda: ops.wgrad_tn(dy, x, gw, colsum=gb, workspace=self.wg_ws, accumulate=acc), [(dy, x, gw, gb)])
+
+    def _padded(self, items):
+        """items with their row-padded operands (zero pad rows): K a multiple of 128 for the large-tile kernels."""
+        pad = self._row_padded
+        return [(pad.get(dy.data_ptr(), dy), pad.get(x.data_ptr(), x), gw, gb) for dy, x, gw, gb in items]
 
     def _wgrad_group(self, items):
         """items: [(dy, x, gw, gb)] over the same rows -- the four Linear layers of an encoder layer -- as one grouped launch on the
-        side stream (ops.wgrad_tn_group); falls back to single calls without the TN path."""
-        if not self.use_tn_wgrad:
-            for dy, x, gw, gb in items:
-                self._wgrad(dy, x, gw, gb, self.tG, self.tA, self.Mp)
-            return
+        side stream (ops.wgrad_tn_group)."""
         acc = not self._fresh_grads
-        pad = self._row_padded       # row-padded operands (zero pad rows): K a multiple of 128 for the large-tile kernel
-        items = [(pad.get(dy.data_ptr(), dy), pad.get(x.data_ptr(), x), gw, gb) for dy, x, gw, gb in items]
+        items = self._padded(items)
         if len({t.shape[0] for it in items for t in it[:2]}) != 1:
             items = [(dy[:self.M], x[:self.M], gw, gb) for dy, x, gw, gb in items]
-        if self.side is None:
-            ops.wgrad_tn_group(items, workspace=self.wg_ws, accumulate=acc)
-            return
-        ready = torch.cuda.Event()
-        ready.record()
-        with torch.cuda.stream(self.side):
-            self.side.wait_event(ready)
-            ops.wgrad_tn_group(items, workspace=self.wg_ws, accumulate=acc)
-            done = torch.cuda.Event()
-            done.record()
-        for dy, _, _, _ in items:
-            self._pending[dy.data_ptr()] = done              # whoever overwrites an operand next must wait for the group
+        self._on_side(lambda: ops.wgrad_tn_group(items, workspace=self.wg_ws, accumulate=acc), items)
 
     def _wgrad_pair(self, items):
         """items: [(dy, x, gw, gb)] of TWO encoder layers (8 products over the same rows) as ONE table launch of full-K 256 x 256 work
@@ -804,8 +777,7 @@ class PretrainEngine:
         (buffers, accumulate) and replayed.  False: not taken (a product outside what the table kernel covers, or a table that would
         have to be built during stream capture) -- the caller falls back to one grouped launch per layer."""
         acc = not self._fresh_grads
-        pad = self._row_padded
-        items = [(pad.get(dy.data_ptr(), dy), pad.get(x.data_ptr(), x), gw, gb) for dy, x, gw, gb in items]
+        items = self._padded(items)
         key = (acc,) + tuple(t.data_ptr() for it in items for t in it)
         tab = self._pair_tables.get(key)
         if tab is None:
@@ -817,34 +789,17 @@ class PretrainEngine:
             self._pair_tables[key] = tab
         if not tab.ok:
             return False
-        if self.side is None:
-            tab.run()
-            return True
-        ready = torch.cuda.Event()
-        ready.record()
-        with torch.cuda.stream(self.side):
-            self.side.wait_event(ready)
-            tab.run()
-            done = torch.cuda.Event()
-            done.record()
-        for dy, _, _, _ in items:
-            self._pending[dy.data_ptr()] = done              # whoever overwrites an operand next must wait for the launch
+        self._on_side(lambda: tab.run(), items)
         return True
 
     def _before_write(self, *bufs):
         """Main stream is about to overwrite these buffers: wait for side-stream weight gradients still reading them."""
-        for b in bufs:
-            ev = self._pending.pop(b.data_ptr(), None)
-            if ev is not None:
-                torch.cuda.current_stream().wait_event(ev)
+        self._hazards.before_write(*bufs)
 
     def _join_side(self):
         """All side-stream weight gradients issued so far complete before later main-stream work."""
         if self.side is not None:
-            ev = torch.cuda.Event()
-            ev.record(self.side)
-            torch.cuda.current_stream().wait_event(ev)
-            self._pending.clear()
+            self._hazards.join([self.side])
 
     def _ln_bwd(self, dy, x, stats, gamma, dgamma, dbeta, **kw):
         if not self._ln_slices:             # VLB_LN_DEFER=0: finalize behind every call
@@ -879,7 +834,6 @@ class PretrainEngine:
             cfg.num_hidden_layers, cfg.num_attention_heads
         p_h, p_a, p_ds = self._p(train)
         w16, w32, g32, wT, seed = self.w16, self.w32, self.g32, self.wT, self.seed
-        Mp, BTp, BRp = self.Mp, self.BTp, self.BRp
         if self._wT_stale:           # sharded optimizer: every gathered weight has landed by now -> the dgrad operands W^T
             self.buckets.wait_params("all")
             self._refresh_transposes()
@@ -891,15 +845,13 @@ class PretrainEngine:
             pm = "vlbert.mlm_head.predictions."
             compact = self._mlm_compact_now and not self.core
             nr = self.mlm_cap if compact else self.BT
-            nrp = _ru(nr, 64)
             dlog = self.mlm_logits[:nr]                  # [rows, Vp], pad columns zero
-            self._wgrad(dlog[:, :V], self.mlm_h[:nr], g32["vlbert.word_embeddings.weight"], g32[pm + "bias"], self.tG_bt, self.tA_bt, nrp)
+            self._wgrad(dlog[:, :V], self.mlm_h[:nr], g32["vlbert.word_embeddings.weight"], g32[pm + "bias"])
             ops.gemm_nt_splitk(dlog, wT["vlbert.word_embeddings.weight"], self.d_mlm_h[:nr], workspace=self.wg_ws_main)
             self._ln_bwd(self.d_mlm_h[:nr], self.mlm_g[:nr], self.st_mlm[:nr], w32[pm + "transform.LayerNorm.weight"],
                          g32[pm + "transform.LayerNorm.weight"], g32[pm + "transform.LayerNorm.bias"], dx=self.d_mlm_g[:nr])
             ops.mul_bf16(self.d_mlm_g[:nr], self.mlm_u[:nr], self.d_mlm_u[:nr])
-            self._wgrad(self.d_mlm_u[:nr], self.text_out[:nr], g32[pm + "transform.dense.weight"], g32[pm + "transform.dense.bias"], self.tG_bt,
-                        self.tA_bt, nrp)
+            self._wgrad(self.d_mlm_u[:nr], self.text_out[:nr], g32[pm + "transform.dense.weight"], g32[pm + "transform.dense.bias"])
             if compact:      # gradient of the labelled rows back to their text positions; every other position gets exactly zero
                 ops.gemm_nt(self.d_mlm_u[:nr], wT[pm + "transform.dense.weight"], self.d_text_out_c)
                 self.d_text_out.zero_()
@@ -909,14 +861,14 @@ class PretrainEngine:
             # --- MVRC head -----------------------------------------------------------------------------------
             dlog2 = self.mvrc_logits                     # [BR, Cp]
             self._wgrad(dlog2[:, :C], self.mvrc_g, g32["vlbert.mvrc_head.region_cls_pred.weight"],
-                        g32["vlbert.mvrc_head.region_cls_pred.bias"], self.tG_br, self.tA_br, BRp)
+                        g32["vlbert.mvrc_head.region_cls_pred.bias"])
             ops.gemm_nt(dlog2, wT["vlbert.mvrc_head.region_cls_pred.weight"], self.d_mvrc_u, act=ops.ACT_MULAUX, aux=self.mvrc_u)
             self._wgrad(self.d_mvrc_u, self.obj_out, g32["vlbert.mvrc_head.transform.dense.weight"],
-                        g32["vlbert.mvrc_head.transform.dense.bias"], self.tG_br, self.tA_br, BRp)
+                        g32["vlbert.mvrc_head.transform.dense.bias"])
             ops.gemm_nt(self.d_mvrc_u, wT["vlbert.mvrc_head.transform.dense.weight"], self.d_obj_out)
             if cfg.with_rel_loss:
                 pr = "vlbert.relationsip_head.caption_image_relationship."
-                self._wgrad(self.rel_logits[:, :2], self.pooled, g32[pr + "weight"], g32[pr + "bias"], None, None, 0)
+                self._wgrad(self.rel_logits[:, :2], self.pooled, g32[pr + "weight"], g32[pr + "bias"])
                 ops.gemm_nt(self.rel_logits, wT[pr + "weight"], self.d_pooled)      # K = 64: two logits + zero padding
         dx = self.dXa
         if not self.seq_out:      # (sequence mode: the caller's d(sequence_output) is already in dXa)
@@ -926,7 +878,7 @@ class PretrainEngine:
             # dense layer, then ADDED to the first-token rows of dX (gemm epilogue residual = its own output rows)
             ops.tanh_bwd(self.d_pooled, self.pooled, self.d_pool_pre)
             x0 = self.X[L].view(Bt, S * H)[:self.B, :H]
-            self._wgrad(self.d_pool_pre, x0, g32["vlbert.pooler.dense.weight"], g32["vlbert.pooler.dense.bias"], None, None, 0)
+            self._wgrad(self.d_pool_pre, x0, g32["vlbert.pooler.dense.weight"], g32["vlbert.pooler.dense.bias"])
             dx0 = dx.view(Bt, S * H)[:self.B, :H]
             ops.gemm_nt(self.d_pool_pre, wT["vlbert.pooler.dense.weight"], dx0, res=dx0)
         if on_layer_done:
@@ -938,36 +890,31 @@ class PretrainEngine:
             dx = self.enc32.backward(dx, p_h, p_a, on_layer_done, will_launch)
         held = None      # (layer, weight-gradient items) of an odd layer waiting for the layer below it (self._pairs)
         for l in reversed(range(L if self.enc32 is None else 0)):
-            p = "vlbert.encoder.layer.%d." % l
+            r = self.layer[l]
             dx_next = self.dXb if dx is self.dXa else self.dXa
             par = l & (len(self.dD2) - 1)
             dD2, dD1, dU, dQKV = self.dD2[par], self.dD1[par], self.dU2[par], self.dQKV2[par]
             # LN2: dZ2 (residual branch) and dD2 (into output.dense, through its dropout; a plain copy when dropout is off --
             # dZ is reused inside the layer, the grouped weight gradient at its end needs its own operand)
             self._before_write(self.dZ, dD2)
-            self._ln_bwd(dx, self.Z2[l], self.ST2[l], w32[p + "output.LayerNorm.weight"], g32[p + "output.LayerNorm.weight"],
-                         g32[p + "output.LayerNorm.bias"], dx=self.dZ, dx_drop=dD2, drop_p=p_h, seed=seed, tag=l * 8 + 2)
+            self._ln_bwd(dx, self.Z2[l], self.ST2[l], r.ln2.g, r.ln2.gg, r.ln2.gb, dx=self.dZ, dx_drop=dD2, drop_p=p_h, seed=seed,
+                         tag=l * 8 + 2)
             self._before_write(dU)
-            ops.gemm_nt(dD2, wT[p + "output.dense.weight"], dU, act=ops.ACT_MULAUX, aux=self.U[l])
-            ops.gemm_nt(dU, wT[p + "intermediate.dense.weight"], dx_next, res=self.dZ)            # dY1
+            ops.gemm_nt(dD2, r.f2.wT, dU, act=ops.ACT_MULAUX, aux=self.U[l])
+            ops.gemm_nt(dU, r.f1.wT, dx_next, res=self.dZ)                                         # dY1
             # LN1
             self._before_write(self.dZ, dD1)
-            self._ln_bwd(dx_next, self.Z1[l], self.ST1[l], w32[p + "attention.output.LayerNorm.weight"],
-                         g32[p + "attention.output.LayerNorm.weight"], g32[p + "attention.output.LayerNorm.bias"], dx=self.dZ,
-                         dx_drop=dD1, drop_p=p_h, seed=seed, tag=l * 8 + 1)
-            ops.gemm_nt(dD1, wT[p + "attention.output.dense.weight"], self.dCTX)
+            self._ln_bwd(dx_next, self.Z1[l], self.ST1[l], r.ln1.g, r.ln1.gg, r.ln1.gb, dx=self.dZ, dx_drop=dD1, drop_p=p_h, seed=seed,
+                         tag=l * 8 + 1)
+            ops.gemm_nt(dD1, r.ao.wT, self.dCTX)
             self._before_write(dQKV)
             ops.attention_bwd(self.QKV[l], mask, self.CTX[l], self.LSE[l], self.dCTX, dQKV, Bt, S, H, nh, drop_p=p_a,
                               seed=seed, tag=l * 8 + 0)
-            gwqkv = self.P.view(self.P.grad, p + "attention.self.query.weight", (3 * H, H), span=3)
-            gbqkv = self.P.view(self.P.grad, p + "attention.self.query.bias", (3 * H,), span=3)
-            ops.gemm_nt(dQKV, wT[p + "qkv"], dx_next, res=self.dZ)                                  # dX_l (overwrites dY1)
+            ops.gemm_nt(dQKV, r.qkv.wT, dx_next, res=self.dZ)                                      # dX_l (overwrites dY1)
             # the layer's four weight gradients on the side stream, off the critical dgrad chain: with the layer below as ONE table launch
             # (an odd layer waits for its partner), or as one grouped launch per layer
-            wg = [(dD2, self.G[l], g32[p + "output.dense.weight"], g32[p + "output.dense.bias"]),
-                  (dU, self.Y1[l], g32[p + "intermediate.dense.weight"], g32[p + "intermediate.dense.bias"]),
-                  (dD1, self.CTX[l], g32[p + "attention.output.dense.weight"], g32[p + "attention.output.dense.bias"]),
-                  (dQKV, self.X[l], gwqkv, gbqkv)]
+            wg = [(dD2, self.G[l], r.f2.gw, r.f2.gb), (dU, self.Y1[l], r.f1.gw, r.f1.gb), (dD1, self.CTX[l], r.ao.gw, r.ao.gb),
+                  (dQKV, self.X[l], r.qkv.gw, r.qkv.gb)]
             dx = dx_next
             if self._pairs and (l & 1):
                 held = (l, wg)              # (its hook fires behind the pair's launch)
@@ -1022,7 +969,6 @@ class PretrainEngine:
         cfg, B, T, R, S, Bt, Ba = self.cfg, self.B, self.T, self.R, self.S, self.Bt, self.Ba
         H = cfg.hidden_size
         w16, w32, g32, wT, seed = self.w16, self.w32, self.g32, self.wT, self.seed
-        BRp = self.BRp
         # --- embedding + visual LayerNorms + obj_downsample ---------------------------------------------
         self.d_objvis.zero_()
         self.d_obj_reps.zero_()
@@ -1050,7 +996,7 @@ class PretrainEngine:
                               rows=Ba, ldx=0, ldacc=0)
         ops.relu_bwd_cast(self.d_obj_reps, self.obj_reps, self.d_yds)
         pd = "image_feature_extractor.obj_downsample.1."
-        self._wgrad(self.d_yds, self.a_ds, g32[pd + "weight"], g32[pd + "bias"], self.tG_br, self.tA_br, BRp)
+        self._wgrad(self.d_yds, self.a_ds, g32[pd + "weight"], g32[pd + "bias"])
         # gradient of the mask embedding: feature half of dA = dY W, masked regions only
         ops.gemm_nt(self.d_yds, wT[pd + "weight"][VIS_DIM:], self.d_afeat)
         if self.vision is not None:      # the features are activations of the CNN: RoI head, ROIAlign and trunk backward
@@ -1155,9 +1101,9 @@ class PretrainEngine:
     # optimizer
     # ------------------------------------------------------------------------------------------
     def zero_grad(self):
-        """Start of an optimizer step.  With the TN weight-gradient path the Linear weight gradients (97 % of the buffer)
-        are OVERWRITTEN by the first backward, so only the ranges that are accumulated with atomics are cleared."""
-        if not self.use_tn_wgrad or self.core or self.enc32 is not None:      # (module-API mode may run without the heads: nothing overwrites
+        """Start of an optimizer step.  The Linear weight gradients (97 % of the buffer) are OVERWRITTEN by the first
+        backward, so only the ranges that are accumulated with atomics are cleared."""
+        if self.core or self.enc32 is not None:      # (module-API mode may run without the heads: nothing overwrites
             # their gradients; the fp32 encoder ACCUMULATES its weight gradients with atomics)
             self.P.grad.zero_()
             self._fresh_grads = False

@@ -29,6 +29,7 @@ from collections import OrderedDict
 import torch
 
 from . import ops
+from .side_streams import SideStreams
 
 F32 = torch.float32
 MODEL_LAYERS = {50: (3, 4, 6, 3), 101: (3, 4, 23, 3), 152: (3, 8, 36, 3)}    # resnet.py model_layers
@@ -113,7 +114,7 @@ class VisionStack:
         n_side = max(1, int(os.environ.get("VLB_VISION_WGRAD_STREAMS", "3"))) if self.side is not None else 0
         self.sides = [self.side] + [torch.cuda.Stream(device=d) for _ in range(n_side - 1)] if self.side is not None else []
         self._side_rr = 0
-        self._pending = {}
+        self._hazards = SideStreams()
         min_train = min(b["stage"] for b in self.blocks if b["stage"] not in self.frozen_stages)
         if any(b["stage"] in self.frozen_stages and b["stage"] > min_train for b in self.blocks):
             raise NotImplementedError("frozen stages must be a prefix of the network")
@@ -383,35 +384,19 @@ class VisionStack:
     # ------------------------------------------------------------------------------------------------------------------
     def _side_run(self, fn, *reads):
         """Run fn(workspace) on the next weight-gradient stream after everything enqueued so far; `reads` are the transient buffers it
-        reads."""
+        reads (a buffer read by several pending weight gradients: the next writer waits for all of them)."""
         if self.side is None:
             fn(self.wg_ws)
             return
         i = self._side_rr
         self._side_rr = (i + 1) % len(self.sides)
-        side = self.sides[i]
-        ready = torch.cuda.Event()
-        ready.record()
-        with torch.cuda.stream(side):
-            side.wait_event(ready)
-            fn(self.wg_wss[i])
-            done = torch.cuda.Event()
-            done.record()
-        for t in reads:          # a buffer read by several pending weight gradients: the next writer waits for all of them
-            self._pending.setdefault(t.data_ptr(), []).append(done)
+        self._hazards.run(self.sides[i], lambda: fn(self.wg_wss[i]), reads)
 
     def _before_write(self, *bufs):
-        for t in bufs:
-            evs = self._pending.pop(t.data_ptr(), None) if t is not None else None
-            for ev in evs or ():
-                torch.cuda.current_stream().wait_event(ev)
+        self._hazards.before_write(*bufs)
 
     def _join_side(self):
-        for side in self.sides:
-            ev = torch.cuda.Event()
-            ev.record(side)
-            torch.cuda.current_stream().wait_event(ev)
-        self._pending.clear()
+        self._hazards.join(self.sides)
 
     def _wgrad(self, c, dy, x, conv=None):
         """g32 += scale[o] * (dy^T x) for the folded operand; conv = (n, h, w, C, dil): x is the NHWC activation and the im2col
