@@ -232,6 +232,24 @@ int vlb_soft_ce_fwd_bwd(void* logits, long ld, int rows, int C, const float* tar
                         float* counts, float gscale, float* loss_out, void* logits_copy, long ldcopy,
                         vlb_stream_t stream);
 
+/* ---- validation: forward-only loss value + top-1 accuracy, the logits are only READ (one pass per row) -------------
+ * The metrics of common/metrics/pretrain_metrics.py:20-85 without copying the logits out: MLMAccuracy / MLMAccuracyWVC /
+ * MLMAccuracyAUX and (V = 2) RelationshipAccuracy through vlb_ce_eval, MVRCAccuracy through vlb_soft_ce_eval.  No host
+ * synchronisation, no allocation; columns >= V (C) of a row are padding and take no part.  An argmax tie goes to the lowest
+ * column (torch.argmax).  Every output is ACCUMULATED: loss_out += the mean loss over the counted rows, acc[0] += rows whose
+ * argmax is the label, acc[1] += counted rows; a call that counts no row leaves all of them untouched.
+ * vlb_ce_eval: rows with a label in [0, V) are counted.  count1 != NULL: the rows are compacted as by vlb_mlm_compact --
+ *   [0, *count0) form group 0 (mean over *count0 into loss_out0, counters acc0), the labelled rows behind them group 1 (*count1,
+ *   loss_out1, acc1).  count1 == NULL: one group over all rows, unlabelled rows anywhere, the kernel counts the labelled rows
+ *   itself (count0 / loss_out1 / acc1 unused).  pred (optional): argmax per row, -1 for an unlabelled row.
+ *   ld % 8 == 0, logits 16-byte aligned.
+ * vlb_soft_ce_eval: a row is counted iff |sum(target) - 1| < 0.1 (common/utils/misc.py:124-151); its hit is
+ *   argmax(logits) == argmax(target). */
+int vlb_ce_eval(const void* logits, long ld, int rows, int V, const int64_t* labels, const float* count0, const float* count1,
+                float* loss_out0, float* loss_out1, int64_t* acc0, int64_t* acc1, int32_t* pred, vlb_stream_t stream);
+int vlb_soft_ce_eval(const void* logits, long ld, int rows, int C, const float* target, long ldt, float* loss_out, int64_t* acc,
+                     vlb_stream_t stream);
+
 /* VQA answer loss (vqa/modules/resnet_vlbert_for_vqa.py:226): binary_cross_entropy_with_logits(logits[rows,A], label) * A =
  * (1/rows) sum of the element losses; logits (bf16, row stride ld, columns >= A zeroed) are overwritten IN PLACE by
  * gscale * d(loss)/d(logits) = gscale * w * (sigmoid(x) - y) / rows; loss_out is accumulated (+=); logits_copy (optional) keeps the logits.

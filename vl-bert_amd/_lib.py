@@ -65,6 +65,8 @@ _SIGS = {
     "vlb_tanh_bwd": "pppls",
     "vlb_ce_fwd_bwd": "pliippfppls",
     "vlb_soft_ce_fwd_bwd": "pliiplppfppls",
+    "vlb_ce_eval": "plii" + "p" * 8 + "s",
+    "vlb_soft_ce_eval": "pliiplpps",
     "vlb_sumsq_f32": "plps",
     "vlb_zero_padded_rows_bf16": "plpliis",
     "vlb_bce_logits_fwd_bwd": "pliiplffppls",

@@ -271,6 +271,8 @@ class PretrainEngine:
         self.sumsq_ws = zf(2048)  # per-block partial sums of the gradient norm
         self.losses = zf(4)       # mlm (with visual content), mvrc, mlm (aux text), relationship
         self.counts = zf(4)       # n_valid mlm, n_valid mvrc, n_valid mlm aux
+        # validation counters of eval_step(): [hits, counted rows] per row of METRIC_ROWS
+        self.metric_acc = torch.zeros((4, 2), dtype=torch.int64, device=d)
 
         # static batch buffers (graph-capturable: the host copies new batches into them)
         self.in_boxes = zf(B, R, 4 + VIS_DIM)
@@ -586,6 +588,12 @@ class PretrainEngine:
 
     def forward(self, train=None, gscale=1.0):
         train = self.train if train is None else train
+        self._forward_to_logits(train)
+        if not self.core:
+            self._losses_fwd_bwd(gscale * self.loss_scale, True)
+
+    def _forward_to_logits(self, train):
+        """Everything of a forward up to the logits (loss slots zeroed, losses not yet computed): shared by forward() and eval_step()."""
         if self._weights_dirty:
             self.sync_weights()
         cfg, B, T, R, S, Bt, Ba = self.cfg, self.B, self.T, self.R, self.S, self.Bt, self.Ba
@@ -607,8 +615,42 @@ class PretrainEngine:
         else:
             self._front_pretrain_fwd(p_h, p_ds)
         self._encoder_heads_fwd(p_h, p_a)
-        if not self.core:
-            self._losses_fwd_bwd(gscale * self.loss_scale, True)
+
+    # ------------------------------------------------------------------------------------------
+    # validation (forward only)
+    # ------------------------------------------------------------------------------------------
+    METRIC_ROWS = ("mlm", "mlm_aux", "mvrc", "relationship")      # rows of metric_acc; "mlm" = MLMAcc, or MLMAccWVC of the multitask model
+
+    def eval_step(self):
+        """One validation batch (the reference's do_validation body, pretrain/function/val.py:6-13, on the batch in the static input
+        buffers): the forward with every dropout probability 0 up to the logits -- forward(train=False)'s own path, compaction / aux
+        rows / e2e / fp32 encoder / relationship head included -- then the forward-only kernels of csrc/metrics.hip in place of the
+        fused forward+backward losses.  Writes the four `losses` slots as a forward does and ADDS [hits, counted rows] per head to
+        `metric_acc`; the logits stay as the GEMMs wrote them, and neither the dropout seed nor any gradient / optimizer state is
+        touched.  No host synchronisation (read with metric_counts() / loss_values(), whose MLM-overflow contract applies)."""
+        if self.core:
+            raise ValueError("eval_step: the module-API engine has no loss heads (metrics belong to the wrapper that owns the labels)")
+        self._forward_to_logits(False)
+        B, T, Ba, V, C = self.B, self.T, self.Ba, self.cfg.vocab_size, self.cfg.visual_region_classes
+        losses, acc, nw = self.losses, self.metric_acc, B * T
+        if self._mlm_compact_now:      # labelled rows only: caption rows, then the aux rows (their counts came from mlm_compact)
+            ops.ce_eval(self.mlm_logits[:self.mlm_cap], V, self.labels_c, losses[0:1], acc[0], count0=self.counts[0:1],
+                        count1=self.counts[2:3], loss_out1=losses[2:3], acc1=acc[1])
+        else:
+            ops.ce_eval(self.mlm_logits[:nw], V, self.in_mlm_labels.view(-1)[:nw], losses[0:1], acc[0])
+            if Ba:
+                ops.ce_eval(self.mlm_logits[nw:], V, self.in_mlm_labels.view(-1)[nw:], losses[2:3], acc[1])
+        ops.soft_ce_eval(self.mvrc_logits, C, self.in_mvrc_labels.view(self.BR, C), losses[1:2], acc[2])
+        if self.cfg.with_rel_loss:
+            ops.ce_eval(self.rel_logits, 2, self.in_rel_label, losses[3:4], acc[3])
+
+    def reset_metrics(self):
+        self.metric_acc.zero_()
+
+    def metric_counts(self):
+        """{head: (hits, counted rows)} accumulated by eval_step() since reset_metrics() (one host synchronisation)."""
+        a = self.metric_acc.cpu()
+        return {k: (int(a[i, 0]), int(a[i, 1])) for i, k in enumerate(self.METRIC_ROWS)}
 
     def _front_core_fwd(self, p_h):
         """VisualLinguisticBert.embedding (common/visual_linguistic_bert.py:173-241) on caller-provided embeddings."""

@@ -414,6 +414,20 @@ def soft_ce_fwd_bwd(logits, C, target, tsum, counts, loss_out, gscale=1.0, logit
               _p(logits_copy, BF16), _ld(logits_copy), _stream())
 
 
+def ce_eval(logits, V, labels, loss_out, acc, count0=None, count1=None, loss_out1=None, acc1=None, pred=None):
+    """Forward-only cross entropy + top-1 hits (vlb_ce_eval): logits are only read; loss_out (+=) the mean over the labelled rows,
+    acc int64 [2] (+=) [hits, labelled rows].  count0 / count1 / loss_out1 / acc1: the two-group form over compacted rows."""
+    _lib.call("vlb_ce_eval", _p(logits, BF16), _ld(logits), logits.shape[0], int(V), _p(labels, torch.int64), _p(count0, torch.float32),
+              _p(count1, torch.float32), _p(loss_out, torch.float32), _p(loss_out1, torch.float32), _p(acc, torch.int64),
+              _p(acc1, torch.int64), _p(pred, torch.int32), _stream())
+
+
+def soft_ce_eval(logits, C, target, loss_out, acc):
+    """Forward-only soft-label cross entropy + argmax(logits) == argmax(target) hits over the valid rows (vlb_soft_ce_eval)."""
+    _lib.call("vlb_soft_ce_eval", _p(logits, BF16), _ld(logits), logits.shape[0], int(C), _p(target, torch.float32), _ld(target),
+              _p(loss_out, torch.float32), _p(acc, torch.int64), _stream())
+
+
 def bce_logits_fwd_bwd(logits, A, label, loss_out, gscale=1.0, logits_copy=None, pos_weight=1.0):
     """logits bf16 [rows, >=A] <- gscale * w * (sigmoid(x) - y) / rows in place; loss_out += BCE-with-logits * A (reference convention);
     w = pos_weight on the positive labels (VCR), 1 elsewhere."""

@@ -1,7 +1,7 @@
 """Entry point with the reference's command line (pretrain/train_end2end.py:11-48) over the HIP engine:
 
     python -m vl-bert_amd.pretrain.train_end2end --cfg cfgs/pretrain/base_prec_withouttextonly_4x16G_fp32.yaml [--dist]
-           [--steps N] [--steps-per-epoch M] [--batch-images B] [--data] [--dry-run]
+           [--steps N] [--steps-per-epoch M] [--batch-images B] [--data] [--val-steps N] [--dry-run]
 
 It reads the reference's YAML files as they are (the keys of pretrain/function/config.py that the hot path consumes: NETWORK.*,
 TRAIN.{BATCH_IMAGES, LR, WD, CLIP_GRAD_NORM, LR_SCHEDULE, WARMUP, WARMUP_STEPS, END_EPOCH, BEGIN_EPOCH, GRAD_ACCUMULATE_STEPS},
@@ -14,7 +14,10 @@ hyper-parameter conventions:
 Checkpoints: with --model-dir the reference's epoch files `{prefix}-{epoch:04d}.model` are written and TRAIN.RESUME / AUTO_RESUME
 honoured (vl-bert_amd/common/checkpoint.py).  Batches are synthetic by default (the collated layout of pretrain/data/collate_batch.py);
 with --data they come from the data sets the YAML names, read by vl-bert_amd/pretrain/data (the reference's annotation / detector-record /
-corpus formats, its sampling and collation).  There is no CPU execution path: without a GPU
+corpus formats, its sampling and collation).  Validation: at every epoch end the reference's ValidationMonitor
+(pretrain/function/train.py:244-281) runs PretrainEngine.eval_step() over the validation set(s) the YAML names (--data; DATASET.VAL_IMAGE_SET /
+VAL_ANNOTATION_FILE) or over --val-steps synthetic batches with fixed seeds, prints `Epoch[k] \tVal-MLMAcc=...` and tracks the best epoch
+(vl-bert_amd/common/metrics.py).  There is no CPU execution path: without a GPU
 the program stops with an error unless --dry-run is given, which only resolves and prints the configuration (the "plumbing"
 check of the reference's scripts/nondist_run.sh case).
 """
@@ -110,6 +113,32 @@ def resolve(config, world, args):
                 loss_scale=(float(tr.FP16_LOSS_SCALE) if isinstance(tr.get("FP16_LOSS_SCALE", None), (int, float)) else None))
 
 
+def _names_val_set(ds):
+    return bool(ds.get("VAL_IMAGE_SET", "") or ds.get("VAL_ANNOTATION_FILE", ""))
+
+
+def pad_masked_samples(batch, B, B_aux=0):
+    """A last validation batch shorter than the engine's static batch, completed with FULLY MASKED samples: copies of its first
+    sample's inputs whose labels are all -1 and whose soft labels are zero, so they add nothing to any loss or counter."""
+    import torch
+    batch = list(batch)
+
+    def rep(t, n):
+        return t if t is None or n <= 0 else torch.cat((t, t[:1].expand(n, *t.shape[1:])), 0)
+
+    def fill(t, n, value):
+        return t if t is None or n <= 0 else torch.cat((t, t.new_full((n,) + tuple(t.shape[1:]), value)), 0)
+
+    n = B - batch[1].shape[0]
+    for i in (0, 1, 2, 3, 6):           # image, boxes, im_info, text, mvrc_ops
+        batch[i] = rep(batch[i], n)
+    batch[4], batch[5], batch[7] = fill(batch[4], n, -1), fill(batch[5], n, -1), fill(batch[7], n, 0)      # relationship / MLM labels, soft labels
+    if len(batch) >= 10 and B_aux:
+        na = B_aux - batch[8].shape[0]
+        batch[8], batch[9] = rep(batch[8], na), fill(batch[9], na, -1)
+    return batch
+
+
 def parse_args(argv=None):
     ap = argparse.ArgumentParser("Train VL-BERT on the MI355X engine")
     ap.add_argument("--cfg", type=str, help="path to a reference-style config file (cfgs/pretrain/*.yaml)")
@@ -137,6 +166,8 @@ def parse_args(argv=None):
                     help="read the data sets the YAML names (DATASET.*: annotation jsonl, detector records with base64 boxes / class scores / "
                          "features, images, text corpora -- vl-bert_amd/pretrain/data) instead of synthetic batches; steps per epoch = "
                          "len(loader) unless --steps-per-epoch is given; the engine's text / box capacities default to DATASET.SEQ_LEN")
+    ap.add_argument("--val-steps", type=int, default=0, help="without --data: validate at every epoch end on this many synthetic batches with "
+                    "fixed seeds (0 = no validation)")
     ap.add_argument("--dry-run", action="store_true", help="resolve and print the configuration, touch no GPU")
     return ap.parse_args(argv)
 
@@ -150,7 +181,7 @@ def main(argv=None):
     world = int(os.environ.get("WORLD_SIZE", "1")) if args.dist else 1
     rank = int(os.environ.get("RANK", "0")) if args.dist else 0
     local_rank = int(os.environ.get("LOCAL_RANK", "0")) if args.dist else 0
-    loader = None
+    loader = val_loader = None
     if args.data:        # the reference's make_dataloader(s) + MultiTaskDataLoader (pretrain/function/train.py:60-66,113-118), one process per GPU
         data = importlib.import_module(__package__ + ".data")
         if "DATASET" not in config:
@@ -161,12 +192,23 @@ def main(argv=None):
                 raise ValueError("--batch-images with a multitask DATASET list: edit TRAIN.BATCH_IMAGES instead")
             loaders = data.make_dataloaders(config, **kw)
             loader = data.MultiTaskDataLoader(loaders) if len(loaders) > 1 else loaders[0]
+            val_sets = [_names_val_set(d) for d in config.DATASET]
             seq_len = max(int(d.get("SEQ_LEN", 64)) for d in config.DATASET)
         else:
             if args.batch_images:
                 config.TRAIN["BATCH_IMAGES"] = args.batch_images
             loader = data.make_dataloader(config, **kw)
             seq_len = int(config.DATASET.get("SEQ_LEN", 64))
+            val_sets = [_names_val_set(config.DATASET)]
+        if all(val_sets) and not args.dry_run:      # the val_loader of pretrain/function/train.py:63-66,116-118 (every sample once: no drop_last)
+            if "VAL" not in config or "BATCH_IMAGES" not in config.VAL:
+                config["VAL"] = AttrDict.wrap(dict(config.get("VAL", {}), BATCH_IMAGES=config.TRAIN.BATCH_IMAGES))
+            vkw = dict(kw, mode="val", drop_last=False)
+            if isinstance(config.DATASET, (list, tuple)):
+                vls = data.make_dataloaders(config, **vkw)
+                val_loader = data.MultiTaskDataLoader(vls) if len(vls) > 1 else vls[0]
+            else:
+                val_loader = data.make_dataloader(config, **vkw)
         if len(loader) == 0:
             raise ValueError("--data: fewer samples than one batch per rank")
         args.steps_per_epoch = args.steps_per_epoch or len(loader)
@@ -271,8 +313,8 @@ def main(argv=None):
             except StopIteration:
                 stream["it"], stream["epoch"] = None, stream["epoch"] + 1
 
-    def load_real_batch():
-        batch = next_real_batch()
+    def load_real_batch(batch=None):
+        batch = next_real_batch() if batch is None else batch
         image, boxes, im_info, text, rel, mlm, ops_, soft = batch[:8]
         if text.shape[1] > T or boxes.shape[1] > R:
             raise ValueError("batch of %d tokens / %d boxes exceeds the step's capacities (--text-len %d, --regions %d)" % (text.shape[1], boxes.shape[1], T, R))
@@ -309,6 +351,21 @@ def main(argv=None):
             kw["mask_raw_pixels"] = bool(config.NETWORK.get("MASK_RAW_PIXELS", True))      # conceptual_captions.py:201-206
         eng.set_batch(*[t.cuda(non_blocking=True) for t in batch], **kw)
 
+    # validation at every epoch end (pretrain/function/train.py:244-281): metrics in the reference's order, all-reduced under --dist
+    monitor = None
+    if val_loader is not None or (loader is None and args.val_steps > 0):
+        met = importlib.import_module(pkg + ".common.metrics")
+        metrics = met.pretrain_metrics(with_rel_loss=bool(config.NETWORK.WITH_REL_LOSS), with_mlm_loss=bool(config.NETWORK.WITH_MLM_LOSS),
+                                       with_mvrc_loss=bool(config.NETWORK.WITH_MVRC_LOSS), multitask=r["multitask"],
+                                       loss_loggers=met.parse_loss_loggers(config.TRAIN.get("LOSS_LOGGERS", None)),
+                                       allreduce=world > 1, num_replicas=world)
+        if val_loader is not None:
+            val_items, put = val_loader, lambda batch: load_real_batch(pad_masked_samples(batch, B, B_aux))
+        else:           # the same synthetic batches at every epoch (seed offsets clear of the training steps')
+            val_items, put = [(1 << 24) + i for i in range(args.val_steps)], load_batch
+        monitor = met.ValidationMonitor(met.do_validation, val_items, metrics, host_metric_name=met.host_metric_name(r["multitask"]),
+                                        load_batch=put, verbose=rank == 0)
+    eng.validation_monitor = monitor
     accum = r["accumulate"]
     for step in range(first_step, first_step + args.steps):
         if accum == 1:
@@ -338,6 +395,9 @@ def main(argv=None):
             if rank == 0:
                 print("step %d  lr %.3e  loss %.4f (mlm %.4f mvrc %.4f)  %.1f samples/s" %
                       (step + 1, float(eng.adam[0]), lv["loss"], lv["mlm_loss"], lv["mvrc_loss"], seen / (time.time() - t0)), flush=True)
+        if monitor is not None and (step + 1) % spe == 0:      # after the step's log line: validation overwrites the loss slots
+            monitor((step + 1) // spe - 1, eng)
+            eng.loss_values()               # (raises if a validation batch overflowed the MLM compaction capacity)
     if dist is not None:
         dist.barrier()
         dist.destroy_process_group()
