@@ -250,6 +250,31 @@ int vlb_ce_eval(const void* logits, long ld, int rows, int V, const int64_t* lab
 int vlb_soft_ce_eval(const void* logits, long ld, int rows, int C, const float* target, long ldt, float* loss_out, int64_t* acc,
                      vlb_stream_t stream);
 
+/* ---- fine-tuning evaluation (csrc/finetune_metrics.hip): the metrics of common/metrics/{vqa,vcr,refcoco}_metrics.py and the
+ * predictions of the test-set writers on the device.  All three read fp32 data only, synchronise nothing, allocate nothing and
+ * ACCUMULATE (+=) into their outputs.
+ * vlb_argmax_eval: per row the argmax over the first C columns of logits [rows, ld] with torch.argmax's rules (equal maxima -> the
+ *   lowest column; NaN is the largest value, the first NaN wins; a row of -inf -> column 0).  pred (optional) int32 [rows] receives
+ *   it, probs (optional) fp32 [rows, ldp] the softmax of the row (F.softmax(logits.float(), 1)).  mode:
+ *     0 predict         label NULL; no accumulator
+ *     1 hard            label int64 [rows]; score = pred == label; sum int64 += hits, count += rows with label != -1 (only -1 is
+ *                       filtered: any other value is counted, an out-of-range label is a miss) -- vcr_metrics.Accuracy
+ *     2 gather          label fp32 [rows, ldl]; score = label[r, pred]; sum DOUBLE += the scores added in ascending row order (a
+ *                       second single-block launch: bit-equal to a sequential loop), count += rows -- vqa_metrics.SoftAccuracy;
+ *                       score [rows] is required (scratch of the ordered sum)
+ *     3 gather > 0.5    label fp32 [rows, ldl]; score = label[r, pred] > 0.5 (strict); sum int64 += hits, count += rows --
+ *                       refcoco_metrics.RefAccuracy
+ *   score (optional in modes 1, 3) fp32 [rows].  C <= 256: one wave per row; above: one 256-thread block per row.
+ * vlb_binary_cls_eval: ClsAccuracy / ClsPosAccuracy / ClsPosFraction of refcoco_metrics.py over logits [rows, N] (stride ld) and
+ *   label fp32 [rows, N] (stride ldl): lab = (long)label (truncation toward zero: -0.5 is valid, -1 is not), pred = logit > 0;
+ *   acc += [correct among lab >= 0, #(lab >= 0), correct among lab == 1, #(lab == 1)].
+ * vlb_joint_hits: vcr_metrics.JointAccuracy: acc += [#(pred_a == label_a and pred_r == label_r), rows] (no -1 filter). */
+int vlb_argmax_eval(const float* logits, long ld, int rows, int C, int mode, const void* label, long ldl, int32_t* pred, float* score,
+                    float* probs, long ldp, void* sum, int64_t* count, vlb_stream_t stream);
+int vlb_binary_cls_eval(const float* logits, long ld, const float* label, long ldl, int rows, int N, int64_t* acc, vlb_stream_t stream);
+int vlb_joint_hits(const int32_t* pred_a, const int64_t* label_a, const int32_t* pred_r, const int64_t* label_r, int rows, int64_t* acc,
+                   vlb_stream_t stream);
+
 /* VQA answer loss (vqa/modules/resnet_vlbert_for_vqa.py:226): binary_cross_entropy_with_logits(logits[rows,A], label) * A =
  * (1/rows) sum of the element losses; logits (bf16, row stride ld, columns >= A zeroed) are overwritten IN PLACE by
  * gscale * d(loss)/d(logits) = gscale * w * (sigmoid(x) - y) / rows; loss_out is accumulated (+=); logits_copy (optional) keeps the logits.

@@ -67,6 +67,9 @@ _SIGS = {
     "vlb_soft_ce_fwd_bwd": "pliiplppfppls",
     "vlb_ce_eval": "plii" + "p" * 8 + "s",
     "vlb_soft_ce_eval": "pliiplpps",
+    "vlb_argmax_eval": "pliiiplppplpps",
+    "vlb_binary_cls_eval": "plpliips",
+    "vlb_joint_hits": "ppppips",
     "vlb_sumsq_f32": "plps",
     "vlb_zero_padded_rows_bf16": "plpliis",
     "vlb_bce_logits_fwd_bwd": "pliiplffppls",

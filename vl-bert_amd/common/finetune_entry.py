@@ -15,8 +15,11 @@ vcr/function/train.py:96-335:
   * per step: GRAD_ACCUMULATE_STEPS micro-batches of loss / accumulate, clip_grad_norm_(CLIP_GRAD_NORM), optimizer step
     (common/trainer.py:101-189); TRAIN.FP16 -> the fp16 build + static loss scale FP16_LOSS_SCALE ("--compute cfg").
 Not reproduced: the data side (datasets, tokeniser, image decoding: batches are synthetic in the collated layouts of
-vqa/data/collate_batch.py / vcr/data/collate_batch.py / refcoco/data/collate_batch.py), validation / test-set csv writing, tensorboard.  No CPU path: without a GPU the
-program stops with an error unless --dry-run is given.
+vqa/data/collate_batch.py / vcr/data/collate_batch.py / refcoco/data/collate_batch.py), the test.py command lines, tensorboard.
+--val-steps N: validation at every epoch end over N synthetic batches ({vqa,vcr,refcoco}/function/val.py through
+common/finetune_eval.do_validation, the metrics on the device), the reference's ValidationMonitor lines and, with --model-dir, its
+Checkpoint callback ({prefix}-{epoch:04d}.model + {prefix}-best.model).  No CPU path: without a GPU the program stops with an error
+unless --dry-run is given.
 """
 import argparse
 import importlib
@@ -124,11 +127,14 @@ def parse_args(task, argv=None):
     ap.add_argument("--log-dir", type=str, help="accepted for command-line compatibility")
     ap.add_argument("--dist", action="store_true")
     ap.add_argument("--slurm", action="store_true")
-    ap.add_argument("--do-test", action="store_true", help="accepted; test-set csv writing is data-side and not built")
+    ap.add_argument("--do-test", action="store_true", help="accepted; the test sets are data-side and not built -- the result files are written "
+                    "by common.finetune_eval: predict + write_vqa_result / write_vcr_result / merge_vcr_results / write_refcoco_result")
     ap.add_argument("--cudnn-off", action="store_true")
     ap.add_argument("--partial-pretrain", type=str, help="checkpoint whose matching keys are loaded (smart_partial_load_model_state_dict)")
     ap.add_argument("--steps", type=int, default=5, help="optimizer steps to run on synthetic batches")
     ap.add_argument("--steps-per-epoch", type=int, default=10000, help="stands in for len(train_loader) in the LR schedule")
+    ap.add_argument("--val-steps", type=int, default=0, help="validate over N synthetic batches (fixed seed) after every --steps-per-epoch "
+                    "optimizer steps of this loop; 0 = no validation")
     ap.add_argument("--compute", default="bf16", choices=["bf16", "fp16", "fp32", "cfg"], help="as pretrain/train_end2end: cfg = what the "
                     "YAML names (TRAIN.FP16 true -> the fp16 build + FP16_LOSS_SCALE, false -> fp32 encoder)")
     ap.add_argument("--dry-run", action="store_true", help="resolve and print the configuration, touch no GPU")
@@ -146,6 +152,34 @@ def resolve(task, config, world, args):
                 lr_schedule=tr.LR_SCHEDULE, warmup_steps=int(tr.WARMUP_STEPS) if tr.WARMUP else 0, compute=compute,
                 loss_scale=float(tr.FP16_LOSS_SCALE) if isinstance(tr.FP16_LOSS_SCALE, (int, float)) else 128.0,
                 precomputed=bool(config.NETWORK.IMAGE_FEAT_PRECOMPUTED), seed=int(config.RNG_SEED))
+
+
+# position of the label in a validation batch = the argument list of the mirror's inference_forward with the label put where
+# train_forward takes it (DATASET.LABEL_INDEX_IN_BATCH of the reference's YAMLs names the same position in its loaders' batches)
+VAL_LABEL_INDEX = {"vqa": 4, "refcoco": 4, "vcr": 7}
+VAL_SEED = 7000000
+
+
+class _ValBatches(object):
+    """The stand-in for val_loader: n synthetic batches from a fixed seed, rebuilt at every pass (the same batches at every epoch)."""
+
+    def __init__(self, task, make, n):
+        self.task, self.make, self.n = task, make, n
+
+    def __len__(self):
+        return self.n
+
+    def __iter__(self):
+        for i in range(self.n):
+            b = self.make(VAL_SEED + i)
+            if self.task == "vqa":
+                boxes, im_info, question, label = b
+                yield (None, boxes, im_info, question, label)
+            elif self.task == "refcoco":
+                yield tuple(b)
+            else:
+                image, boxes, masks, question, answers, label, im_info = b
+                yield (image, boxes, masks, question, None, answers, None, label, im_info)
 
 
 def main(task, argv=None):
@@ -226,6 +260,33 @@ def main(task, argv=None):
         print("%s/train_end2end: %s | %d GPU(s) x batch %d x accumulate %d | %s lr %.3e wd %.1e clip %.1f | schedule %s warmup %d | compute %s" %
               (task, config.MODULE, world, B, accum, r["optimizer"], r["lr"], r["weight_decay"], r["clip_grad_norm"], r["lr_schedule"],
                r["warmup_steps"], r["compute"]), flush=True)
+    # validation at the epoch ends ({vqa,vcr,refcoco}/function/train.py: val_metrics_list + ValidationMonitor + Checkpoint)
+    monitor, prefix, epoch_files = None, config.get("MODEL_PREFIX", "") or ("vl-bert_" + task), 0
+    if args.val_steps > 0:
+        MT = importlib.import_module(pkg + ".common.metrics")
+        FE = importlib.import_module(pkg + ".common.finetune_eval")
+        TM = importlib.import_module(pkg + ".common.%s_metrics" % task)
+        host = getattr(TM, {"vqa": "SoftAccuracy", "vcr": "Accuracy", "refcoco": "RefAccuracy"}[task])(allreduce=world > 1, num_replicas=world)
+        val_metrics = MT.CompositeEvalMetric()
+        val_metrics.add(host)
+        monitor = MT.ValidationMonitor(FE.do_validation, _ValBatches(task, batch, args.val_steps), val_metrics, host_metric_name=host.name,
+                                       label_index_in_batch=VAL_LABEL_INDEX[task], verbose=rank == 0)
+
+    def epoch_end(epoch):
+        monitor(epoch, net.module if hasattr(net, "module") else net)
+        net.train()
+        if not (args.model_dir and rank == 0):
+            return 0
+        os.makedirs(args.model_dir, exist_ok=True)      # common/callbacks/epoch_end_callbacks/checkpoint.py:10-25
+        core = net.module if hasattr(net, "module") else net
+        ckpt = {"state_dict": {k: v.detach().cpu() for k, v in core.state_dict().items()}, "optimizer": opt.state_dict(),
+                "validation_monitor": monitor.state_dict()}
+        torch.save(ckpt, os.path.join(args.model_dir, "%s-%04d.model" % (prefix, epoch)))
+        if monitor.best_epoch == epoch:
+            best = os.path.join(args.model_dir, "%s-best.model" % prefix)
+            torch.save(ckpt, best)
+            print("Save new best model to {}.".format(best), flush=True)
+        return 1
     t0, last = time.time(), None
     for step in range(args.steps):
         for g in opt.param_groups:
@@ -252,9 +313,11 @@ def main(task, argv=None):
         if rank == 0 and ((step + 1) % max(1, min(int(config.LOG_FREQUENT), args.steps)) == 0 or step + 1 == args.steps):
             print("step %d  lr %.3e  loss %.4f  %.1f samples/s" % (step + 1, opt.param_groups[0]["lr"], float(last),
                                                                    (step + 1) * B * accum * world / (time.time() - t0)), flush=True)
-    if args.model_dir and rank == 0:
+        if monitor is not None and (step + 1) % max(1, args.steps_per_epoch) == 0:
+            epoch_files += epoch_end((step + 1) // max(1, args.steps_per_epoch) - 1)
+    if args.model_dir and rank == 0 and not epoch_files:      # (with epoch checkpoints written, {prefix}-0000.model is epoch 0's: kept)
         os.makedirs(args.model_dir, exist_ok=True)
-        path = os.path.join(args.model_dir, "%s-%04d.model" % (config.get("MODEL_PREFIX", "") or ("vl-bert_" + task), 0))
+        path = os.path.join(args.model_dir, "%s-%04d.model" % (prefix, 0))
         core = net.module if hasattr(net, "module") else net
         torch.save({"state_dict": {k: v.detach().cpu() for k, v in core.state_dict().items()}, "optimizer": opt.state_dict()}, path)
         print("checkpoint %s" % path, flush=True)

@@ -126,6 +126,62 @@ class LossLogger(EvalMetric):
         self._add(losses[self.slot] if self.slot is not None else torch.zeros((), dtype=torch.float32, device=losses.device), one)
 
 
+class OutputsMetric(EvalMetric):
+    """Base of the fine-tuning metrics (common/{vqa,vcr,refcoco}_metrics.py): update(outputs) takes the reference's `outputs` dict and
+    launches a kernel of csrc/finetune_metrics.hip straight into sum_metric / num_inst, which move to the logits' device at the first
+    update and stay there -- no host synchronisation before get().  CPU tensors raise (ops._p): there is no CPU path."""
+
+    def __init__(self, allreduce=False, num_replicas=1, group=None):
+        super(OutputsMetric, self).__init__(self.display, allreduce, num_replicas, group)
+
+    display = None
+
+    def _on(self, device):
+        if self.sum_metric.device != device:
+            self.sum_metric, self.num_inst = self.sum_metric.to(device), self.num_inst.to(device)
+
+    @staticmethod
+    def _logits(outputs, key="label_logits"):
+        x = outputs[key].detach()
+        if not x.is_cuda:
+            raise RuntimeError("fine-tuning metrics need GPU tensors (got %s); there is no CPU path" % x.device)
+        if x.dtype != torch.float32:
+            x = x.float()
+        return x if (x.dim() != 2 or x.stride(1) == 1) else x.contiguous()
+
+    @staticmethod
+    def _soft_label(label):
+        label = label.detach()
+        if label.dtype != torch.float32:
+            label = label.float()
+        return label if label.stride(1) == 1 else label.contiguous()
+
+
+class OutputMean(OutputsMetric):
+    """sum += outputs[name].mean() on the device (fp32, torch ops), num_inst += 1: the reference's LossLogger / AnsLoss / CNNRegLoss /
+    PositiveFraction.  optional: a name the module does not output still counts the batch."""
+    _sum_dtype = torch.float32
+    output_name, optional = None, True
+
+    def update(self, outputs):
+        if self.output_name in outputs or not self.optional:
+            v = outputs[self.output_name].detach()
+            if not v.is_cuda:
+                raise RuntimeError("fine-tuning metrics need GPU tensors (got %s); there is no CPU path" % v.device)
+            self._on(v.device)
+            self.sum_metric += v.float().mean()
+        self.num_inst += 1
+
+
+class OutputLossLogger(OutputMean):
+    """LossLogger(output_name, display_name) of the three fine-tuning metric modules."""
+
+    def __init__(self, output_name, display_name=None, allreduce=False, num_replicas=1, group=None):
+        self.output_name = output_name
+        self.display = output_name if display_name is None else display_name
+        super(OutputLossLogger, self).__init__(allreduce, num_replicas, group)
+
+
 class CompositeEvalMetric(EvalMetric):
     """The reference's composite (composite_eval_metric.py:5-69); update(source) feeds every child from the source's counters and
     losses, then zeroes the source's counters (they have been moved into the metrics)."""
@@ -143,7 +199,8 @@ class CompositeEvalMetric(EvalMetric):
     def update(self, source):
         for metric in self.metrics:
             metric.update(source)
-        source.reset_metrics()
+        if hasattr(source, "reset_metrics"):              # (an `outputs` dict of the fine-tuning metrics carries no counters to clear)
+            source.reset_metrics()
 
     def reset(self):
         for metric in self.metrics:
@@ -210,8 +267,11 @@ class ValidationMonitor(object):
     """common/callbacks/epoch_end_callbacks/validation_monitor.py:5-46: runs val_func at an epoch's end, keeps best_epoch / best_val of
     the host metric (strictly greater wins) and prints the reference's lines."""
 
-    def __init__(self, val_func, val_loader, metrics, host_metric_name="Acc", load_batch=None, verbose=True):
-        self.val_func, self.val_loader, self.metrics, self.load_batch = val_func, val_loader, metrics, load_batch
+    def __init__(self, val_func, val_loader, metrics, host_metric_name="Acc", load_batch=None, verbose=True, label_index_in_batch=None):
+        # label_index_in_batch: the reference's name of the fourth argument of the fine-tuning val_func (common/finetune_eval.py)
+        assert load_batch is None or label_index_in_batch is None
+        self.val_func, self.val_loader, self.metrics = val_func, val_loader, metrics
+        self.load_batch = label_index_in_batch if load_batch is None else load_batch
         self.host_metric_name = host_metric_name
         self.best_epoch = -1
         self.best_val = -1.0

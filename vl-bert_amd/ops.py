@@ -428,6 +428,49 @@ def soft_ce_eval(logits, C, target, loss_out, acc):
               _p(loss_out, torch.float32), _p(acc, torch.int64), _stream())
 
 
+ARGMAX_PREDICT, ARGMAX_HARD, ARGMAX_GATHER, ARGMAX_GATHER_GT = 0, 1, 2, 3
+
+
+def argmax_eval(logits, mode=ARGMAX_PREDICT, label=None, pred=None, score=None, probs=None, sum=None, count=None, C=None):
+    """Row argmax of fp32 logits [rows, >= C] with torch.argmax's rules + the fine-tuning accuracies (vlb_argmax_eval): mode 1 hard
+    int64 labels (sum int64 += hits, count += rows with label != -1), 2 sum (float64) += label[r, pred] in row order, count += rows
+    (score [rows] is the scratch), 3 sum int64 += label[r, pred] > 0.5, count += rows.  pred int32 [rows], score fp32 [rows],
+    probs fp32 [rows, >= C] (softmax) are optional outputs."""
+    rows = logits.shape[0]
+    C = logits.shape[1] if C is None else int(C)
+    if mode == ARGMAX_HARD:
+        lp, ldl = _p(label, torch.int64), 0
+        assert label.dim() == 1 and label.shape[0] == rows and label.is_contiguous()
+    elif mode != ARGMAX_PREDICT:
+        lp, ldl = _p(label, torch.float32), _ld(label)
+        assert label.shape[0] == rows
+    else:
+        lp, ldl = None, 0
+    for t in (pred, score):
+        assert t is None or (t.is_contiguous() and t.numel() >= rows)
+    _lib.call("vlb_argmax_eval", _p(logits, torch.float32), _ld(logits), rows, C, int(mode), lp, ldl, _p(pred, torch.int32),
+              _p(score, torch.float32), _p(probs, torch.float32), _ld(probs),
+              _p(sum, torch.float64 if mode == ARGMAX_GATHER else torch.int64), _p(count, torch.int64), _stream())
+
+
+def binary_cls_eval(logits, label, acc, N=None):
+    """acc int64 [4] += [correct among lab >= 0, #(lab >= 0), correct among lab == 1, #(lab == 1)] with lab = label.long(),
+    pred = logits > 0 over the first N columns (vlb_binary_cls_eval: ClsAccuracy / ClsPosAccuracy / ClsPosFraction)."""
+    N = logits.shape[1] if N is None else int(N)
+    assert label.shape[0] == logits.shape[0] and acc.numel() >= 4 and acc.is_contiguous()
+    _lib.call("vlb_binary_cls_eval", _p(logits, torch.float32), _ld(logits), _p(label, torch.float32), _ld(label), logits.shape[0], N,
+              _p(acc, torch.int64), _stream())
+
+
+def joint_hits(pred_a, label_a, pred_r, label_r, acc):
+    """acc int64 [2] += [#(pred_a == label_a and pred_r == label_r), rows] (vlb_joint_hits: JointAccuracy)."""
+    rows = pred_a.shape[0]
+    for t in (pred_a, label_a, pred_r, label_r):
+        assert t.dim() == 1 and t.shape[0] == rows and t.is_contiguous()
+    _lib.call("vlb_joint_hits", _p(pred_a, torch.int32), _p(label_a, torch.int64), _p(pred_r, torch.int32), _p(label_r, torch.int64), rows,
+              _p(acc, torch.int64), _stream())
+
+
 def bce_logits_fwd_bwd(logits, A, label, loss_out, gscale=1.0, logits_copy=None, pos_weight=1.0):
     """logits bf16 [rows, >=A] <- gscale * w * (sigmoid(x) - y) / rows in place; loss_out += BCE-with-logits * A (reference convention);
     w = pos_weight on the positive labels (VCR), 1 elsewhere."""
