@@ -137,6 +137,25 @@ def test_gemm_epilogues(ops):
         report("gemm atomic splitk=%d" % sk, C32, base + acc, 1e-4, 2e-5)
 
 
+# the run-time names of the option table (csrc/options.h) with their defaults
+OPTION_DEFAULTS = {"p8_mode": 1, "p8_keepb": 1, "p8_group": 2, "p8_min_tiles": 160, "p8_wgs": 256, "p8_ablate": 0, "p8_tile192": 1,
+                   "p8_drain": 0, "p8_lastw": 0, "nt_ring": 1, "nt_stagger": 0, "tn8_mode": 1, "tn8_wgs": 256, "tn8_uneven": 0,
+                   "tn8_m32": 0, "tn8_ablate": 0, "ln_fwd_rows": 0, "ln_bwd4": 1}
+
+
+def test_gemm_set_option_names():
+    """vlb_gemm_set_option takes every name of the table, rejects unknown names and negative values; only set calls, defaults last."""
+    lib = pkg("_lib")
+    try:
+        with pytest.raises(RuntimeError, match="unknown option"):
+            lib.gemm_set_option("no_such_option", 1)
+        with pytest.raises(RuntimeError, match="negative value"):
+            lib.gemm_set_option("p8_mode", -1)
+    finally:
+        for name, value in OPTION_DEFAULTS.items():
+            lib.gemm_set_option(name, value)
+
+
 @pytest.fixture
 def force_p8():
     """Route every eligible bf16 GEMM through the large-tile 8-phase core (gemm_p8.hip) whatever its tile count."""

@@ -25,6 +25,7 @@
 //  * every output fragment has 4 consecutive head-dim elements per lane -> 8-B bf16 stores.
 // Dropout uses the counter RNG of vlb_common.h keyed on (b, h, q, key): forward and both backward
 // orientations regenerate identical masks, nothing is stored.
+#include "options.h"
 #include "vlb_common.h"
 
 #define ATT_SP_MAX 256  // longest padded sequence one workgroup handles (template NU = SP / 32 key blocks: 4 or 8)
@@ -670,12 +671,7 @@ extern "C" int vlb_attention_bwd(const void* qkv, const float* mask, const void*
     (void)hipFuncSetAttribute((const void*)attn_bwd_kernel<8, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * (256 * ATT_D * 2) + 3 * 256 * 4);
     attr_set = true;
   }
-  static int bwd2 = -1;      // VLB_ATTN_BWD2: 1 (default) the single-evaluation backward for S <= 128; 0 the two-orientation kernel
-  if (bwd2 < 0) {
-    const char* v = getenv("VLB_ATTN_BWD2");
-    bwd2 = v ? atoi(v) : 1;
-  }
-  if (S <= 128 && bwd2)
+  if (S <= 128 && vlb_opt(VLB_OPT_ATTN_BWD2))
     hipLaunchKernelGGL(attn_bwd2_kernel, dim3(B * nh), dim3(ATT_THREADS), 4 * (128 * ATT_D * 2) + 3 * 128 * 4, stream, p);
   else if (S <= 128)
     hipLaunchKernelGGL((attn_bwd_kernel<4, 1>), dim3(B * nh), dim3(ATT_THREADS), 4 * (128 * ATT_D * 2) + 3 * 128 * 4, stream, p);

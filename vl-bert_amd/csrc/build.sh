@@ -6,7 +6,7 @@ HERE="$(cd "$(dirname "${BASH_SOURCE[0]}")" && pwd)"
 OUT="${1:-$HERE/..}"
 HIPCC="${HIPCC:-/opt/rocm/bin/hipcc}"
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wall -Wno-unused-function -ffp-contract=fast"
-SRCS="api gemm gemm_p8 gemm_tn8 layernorm embed loss metrics finetune_metrics attention optim roi_align vision f32_path comm grounding"
+SRCS="api options gemm gemm_p8 gemm_tn8 layernorm embed loss metrics finetune_metrics attention optim roi_align vision f32_path comm grounding"
 JOBS="${VLB_BUILD_JOBS:-$(nproc)}"
 mkdir -p "$HERE/obj" "$HERE/obj_f16"
 todo=()
@@ -15,10 +15,13 @@ for variant in bf16 f16; do
   for f in $SRCS; do
     [ -f "$HERE/$f.hip" ] || continue
     o="$OBJ/$f.o"
-    if [ ! -f "$o" ] || [ "$HERE/$f.hip" -nt "$o" ] || [ "$HERE/vlb_common.h" -nt "$o" ] || [ "$HERE/gemm_params.h" -nt "$o" ] \
-       || [ "$HERE/../../include/vlbert_hip.h" -nt "$o" ]; then
-      todo+=("$variant:$f")
+    stale=0
+    if [ ! -f "$o" ]; then stale=1; else
+      for dep in "$HERE/$f.hip" "$HERE"/*.h "$HERE/../../include/vlbert_hip.h"; do
+        if [ "$dep" -nt "$o" ]; then stale=1; fi
+      done
     fi
+    if [ $stale = 1 ]; then todo+=("$variant:$f"); fi
   done
 done
 if [ ${#todo[@]} -gt 0 ]; then

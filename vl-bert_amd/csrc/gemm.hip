@@ -311,17 +311,11 @@ __global__ __launch_bounds__(64 * WGM * WGN, (WGM * WGN >= 8) ? 4 : 2) void gemm
   const int ntk = (k_end - k_begin) / BK;
   if ((int)blockIdx.x >= nt || ntk <= 0) return;
   // PERSISTENT workgroups: block b walks work items w = b, b+grid, b+2*grid, ... (grid = resident workgroups).
-  // w -> tile: XCD-aware (block b runs on XCD b%8 and grid%8==0, so w%8 is this block's XCD: each XCD owns a
-  // contiguous run of tiles, bijective for any tile count), then visited in groups of `tile_group` tile-rows,
-  // column-major inside the group, so the ~64 workgroups resident on one XCD share <= tile_group A panels and a
-  // few B panels (working set fits the 4 MB L2) instead of sweeping all of B for every A panel.
-  auto tile_of = [&](int w, int& m0, int& n0) {
-    const int xcd = w & 7, q = nt >> 3, r = nt & 7;
-    const int t = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (w >> 3);
-    const int gm = p.tile_group, per_group = gm * p.ntn, gid = t / per_group, first = gid * gm;
-    const int gsz = min(p.ntm - first, gm), rem = t - gid * per_group;
-    m0 = (first + rem % gsz) * BM;
-    n0 = (rem / gsz) * BN;
+  auto tile_of = [&](int w, int& m0, int& n0) {      // work item -> tile origin (tile_order.h)
+    int tile_m, tile_n;
+    vlb_tile_of(vlb_xcd_order(w, nt), p.ntm, p.ntn, p.tile_group, tile_m, tile_n);
+    m0 = tile_m * BM;
+    n0 = tile_n * BN;
   };
   // per-thread staging addresses (16-B chunks; chunk P -> LDS byte 16*P):
   // P = it*NT + tid ; row r = P>>3 ; physical slot s = P&7 ; logical k-chunk kc = s ^ ((r>>1)&7)
@@ -505,13 +499,11 @@ __global__ __launch_bounds__(64 * WGM * WGN, 2) void gemm_nt_ring_kernel(const G
   const int nt = p.ntm * p.ntn;
   const int ntk = p.K / BK;
   if ((int)blockIdx.x >= nt || ntk <= 0) return;
-  auto tile_of = [&](int w, int& m0, int& n0) {      // XCD-aware grouped order, as in gemm_nt_bf16_kernel
-    const int xcd = w & 7, q = nt >> 3, r = nt & 7;
-    const int t = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (w >> 3);
-    const int gm = p.tile_group, per_group = gm * p.ntn, gid = t / per_group, first = gid * gm;
-    const int gsz = min(p.ntm - first, gm), rem = t - gid * per_group;
-    m0 = (first + rem % gsz) * BM;
-    n0 = (rem / gsz) * BN;
+  auto tile_of = [&](int w, int& m0, int& n0) {      // work item -> tile origin (tile_order.h)
+    int tile_m, tile_n;
+    vlb_tile_of(vlb_xcd_order(w, nt), p.ntm, p.ntn, p.tile_group, tile_m, tile_n);
+    m0 = tile_m * BM;
+    n0 = tile_n * BN;
   };
   // ---- producer: (tile, K tile) of the next stage to issue; per-thread source pointers advance in place -------------
   const bf16_t* a_src[NA];
@@ -665,13 +657,11 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_256_kernel(const GemmParams p)
   const int ntk = p.K / 32;
   if ((int)blockIdx.x >= nt) return;
 
-  auto tile_of = [&](int w, int& m0, int& n0) {   // same XCD-aware grouped order as the 2-stage kernel
-    const int xcd = w & 7, q = nt >> 3, r = nt & 7;
-    const int t = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (w >> 3);
-    const int gm = p.tile_group, per_group = gm * p.ntn, gid = t / per_group, first = gid * gm;
-    const int gsz = min(p.ntm - first, gm), rem = t - gid * per_group;
-    m0 = (first + rem % gsz) * BM;
-    n0 = (rem / gsz) * BN;
+  auto tile_of = [&](int w, int& m0, int& n0) {      // work item -> tile origin (tile_order.h)
+    int tile_m, tile_n;
+    vlb_tile_of(vlb_xcd_order(w, nt), p.ntm, p.ntn, p.tile_group, tile_m, tile_n);
+    m0 = tile_m * BM;
+    n0 = tile_n * BN;
   };
   // ---- producer: the (tile, k) of the next stage to issue and its per-thread source pointers (advanced in place)
   const bf16_t* a_src[NA];
@@ -951,19 +941,8 @@ __global__ __launch_bounds__(128 * WGN, WGN) void gemm_tn_bf16_kernel(const Gemm
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave / WGN, wn = wave % WGN;
   const int nt = p.ntm * p.ntn;
-  // tile order: each XCD owns a contiguous run of tiles (block b runs on XCD b%8 when the grid width is a multiple of 8),
-  // walked in groups of `tile_group` tile-rows, column-major inside a group, so that the ~tiles/8 workgroups sharing an
-  // L2 cover a near-square patch of the output: with a row-major run a wide output (dW of output.dense: 6 x 24 tiles)
-  // had every XCD stream all of X -- the profile showed 3.3x the algorithmic HBM bytes, at 4.8 TB/s.
-  int tile_m, tile_n;
-  {
-    const int b = blockIdx.x, xcd = b & 7, q = nt >> 3, r = nt & 7;
-    const int t = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (b >> 3);
-    const int gm = p.tile_group, per_group = gm * p.ntn, gid = t / per_group, first = gid * gm;
-    const int gsz = min(p.ntm - first, gm), rem = t - gid * per_group;
-    tile_m = first + rem % gsz;
-    tile_n = rem / gsz;
-  }
+  int tile_m, tile_n;      // one tile per workgroup, in the order of tile_order.h
+  vlb_tile_of(vlb_xcd_order(blockIdx.x, nt), p.ntm, p.ntn, p.tile_group, tile_m, tile_n);
   const int m0 = tile_m * BM, n0 = tile_n * BN;
   const int r_begin = blockIdx.y * p.k_per_split;
   const int r_end = min(p.K, r_begin + p.k_per_split);       // p.K = number of reduction rows R
@@ -1206,44 +1185,18 @@ __global__ __launch_bounds__(256) void transpose_batched_kernel(const long* __re
 // ------------------------------------------------------------------------------------
 // C ABI
 // ------------------------------------------------------------------------------------
-static int g_nt_stagger = -1;
-void vlb_nt_set_stagger(int v) { g_nt_stagger = v; }
-
-static int env_int(const char* name, int dflt) {
-  const char* v = getenv(name);
-  return v ? atoi(v) : dflt;
-}
-
 template <int BM, int BN, int WGM, int WGN, int EPI>
 static int launch_gemm_cfg(GemmParams& p, int splits, hipStream_t stream) {
-  constexpr int smem = 2 * (BM + BN) * 64 * 2;
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute((const void*)gemm_nt_bf16_kernel<BM, BN, WGM, WGN, EPI>, hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-    attr_set = true;
-  }
-  static const int group = env_int("VLB_GEMM_TILE_GROUP", 4);
-  p.ntm = vlb_cdiv(p.M, BM);
-  p.ntn = vlb_cdiv(p.N, BN);
-  p.tile_group = group < 1 ? 1 : group;
-  // persistent grid: the workgroups that are resident at once (2 per CU with 48-64 KB LDS each on 256 CUs),
-  // a multiple of 8 so that work item w and block b stay on the same XCD
-  static const int resident = env_int("VLB_GEMM_RESIDENT", 512);
-  int gx = p.ntm * p.ntn;
-  int cap = resident / splits;
+  // the workgroups that are resident at once, per K slice
+  int cap = vlb_opt(VLB_OPT_RESIDENT) / splits;
   if (cap < 8) cap = 8;
-  cap &= ~7;
-  if (gx > cap) gx = cap;
-  dim3 grid(gx, splits);
-  hipLaunchKernelGGL((gemm_nt_bf16_kernel<BM, BN, WGM, WGN, EPI>), grid, dim3(64 * WGM * WGN), smem, stream, p);
-  VLB_CHECK_LAUNCH("vlb_gemm_nt_bf16");
-  return VLB_OK;
+  return launch_persistent<gemm_nt_bf16_kernel<BM, BN, WGM, WGN, EPI>>(2 * (BM + BN) * 64 * 2, 64 * WGM * WGN, BM, BN, cap & ~7,
+                                                                       vlb_opt(VLB_OPT_TILE_GROUP), p, splits, stream, "vlb_gemm_nt_bf16");
 }
 
 // which single-epilogue instantiation serves this call (-1: the generic kernel with the runtime dispatch)
 static int epi_class(const GemmParams& p) {
-  static const int specialise = env_int("VLB_GEMM_EPI_SPECIALISE", 1);
-  if (!specialise || p.out_f32 != 0 || p.res_stats || p.c_f16) return -1;
+  if (!vlb_opt(VLB_OPT_EPI_SPECIALISE) || p.out_f32 != 0 || p.res_stats || p.c_f16) return -1;
   if (p.act == 0) return p.res ? (p.drop_thr ? 3 : 4) : (p.drop_thr ? -1 : 0);
   if (p.act == 4) return 1;
   if (p.act == 5) return 2;
@@ -1255,69 +1208,32 @@ static int epi_class(const GemmParams& p) {
 
 template <int BM, int BN, int WGM, int WGN>
 static int launch_gemm_epi(GemmParams& p, int splits, hipStream_t stream) {
-  switch (epi_class(p)) {
-    case 0: return launch_gemm_cfg<BM, BN, WGM, WGN, 0>(p, splits, stream);
-    case 1: return launch_gemm_cfg<BM, BN, WGM, WGN, 1>(p, splits, stream);
-    case 2: return launch_gemm_cfg<BM, BN, WGM, WGN, 2>(p, splits, stream);
-    case 3: return launch_gemm_cfg<BM, BN, WGM, WGN, 3>(p, splits, stream);
-    case 4: return launch_gemm_cfg<BM, BN, WGM, WGN, 4>(p, splits, stream);
-    case 5: return launch_gemm_cfg<BM, BN, WGM, WGN, 5>(p, splits, stream);
-    case 6: return launch_gemm_cfg<BM, BN, WGM, WGN, 6>(p, splits, stream);
-    case 7: return launch_gemm_cfg<BM, BN, WGM, WGN, 7>(p, splits, stream);
-    case 8: return launch_gemm_cfg<BM, BN, WGM, WGN, 8>(p, splits, stream);
-    default: return launch_gemm_cfg<BM, BN, WGM, WGN, -1>(p, splits, stream);
-  }
+  return dispatch_epi(epi_class(p), std::integer_sequence<int, -1, 0, 1, 2, 3, 4, 5, 6, 7, 8>{}, VLB_ERR_ARG, [&](auto epi) {
+    return launch_gemm_cfg<BM, BN, WGM, WGN, decltype(epi)::value>(p, splits, stream);
+  });
 }
 
 // ring kernels: 128x128 (8 waves, 4 stages = 128 KiB: one workgroup per CU) and 128x64 (4 waves, 3 stages = 72 KiB: two per CU)
-static int g_nt_ring = -1;        // VLB_GEMM_NT_RING: 0 off | 1 auto (default) | 2 force 128x128 | 3 force 128x64
-void vlb_nt_set_ring(int v) { g_nt_ring = v; }
-
-template <int BM, int BN, int WGM, int WGN, int EPI, int NS>
-static int launch_ring_cfg(GemmParams& p, hipStream_t stream) {
-  constexpr int smem = NS * (BM + BN) * 128;
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute((const void*)gemm_nt_ring_kernel<BM, BN, WGM, WGN, EPI, NS>, hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-    attr_set = true;
-  }
-  static const int group = env_int("VLB_GEMM_TILE_GROUP", 4);
-  p.ntm = vlb_cdiv(p.M, BM);
-  p.ntn = vlb_cdiv(p.N, BN);
-  p.tile_group = group < 1 ? 1 : group;
-  const int cap = 256 * (163840 / smem);       // resident workgroups (a multiple of 8: work item w and block b share an XCD)
-  int gx = p.ntm * p.ntn;
-  if (gx > cap) gx = cap;
-  hipLaunchKernelGGL((gemm_nt_ring_kernel<BM, BN, WGM, WGN, EPI, NS>), dim3(gx), dim3(64 * WGM * WGN), smem, stream, p);
-  VLB_CHECK_LAUNCH("vlb_gemm_nt_bf16(ring)");
-  return VLB_OK;
-}
-
 template <int BM, int BN, int WGM, int WGN, int NS>
 static int launch_ring_epi(GemmParams& p, hipStream_t stream) {
-  switch (epi_class(p)) {
-    case 0: return launch_ring_cfg<BM, BN, WGM, WGN, 0, NS>(p, stream);
-    case 1: return launch_ring_cfg<BM, BN, WGM, WGN, 1, NS>(p, stream);
-    case 2: return launch_ring_cfg<BM, BN, WGM, WGN, 2, NS>(p, stream);
-    case 3: return launch_ring_cfg<BM, BN, WGM, WGN, 3, NS>(p, stream);
-    case 4: return launch_ring_cfg<BM, BN, WGM, WGN, 4, NS>(p, stream);
-    case 5: return launch_ring_cfg<BM, BN, WGM, WGN, 5, NS>(p, stream);
-    case -1: return launch_ring_cfg<BM, BN, WGM, WGN, -1, NS>(p, stream);
-    default: return 1;      // the Bottleneck-tail epilogues stay on the two-stage kernel
-  }
+  constexpr int smem = NS * (BM + BN) * 128;
+  // 1 (not taken): the Bottleneck-tail epilogues stay on the two-stage kernel
+  return dispatch_epi(epi_class(p), std::integer_sequence<int, -1, 0, 1, 2, 3, 4, 5>{}, 1, [&](auto epi) {
+    return launch_persistent<gemm_nt_ring_kernel<BM, BN, WGM, WGN, decltype(epi)::value, NS>>(
+        smem, 64 * WGM * WGN, BM, BN, 256 * (163840 / smem), vlb_opt(VLB_OPT_TILE_GROUP), p, 1, stream, "vlb_gemm_nt_bf16(ring)");
+  });
 }
 
 // > 0: not taken
-static int gemm_ring_try(GemmParams& p, int splits, bool want_narrow, hipStream_t stream) {
-  if (g_nt_ring < 0) g_nt_ring = env_int("VLB_GEMM_NT_RING", 1);
-  if (!g_nt_ring || splits != 1 || p.c_split_stride != 0 || p.k_per_split < p.K) return 1;
+static int gemm_ring_try(GemmParams& p, int splits, hipStream_t stream) {
+  const int ring = vlb_opt(VLB_OPT_NT_RING);
+  if (!ring || splits != 1 || p.c_split_stride != 0 || p.k_per_split < p.K) return 1;
   // auto: measured on MI355X (tools/p8_check.py ring) the deeper prefetch only pays where a launch has about one tile per CU and a
   // long K loop -- the N = 768 GEMMs of a 32..64-sample per-GPU batch (M = 3232 / 6464: 70 -> 56 us for ffn2 fwd, 52 -> 42 us for
   // the QKV dgrad at M = 6464); with several workgroups per CU the two-stage kernel's co-resident workgroups already cover the
   // latency and its smaller LDS footprint wins (M >= 12928: 5-25 % slower with the ring)
-  if (g_nt_ring == 1 && !(p.N <= 1024 && p.M <= 8192 && p.M >= 1024 && p.K >= 512)) return 1;
-  const bool narrow = g_nt_ring == 3 || g_nt_ring == 1;
-  (void)want_narrow;
+  if (ring == 1 && !(p.N <= 1024 && p.M <= 8192 && p.M >= 1024 && p.K >= 512)) return 1;
+  const bool narrow = ring == 3 || ring == 1;
   // (round 5, measured and removed: 128x128 tiles on FOUR waves -- 64x64 per wave, 0.5 fragment reads per MFMA instead of 0.75, 64
   // FLOP per operand byte instead of 43, three stages = 96 KiB, one block per CU; the N = 768 launches of a 32-sample batch are 156
   // such tiles.  us per launch at M = 3232 / 6464, K = 3072: 39.5 / 75.6 against 34.2 / 55.3 for the 128x64 form: one wave per SIMD
@@ -1362,8 +1278,7 @@ static int gemm_nt_impl(const void* A, long lda, const void* B, long ldb, void* 
   p.res_stats = res_stats; p.res_gamma = res_gamma; p.res_beta = res_beta; p.c_f16 = out_f16 ? 1 : 0;
   p.drop_thr = vlb_drop_thr(drop_p); p.drop_scale = vlb_drop_scale(p.drop_thr); p.seed = seed; p.tag = tag;
   p.C = C; p.ldc = ldc; p.out_f32 = out_mode; p.c_split_stride = 0;
-  if (g_nt_stagger < 0) g_nt_stagger = env_int("VLB_GEMM_NT_STAGGER", 0);
-  p.stagger = g_nt_stagger;
+  p.stagger = vlb_opt(VLB_OPT_NT_STAGGER);
   int splits = 1;
   const int ktiles = K / 64;
   if (out_mode == 2) {
@@ -1398,32 +1313,20 @@ static int gemm_nt_impl(const void* A, long lda, const void* B, long ldb, void* 
   // have enough tiles for one workgroup per CU: the tied decoder X . E^T (B = 47 MB word embeddings; 1.00 -> 0.80 ms).
   // With an L2-resident weight matrix and K = 768 (QKV, FFN) the 128x128 kernel is as fast (measured) and keeps two
   // workgroups per CU.  VLB_GEMM_256: 0 off | 1 this rule (default) | n >= 2: every plain GEMM with at least n tiles.
-  static const int use256 = env_int("VLB_GEMM_256", 1);
+  const int use256 = vlb_opt(VLB_OPT_NT_256);
   const long tiles256 = (long)vlb_cdiv(M, 256) * vlb_cdiv(N, 256);
   const bool big_b = (long)N * K * 2 >= (24L << 20) && tiles256 >= 512;
   if (use256 && out_mode == 0 && splits == 1 && act == 0 && !res && !p.drop_thr &&
       (use256 == 1 ? big_b : tiles256 >= use256)) {
-    constexpr int smem = 3 * (256 + 256) * 64;
-    static bool attr_set = false;
-    if (!attr_set) {
-      (void)hipFuncSetAttribute((const void*)gemm_nt_256_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-      attr_set = true;
-    }
-    static const int group5 = env_int("VLB_GEMM_256_GROUP", 2);
-    p.ntm = vlb_cdiv(M, 256);
-    p.ntn = vlb_cdiv(N, 256);
-    p.tile_group = group5 < 1 ? 1 : group5;
-    int gx = p.ntm * p.ntn;
-    if (gx > 256) gx = 256;             // one workgroup per CU
-    hipLaunchKernelGGL(gemm_nt_256_kernel, dim3(gx), dim3(512), smem, stream, p);
-    VLB_CHECK_LAUNCH("vlb_gemm_nt_bf16(256)");
-    return VLB_OK;
+    // one workgroup per CU
+    return launch_persistent<gemm_nt_256_kernel>(3 * (256 + 256) * 64, 512, 256, 256, 256, vlb_opt(VLB_OPT_NT_256_GROUP), p, 1, stream,
+                                                 "vlb_gemm_nt_bf16(256)");
   }
   // narrow-N tile when the 128x128 grid would leave most CUs idle
   const long tiles128 = (long)vlb_cdiv(M, 128) * vlb_cdiv(N, 128) * splits;
   const bool narrow = tiles128 < 384 || N <= 64;
   {
-    const int took = gemm_ring_try(p, splits, narrow, stream);
+    const int took = gemm_ring_try(p, splits, stream);
     if (took <= 0) return took;
   }
   if (narrow) return launch_gemm<128, 64>(p, splits, stream);
@@ -1458,23 +1361,12 @@ extern "C" int vlb_gemm_nt_bf16_ex(const void* A, long lda, const void* B, long 
 // Epilogues: bias (act 0), bias + ReLU (act 2: the Bottleneck's conv2), x (aux > 0) (act 8: its data gradient with the
 // mirrored-tap operand of vlb_conv_weight_prepare).
 // ------------------------------------------------------------------------------------
-template <int BN, int WGN, int EPI>
-static int launch_conv_cfg(GemmParams& p, hipStream_t stream) {
-  constexpr int smem = 2 * (128 + BN) * 64 * 2;
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute((const void*)gemm_nt_bf16_kernel<128, BN, 2, WGN, EPI, true>, hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-    attr_set = true;
-  }
-  static const int group = env_int("VLB_GEMM_TILE_GROUP", 4);
-  p.ntm = vlb_cdiv(p.M, 128);
-  p.ntn = vlb_cdiv(p.N, BN);
-  p.tile_group = group < 1 ? 1 : group;
-  int gx = p.ntm * p.ntn;
-  if (gx > 512) gx = 512;
-  hipLaunchKernelGGL((gemm_nt_bf16_kernel<128, BN, 2, WGN, EPI, true>), dim3(gx, 1), dim3(64 * 2 * WGN), smem, stream, p);
-  VLB_CHECK_LAUNCH("vlb_conv3x3_nhwc_bf16");
-  return VLB_OK;
+template <int BN, int WGN>
+static int launch_conv(GemmParams& p, hipStream_t stream) {
+  return dispatch_epi(p.act == 0 ? 0 : p.act == 2 ? 5 : 8, std::integer_sequence<int, 0, 5, 8>{}, VLB_ERR_ARG, [&](auto epi) {
+    return launch_persistent<gemm_nt_bf16_kernel<128, BN, 2, WGN, decltype(epi)::value, true>>(
+        2 * (128 + BN) * 64 * 2, 64 * 2 * WGN, 128, BN, 512, vlb_opt(VLB_OPT_TILE_GROUP), p, 1, stream, "vlb_conv3x3_nhwc_bf16");
+  });
 }
 
 extern "C" int vlb_conv3x3_nhwc_bf16(const void* x, int N, int H, int W, int C, int dil, const void* w, long ldw, void* y, long ldy,
@@ -1496,9 +1388,7 @@ extern "C" int vlb_conv3x3_nhwc_bf16(const void* x, int N, int H, int W, int C, 
   p.conv_C = C; p.conv_H = H; p.conv_W = W; p.conv_dil = dil; p.zero = (const bf16_t*)zero16;
   const long tiles128 = (long)vlb_cdiv(p.M, 128) * vlb_cdiv(O, 128);
   const bool narrow = tiles128 < 384 || O <= 64;
-  if (act == 0) return narrow ? launch_conv_cfg<64, 2, 0>(p, stream) : launch_conv_cfg<128, 4, 0>(p, stream);
-  if (act == 2) return narrow ? launch_conv_cfg<64, 2, 5>(p, stream) : launch_conv_cfg<128, 4, 5>(p, stream);
-  return narrow ? launch_conv_cfg<64, 2, 8>(p, stream) : launch_conv_cfg<128, 4, 8>(p, stream);
+  return narrow ? launch_conv<64, 2>(p, stream) : launch_conv<128, 4>(p, stream);
 }
 
 // ------------------------------------------------------------------------------------
@@ -1551,6 +1441,18 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* __restr
   }
 }
 
+// C (fp32, (+)= when accumulate, rows scaled by rowscale if given) or Cb (bf16, overwritten; ldc is then ITS leading dimension) =
+// the sum of the `splits` slabs of [Mo, ldw] floats in `workspace`
+static int launch_splitk_reduce(const float* workspace, long slab_stride, int splits, float* C, long ldc, int Mo, int No, long ldw,
+                                int accumulate, const float* rowscale, hipStream_t stream, const char* name, bf16_t* Cb = nullptr) {
+  long blocks = ((long)Mo * (ldw / 4) + 255) / 256;
+  if (blocks > 2048) blocks = 2048;
+  hipLaunchKernelGGL(splitk_reduce_kernel, dim3((int)blocks), dim3(256), 0, stream, workspace, slab_stride, splits, C, ldc, Mo, No, (int)ldw,
+                     Cb, ldc, accumulate, rowscale);
+  VLB_CHECK_LAUNCH(name);
+  return VLB_OK;
+}
+
 static int wgrad_pick_splits(int M, int N, int K, long workspace_floats) {
   const int ktiles = K / 64;
   const long tiles = (long)vlb_cdiv(M, 128) * vlb_cdiv(N, 128);
@@ -1600,13 +1502,7 @@ extern "C" int vlb_wgrad_nt_bf16(const void* A, long lda, const void* B, long ld
   }
   int rc = launch_gemm<128, 128>(p, nsp, stream);
   if (rc) return rc;
-  if (nsp > 1) {
-    long blocks = ((long)M * (ldw / 4) + 255) / 256;
-    if (blocks > 2048) blocks = 2048;
-    hipLaunchKernelGGL(splitk_reduce_kernel, dim3((int)blocks), dim3(256), 0, stream, workspace, (long)M * ldw, nsp, C, ldc, M, N,
-                       (int)ldw, (bf16_t*)nullptr, 0L, 1);
-    VLB_CHECK_LAUNCH("vlb_wgrad_nt_bf16(reduce)");
-  }
+  if (nsp > 1) return launch_splitk_reduce(workspace, (long)M * ldw, nsp, C, ldc, M, N, ldw, 1, nullptr, stream, "vlb_wgrad_nt_bf16(reduce)");
   return VLB_OK;
 }
 
@@ -1634,12 +1530,8 @@ extern "C" int vlb_gemm_nt_bf16_splitk(const void* A, long lda, const void* B, l
   p.C = workspace; p.ldc = ldw; p.out_f32 = 1; p.c_split_stride = (long)M * ldw;
   int rc = launch_gemm<128, 128>(p, nsp, stream);
   if (rc) return rc;
-  long blocks = ((long)M * (ldw / 4) + 255) / 256;
-  if (blocks > 2048) blocks = 2048;
-  hipLaunchKernelGGL(splitk_reduce_kernel, dim3((int)blocks), dim3(256), 0, stream, workspace, (long)M * ldw, nsp, (float*)nullptr, 0L, M, N,
-                     (int)ldw, (bf16_t*)C, ldc, 0);
-  VLB_CHECK_LAUNCH("vlb_gemm_nt_bf16_splitk(reduce)");
-  return VLB_OK;
+  return launch_splitk_reduce(workspace, (long)M * ldw, nsp, nullptr, ldc, M, N, ldw, 0, nullptr, stream, "vlb_gemm_nt_bf16_splitk(reduce)",
+                              (bf16_t*)C);
 }
 
 struct SplitkReduceGroup {
@@ -1681,6 +1573,53 @@ __global__ __launch_bounds__(256) void splitk_reduce_group_kernel(const SplitkRe
   }
 }
 
+template <auto KERNEL>
+static void tn128_launch_kernel(dim3 grid, int block, const GemmParams& p, float* colsum, hipStream_t stream) {
+  constexpr int smem = 2 * 2 * 64 * 128 * 2;
+  static bool attr_set = false;
+  if (!attr_set) {
+    (void)hipFuncSetAttribute((const void*)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, smem);
+    attr_set = true;
+  }
+  hipLaunchKernelGGL(KERNEL, grid, dim3(block), smem, stream, p, colsum);
+}
+
+// The 128x128 TN kernel on C[Mo,No] (fp32) (+)= A[R,Mo]^T B[R,No]: split choice, slab (K slices, or a row scale -- applied by the reduce
+// kernel, so it always goes through a slab) or direct output, launch, reduce.  The caller has filled p's operands, tile_group and, for
+// CONV (B = the NHWC activation, gathered by the kernel), the convolution geometry.
+template <bool CONV>
+static int tn128_launch(GemmParams& p, float* C, long ldc, int R, int Mo, int No, float* colsum, const float* rowscale, float* workspace,
+                        long workspace_floats, int accumulate, hipStream_t stream, const char* name) {
+  const int Rp = vlb_cdiv(R, 64) * 64;
+  const int splits = wgrad_pick_splits(Mo, No, Rp, workspace ? workspace_floats : 0);
+  const int ktiles = Rp / 64;
+  const int per = vlb_cdiv(ktiles, splits);
+  const int nsp = vlb_cdiv(ktiles, per);
+  const long ldw = (No + 3) / 4 * 4;
+  const bool slab = nsp > 1 || rowscale != nullptr;
+  VLB_CHECK_ARG(!rowscale || (workspace && workspace_floats >= (long)nsp * Mo * ldw), "%s: rowscale needs a workspace of %ld floats", name,
+                (long)nsp * Mo * ldw);
+  p.M = Mo; p.N = No; p.K = R; p.k_per_split = per * 64;
+  p.drop_scale = 1.f;
+  if (!slab) {
+    p.C = C; p.ldc = ldc; p.out_f32 = accumulate ? 3 : 1; p.c_split_stride = 0;
+  } else {
+    p.C = workspace; p.ldc = ldw; p.out_f32 = 1; p.c_split_stride = (long)Mo * ldw;
+  }
+  p.ntm = vlb_cdiv(Mo, 128); p.ntn = vlb_cdiv(No, 128);
+  const dim3 grid(p.ntm * p.ntn, nsp);
+  if (CONV || vlb_opt(VLB_OPT_TN_WAVES8)) {
+    if (p.out_f32 == 3) tn128_launch_kernel<gemm_tn_bf16_kernel<4, 3, CONV>>(grid, 512, p, colsum, stream);
+    else tn128_launch_kernel<gemm_tn_bf16_kernel<4, 1, CONV>>(grid, 512, p, colsum, stream);
+  } else if constexpr (!CONV) {
+    if (p.out_f32 == 3) tn128_launch_kernel<gemm_tn_bf16_kernel<2, 3>>(grid, 256, p, colsum, stream);
+    else tn128_launch_kernel<gemm_tn_bf16_kernel<2, 1>>(grid, 256, p, colsum, stream);
+  }
+  VLB_CHECK_LAUNCH(name);
+  if (slab) return launch_splitk_reduce(workspace, (long)Mo * ldw, nsp, C, ldc, Mo, No, ldw, accumulate, rowscale, stream, name);
+  return VLB_OK;
+}
+
 // dW[Mo,No] (fp32) (+)= A[R,Mo]^T B[R,No]; optional colsum[Mo] += column sums of A (bias gradient).
 // accumulate == 0 overwrites dW (first micro-batch of an optimizer step: no zero fill and no read-modify-write).
 static int wgrad_tn_impl(const void* A, long lda, const void* B, long ldb, float* C, long ldc, int R, int Mo, int No, float* colsum,
@@ -1696,76 +1635,18 @@ static int wgrad_tn_impl(const void* A, long lda, const void* B, long ldb, float
     const int used = vlb_gemm_tn8_try(q, C, ldc, colsum, workspace, workspace_floats, accumulate, rowscale != nullptr, stream);
     if (used < 0) return used;
     if (used > 0) {
-      if (used > 1 || rowscale) {
-        const long ldw8 = (No + 3) / 4 * 4;
-        long blocks = ((long)Mo * (ldw8 / 4) + 255) / 256;
-        if (blocks > 2048) blocks = 2048;
-        hipLaunchKernelGGL(splitk_reduce_kernel, dim3((int)blocks), dim3(256), 0, stream, workspace, (long)Mo * ldw8, used, C, ldc, Mo, No,
-                           (int)ldw8, (bf16_t*)nullptr, 0L, accumulate, rowscale);
-        VLB_CHECK_LAUNCH("vlb_wgrad_tn_bf16(tn8 reduce)");
-      }
+      const long ldw8 = (No + 3) / 4 * 4;
+      if (used > 1 || rowscale)
+        return launch_splitk_reduce(workspace, (long)Mo * ldw8, used, C, ldc, Mo, No, ldw8, accumulate, rowscale, stream,
+                                    "vlb_wgrad_tn_bf16(tn8 reduce)");
       return VLB_OK;
     }
   }
-  const int Rp = vlb_cdiv(R, 64) * 64;
-  const int splits = wgrad_pick_splits(Mo, No, Rp, workspace ? workspace_floats : 0);
-  const int ktiles = Rp / 64;
-  const int per = vlb_cdiv(ktiles, splits);
-  const int nsp = vlb_cdiv(ktiles, per);
-  const long ldw = (No + 3) / 4 * 4;
-  const bool slab = nsp > 1 || rowscale != nullptr;      // a row scale is applied by the reduce kernel: always go through a slab
-  VLB_CHECK_ARG(!rowscale || (workspace && workspace_floats >= (long)nsp * Mo * ldw), "vlb_wgrad_tn: rowscale needs a workspace of %ld floats",
-                (long)nsp * Mo * ldw);
   GemmParams p = {};
   p.A = (const bf16_t*)A; p.lda = lda; p.B = (const bf16_t*)B; p.ldb = ldb;
-  p.M = Mo; p.N = No; p.K = R; p.k_per_split = per * 64;
-  p.bias = nullptr; p.act = 0; p.aux = nullptr; p.ldaux = 0; p.pre = nullptr; p.ldpre = 0; p.res = nullptr; p.ldres = 0;
-  p.drop_thr = 0; p.drop_scale = 1.f; p.seed = nullptr; p.tag = 0;
-  if (!slab) {
-    p.C = C; p.ldc = ldc; p.out_f32 = accumulate ? 3 : 1; p.c_split_stride = 0;
-  } else {
-    p.C = workspace; p.ldc = ldw; p.out_f32 = 1; p.c_split_stride = (long)Mo * ldw;
-  }
-  p.ntm = vlb_cdiv(Mo, 128); p.ntn = vlb_cdiv(No, 128);
-  {   // near-square per-XCD patches for wide outputs; tall outputs (decoder: 239 x 6 tiles) already share their A panel row-wise
-    static const int tn_group = env_int("VLB_GEMM_TN_GROUP", -1);
-    int gm = 1;
-    if (tn_group > 0) gm = tn_group;
-    else if (2 * p.ntn >= p.ntm) {
-      const double per_xcd = (double)p.ntm * p.ntn / 8.0;
-      gm = (int)(sqrt(per_xcd) + 0.5);
-    }
-    if (gm > p.ntm) gm = p.ntm;
-    if (gm < 1) gm = 1;
-    p.tile_group = gm;
-  }
-  constexpr int smem = 2 * 2 * 64 * 128 * 2;
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute((const void*)gemm_tn_bf16_kernel<2, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-    (void)hipFuncSetAttribute((const void*)gemm_tn_bf16_kernel<2, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-    (void)hipFuncSetAttribute((const void*)gemm_tn_bf16_kernel<4, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-    (void)hipFuncSetAttribute((const void*)gemm_tn_bf16_kernel<4, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-    attr_set = true;
-  }
-  static const int waves8 = env_int("VLB_GEMM_TN_WAVES8", 1);
-  const dim3 grid(p.ntm * p.ntn, nsp);
-  if (waves8) {
-    if (p.out_f32 == 3) hipLaunchKernelGGL((gemm_tn_bf16_kernel<4, 3>), grid, dim3(512), smem, stream, p, colsum);
-    else hipLaunchKernelGGL((gemm_tn_bf16_kernel<4, 1>), grid, dim3(512), smem, stream, p, colsum);
-  } else {
-    if (p.out_f32 == 3) hipLaunchKernelGGL((gemm_tn_bf16_kernel<2, 3>), grid, dim3(256), smem, stream, p, colsum);
-    else hipLaunchKernelGGL((gemm_tn_bf16_kernel<2, 1>), grid, dim3(256), smem, stream, p, colsum);
-  }
-  VLB_CHECK_LAUNCH("vlb_wgrad_tn_bf16");
-  if (slab) {
-    long blocks = ((long)Mo * (ldw / 4) + 255) / 256;
-    if (blocks > 2048) blocks = 2048;
-    hipLaunchKernelGGL(splitk_reduce_kernel, dim3((int)blocks), dim3(256), 0, stream, workspace, (long)Mo * ldw, nsp, C, ldc, Mo, No,
-                       (int)ldw, (bf16_t*)nullptr, 0L, accumulate, rowscale);
-    VLB_CHECK_LAUNCH("vlb_wgrad_tn_bf16(reduce)");
-  }
-  return VLB_OK;
+  const int ntm = vlb_cdiv(Mo, 128), ntn = vlb_cdiv(No, 128), tn_group = vlb_opt(VLB_OPT_TN_GROUP);
+  p.tile_group = tn_group > 0 ? (tn_group < ntm ? tn_group : ntm) : vlb_square_tile_group(ntm, ntn);
+  return tn128_launch<false>(p, C, ldc, R, Mo, No, colsum, rowscale, workspace, workspace_floats, accumulate, stream, "vlb_wgrad_tn_bf16");
 }
 
 extern "C" int vlb_wgrad_tn_bf16(const void* A, long lda, const void* B, long ldb, float* C, long ldc, int R, int Mo, int No,
@@ -1835,54 +1716,13 @@ extern "C" int vlb_conv3x3_wgrad_tn_bf16(const void* dy, long lddy, const void* 
   VLB_CHECK_ARG(C > 0 && (C % 128) == 0, "vlb_conv3x3_wgrad_tn_bf16: C=%d must be a multiple of 128", C);
   VLB_CHECK_ARG((lddy % 8) == 0 && lddy >= O && (lddw % 4) == 0 && lddw >= 9L * C, "vlb_conv3x3_wgrad_tn_bf16: bad leading dimensions");
   VLB_CHECK_ARG(H > 0 && W > 0 && dil >= 1 && (long)N * H * W < (1L << 24), "vlb_conv3x3_wgrad_tn_bf16: bad geometry (rows must be < 2^24)");
-  const int R = N * H * W, Mo = O, No = 9 * C;
-  const int Rp = vlb_cdiv(R, 64) * 64;
-  const int splits = wgrad_pick_splits(Mo, No, Rp, workspace ? workspace_floats : 0);
-  const int ktiles = Rp / 64;
-  const int per = vlb_cdiv(ktiles, splits);
-  const int nsp = vlb_cdiv(ktiles, per);
-  const long ldw = No;
-  const bool slab = nsp > 1 || rowscale != nullptr;
-  VLB_CHECK_ARG(!rowscale || (workspace && workspace_floats >= (long)nsp * Mo * ldw), "vlb_conv3x3_wgrad_tn_bf16: rowscale needs a workspace of %ld floats",
-                (long)nsp * Mo * ldw);
+  const int R = N * H * W, No = 9 * C;
   GemmParams p = {};
   p.A = (const bf16_t*)dy; p.lda = lddy; p.B = (const bf16_t*)x; p.ldb = C;
-  p.M = Mo; p.N = No; p.K = R; p.k_per_split = per * 64;
-  p.bias = nullptr; p.act = 0; p.aux = nullptr; p.ldaux = 0; p.pre = nullptr; p.ldpre = 0; p.res = nullptr; p.ldres = 0;
-  p.drop_thr = 0; p.drop_scale = 1.f; p.seed = nullptr; p.tag = 0;
   p.conv_C = C; p.conv_H = H; p.conv_W = W; p.conv_dil = dil; p.zero = nullptr;
-  if (!slab) {
-    p.C = dW; p.ldc = lddw; p.out_f32 = accumulate ? 3 : 1; p.c_split_stride = 0;
-  } else {
-    p.C = workspace; p.ldc = ldw; p.out_f32 = 1; p.c_split_stride = (long)Mo * ldw;
-  }
-  p.ntm = vlb_cdiv(Mo, 128); p.ntn = No / 128;
-  {
-    const double per_xcd = (double)p.ntm * p.ntn / 8.0;
-    int gm = (2 * p.ntn >= p.ntm) ? (int)(sqrt(per_xcd) + 0.5) : 1;
-    if (gm > p.ntm) gm = p.ntm;
-    if (gm < 1) gm = 1;
-    p.tile_group = gm;
-  }
-  constexpr int smem = 2 * 2 * 64 * 128 * 2;
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute((const void*)gemm_tn_bf16_kernel<4, 1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-    (void)hipFuncSetAttribute((const void*)gemm_tn_bf16_kernel<4, 3, true>, hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-    attr_set = true;
-  }
-  const dim3 grid(p.ntm * p.ntn, nsp);
-  if (p.out_f32 == 3) hipLaunchKernelGGL((gemm_tn_bf16_kernel<4, 3, true>), grid, dim3(512), smem, stream, p, (float*)nullptr);
-  else hipLaunchKernelGGL((gemm_tn_bf16_kernel<4, 1, true>), grid, dim3(512), smem, stream, p, (float*)nullptr);
-  VLB_CHECK_LAUNCH("vlb_conv3x3_wgrad_tn_bf16");
-  if (slab) {
-    long blocks = ((long)Mo * (ldw / 4) + 255) / 256;
-    if (blocks > 2048) blocks = 2048;
-    hipLaunchKernelGGL(splitk_reduce_kernel, dim3((int)blocks), dim3(256), 0, stream, workspace, (long)Mo * ldw, nsp, dW, lddw, Mo, No,
-                       (int)ldw, (bf16_t*)nullptr, 0L, accumulate, rowscale);
-    VLB_CHECK_LAUNCH("vlb_conv3x3_wgrad_tn_bf16(reduce)");
-  }
-  return VLB_OK;
+  p.tile_group = vlb_square_tile_group(vlb_cdiv(O, 128), No / 128);
+  return tn128_launch<true>(p, dW, lddw, R, O, No, nullptr, rowscale, workspace, workspace_floats, accumulate, stream,
+                            "vlb_conv3x3_wgrad_tn_bf16");
 }
 
 extern "C" int vlb_transpose_bf16(const void* in, long ldi, void* out, long ldo, int R, int C, float* colsum,

@@ -525,13 +525,11 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_p8_kernel(const GemmParams p) 
     t[1] = __builtin_amdgcn_s_memrealtime();
   }
 
-  auto tile_of = [&](int w, int& m0, int& n0) {   // XCD-aware grouped order (see gemm_nt_bf16_kernel)
-    const int xcd = w & 7, q = nt >> 3, r = nt & 7;
-    const int t = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (w >> 3);
-    const int gm = p.tile_group, per_group = gm * p.ntn, gid = t / per_group, first = gid * gm;
-    const int gsz = min(p.ntm - first, gm), rem = t - gid * per_group;
-    m0 = (first + rem % gsz) * BM;
-    n0 = (rem / gsz) * BN;
+  auto tile_of = [&](int w, int& m0, int& n0) {      // work item -> tile origin (tile_order.h)
+    int tile_m, tile_n;
+    vlb_tile_of(vlb_xcd_order(w, nt), p.ntm, p.ntn, p.tile_group, tile_m, tile_n);
+    m0 = tile_m * BM;
+    n0 = tile_n * BN;
   };
 
   // ---------------- producer: a continuous stream of K tiles over this workgroup's work items ----------------
@@ -796,131 +794,22 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_p8_kernel(const GemmParams p) 
   }
 }
 
-static int g_p8_wgs = 256;
-
-template <int FMH, int EPI, bool KEEPB>
-int p8_launch(GemmParams& p, int group, hipStream_t stream) {
-  constexpr int smem = 163840;
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute((const void*)gemm_nt_p8_kernel<FMH, EPI, KEEPB>, hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-    if (e != hipSuccess) {
-      vlb_set_error("gemm_p8: cannot reserve %d bytes of LDS: %s", smem, hipGetErrorString(e));
-      return VLB_ERR_HIP;
-    }
-    attr_set = true;
-  }
-  p.ntm = vlb_cdiv(p.M, 64 * FMH);
-  p.ntn = vlb_cdiv(p.N, 256);
-  p.tile_group = group;
-  int gx = p.ntm * p.ntn;
-  const int cap = (g_p8_wgs >= 8 && g_p8_wgs <= 256) ? (g_p8_wgs & ~7) : 256;
-  if (gx > cap) gx = cap;          // one persistent workgroup per CU (a multiple of 8: work item w and block b share an XCD)
-  hipLaunchKernelGGL((gemm_nt_p8_kernel<FMH, EPI, KEEPB>), dim3(gx), dim3(512), smem, stream, p);
-  VLB_CHECK_LAUNCH("vlb_gemm_nt_bf16(p8)");
-  return 1;
-}
-
 template <int FMH, bool KEEPB>
-int p8_launch_epi(GemmParams& p, int epi, int group, hipStream_t stream) {
-  switch (epi) {
-    case 0: return p8_launch<FMH, 0, KEEPB>(p, group, stream);
-    case 1: return p8_launch<FMH, 1, KEEPB>(p, group, stream);
-    case 2: return p8_launch<FMH, 2, KEEPB>(p, group, stream);
-    case 3: return p8_launch<FMH, 3, KEEPB>(p, group, stream);
-    case 4: return p8_launch<FMH, 4, KEEPB>(p, group, stream);
-    case 5: return p8_launch<FMH, 5, KEEPB>(p, group, stream);
-    case 6: return p8_launch<FMH, 6, KEEPB>(p, group, stream);
-    case 7: return p8_launch<FMH, 7, KEEPB>(p, group, stream);
-    case 8: return p8_launch<FMH, 8, KEEPB>(p, group, stream);
-    default: return p8_launch<FMH, 10, KEEPB>(p, group, stream);
-  }
-}
-
-int env_int(const char* name, int dflt) {
-  const char* v = getenv(name);
-  return v ? atoi(v) : dflt;
+int p8_launch_epi(GemmParams& p, int epi, hipStream_t stream) {
+  const int wgs = vlb_opt(VLB_OPT_P8_WGS);      // one persistent workgroup per CU
+  const int rc = dispatch_epi(epi, std::integer_sequence<int, 0, 1, 2, 3, 4, 5, 6, 7, 8, 10>{}, VLB_ERR_ARG, [&](auto e) {
+    return launch_persistent<gemm_nt_p8_kernel<FMH, decltype(e)::value, KEEPB>>(163840, 512, 64 * FMH, 256, (wgs >= 8 && wgs <= 256) ? (wgs & ~7) : 256,
+                                                                                vlb_opt(VLB_OPT_P8_GROUP), p, 1, stream, "vlb_gemm_nt_bf16(p8)", true);
+  });
+  return rc < 0 ? rc : 1;
 }
 
 inline bool aligned16(const void* q) { return ((uintptr_t)q & 15) == 0; }
 
 }  // namespace
 
-// tuning knobs (environment defaults, run-time override through vlb_gemm_set_option for A/B measurements inside one process)
-// p8_mode: 0 off | 1 cost model (default) | 3 / 4 / 5: force the 192- / 256- / 320-row tile wherever the kernel applies
-// p8_wgs: persistent workgroups per launch (<= 256 = one per CU).  Fewer leave CUs to a kernel running on another stream (the
-// weight-gradient GEMMs of the side stream): an MFMA-bound kernel then fills the HBM-bound epilogue bursts of this one.
-// p8_ablate (tools/p8_check.py ablate; results are WRONG when != 0): 1 no epilogue | 2 epilogue without its global stores | 4 (results
-// correct) per-workgroup clock stamps into the table passed as `pre` (tools/clock_probe.py)
-static int g_opt[8] = {-1, -1, -1, -1, -1, -1, -1, -1};
-static const char* const g_opt_name[8] = {"p8_mode", "p8_keepb", "p8_group", "p8_min_tiles", "p8_wgs", "p8_ablate", "p8_tile192", "p8_drain"};
-static void p8_options_init() {
-  if (g_opt[0] >= 0) return;
-  g_opt[0] = env_int("VLB_GEMM_P8", 1);
-  g_opt[1] = env_int("VLB_GEMM_P8_KEEPB", 1);
-  g_opt[2] = env_int("VLB_GEMM_P8_GROUP", 2);
-  g_opt[3] = env_int("VLB_GEMM_P8_MIN_TILES", 160);
-  g_opt[4] = env_int("VLB_GEMM_P8_WGS", 256);
-  g_opt[5] = 0;
-  g_opt[6] = env_int("VLB_GEMM_P8_192", 1);
-  g_opt[7] = env_int("VLB_GEMM_P8_DRAIN", 0);      // 1: vmcnt(0) behind every output tile (round-3 behaviour, A/B)
-}
-
-void vlb_ln_set_fwd_rows(int v);      // layernorm.hip
-void vlb_ln_set_bwd4(int v);
-
-extern "C" int vlb_gemm_set_option(const char* name, int value) {
-  p8_options_init();
-  VLB_CHECK_ARG(name && value >= 0, "vlb_gemm_set_option: null name / negative value");
-  if (!strcmp(name, "tn8_mode")) {
-    vlb_tn8_set_mode(value);
-    return VLB_OK;
-  }
-  if (!strcmp(name, "nt_ring")) {
-    vlb_nt_set_ring(value);
-    return VLB_OK;
-  }
-  if (!strcmp(name, "nt_stagger")) {
-    vlb_nt_set_stagger(value);
-    return VLB_OK;
-  }
-  if (!strcmp(name, "tn8_wgs")) {
-    vlb_tn8_set_wgs(value);
-    return VLB_OK;
-  }
-  if (!strcmp(name, "ln_fwd_rows")) {      // (the LayerNorm kernels' variants ride on the same knob)
-    vlb_ln_set_fwd_rows(value);
-    return VLB_OK;
-  }
-  if (!strcmp(name, "ln_bwd4")) {
-    vlb_ln_set_bwd4(value);
-    return VLB_OK;
-  }
-  if (!strcmp(name, "tn8_uneven")) {
-    vlb_tn8_set_uneven(value);
-    return VLB_OK;
-  }
-  if (!strcmp(name, "tn8_m32")) {          // weight-gradient core: 1 = 32x32x16 matrix instructions, 0 = 16x16x32 (default)
-    vlb_tn8_set_m32(value);
-    return VLB_OK;
-  }
-  if (!strcmp(name, "tn8_ablate")) {       // measurement builds only (-DVLB_TN8_PROBE)
-    vlb_tn8_set_ablate(value);
-    return VLB_OK;
-  }
-  for (int i = 0; i < 8; ++i)
-    if (!strcmp(name, g_opt_name[i])) {
-      g_opt[i] = value;
-      return VLB_OK;
-    }
-  vlb_set_error("vlb_gemm_set_option: unknown option %s", name);
-  return VLB_ERR_ARG;
-}
-
 int vlb_gemm_p8_try(GemmParams& p, hipStream_t stream) {
-  p8_options_init();
-  const int mode = g_opt[0], keepb = g_opt[1], group = g_opt[2], min_tiles = g_opt[3];
-  g_p8_wgs = g_opt[4];
+  const int mode = vlb_opt(VLB_OPT_P8_MODE), min_tiles = vlb_opt(VLB_OPT_P8_MIN_TILES);
   if (!mode || p.out_f32 != 0 || p.c_split_stride != 0) return 0;
   if ((p.K % 128) != 0 || p.k_per_split < p.K) return 0;
   int epi;
@@ -954,13 +843,12 @@ int vlb_gemm_p8_try(GemmParams& p, hipStream_t stream) {
   double best = 1e30;
   if (ok4) { fmh = 4; best = c4; }
   if (ok5 && c5 < 0.97 * best) { fmh = 5; best = c5; }
-  if (ok3 && g_opt[6] && c3 < 0.97 * best) { fmh = 3; best = c3; }
+  if (ok3 && vlb_opt(VLB_OPT_P8_TILE192) && c3 < 0.97 * best) { fmh = 3; best = c3; }
   if (mode == 3 || mode == 4 || mode == 5) fmh = mode;
   if (!fmh) return 0;
-  const int g = group < 1 ? 1 : group;
-  p.ablate = g_opt[5];
-  p.p8_flags = (g_opt[7] & 1) | (env_int("VLB_GEMM_P8_LASTW", 0) ? 2 : 0);      // p8_drain bit 0; VLB_GEMM_P8_LASTW: wave-private drain for last tiles too
-  if (fmh == 3) return p8_launch_epi<3, true>(p, epi, g, stream);
-  if (fmh == 5) return p8_launch_epi<5, false>(p, epi, g, stream);
-  return keepb ? p8_launch_epi<4, true>(p, epi, g, stream) : p8_launch_epi<4, false>(p, epi, g, stream);
+  p.ablate = vlb_opt(VLB_OPT_P8_ABLATE);
+  p.p8_flags = (vlb_opt(VLB_OPT_P8_DRAIN) & 1) | (vlb_opt(VLB_OPT_P8_LASTW) ? 2 : 0);
+  if (fmh == 3) return p8_launch_epi<3, true>(p, epi, stream);
+  if (fmh == 5) return p8_launch_epi<5, false>(p, epi, stream);
+  return vlb_opt(VLB_OPT_P8_KEEPB) ? p8_launch_epi<4, true>(p, epi, stream) : p8_launch_epi<4, false>(p, epi, stream);
 }

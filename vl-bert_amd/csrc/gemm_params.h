@@ -1,5 +1,9 @@
-// Parameter block shared by the GEMM kernels of libvlbert_hip.so (gemm.hip, gemm_p8.hip).
+// Parameter block and host launch helpers shared by the GEMM kernels of libvlbert_hip.so (gemm.hip, gemm_p8.hip, gemm_tn8.hip).
 #pragma once
+#include <utility>
+
+#include "options.h"
+#include "tile_order.h"
 #include "vlb_common.h"
 
 struct GemmParams {
@@ -50,10 +54,38 @@ int vlb_tn8_pick_splits(int Mo, int No, int R);
 int vlb_gemm_tn8_group(int n, const void* const* A, const long* lda, const void* const* B, const long* ldb, float* const* C,
                        const long* ldc, int R, const int* Mo, const int* No, float* const* colsum, float* workspace,
                        long workspace_floats, int accumulate, int* slices, long* ws_off, hipStream_t stream);
-void vlb_nt_set_stagger(int v);
-void vlb_nt_set_ring(int v);
-void vlb_tn8_set_mode(int v);
-void vlb_tn8_set_wgs(int v);
-void vlb_tn8_set_uneven(int v);
-void vlb_tn8_set_m32(int v);
-void vlb_tn8_set_ablate(int v);
+
+// Launch of a PERSISTENT kernel (one GemmParams argument) over bm x bn output tiles: reserves the dynamic LDS once per kernel, fills the
+// tile counts and the tile order's group height, caps the grid at `grid_cap` workgroups (the resident ones; a multiple of 8 so that work
+// item w and block b stay on the same XCD -- tile_order.h) x `splits` K slices.  A failed reservation is an error only where the caller
+// says so (lds_required).
+template <auto KERNEL>
+static int launch_persistent(int smem, int block, int bm, int bn, int grid_cap, int tile_group, GemmParams& p, int splits,
+                             hipStream_t stream, const char* name, bool lds_required = false) {
+  static bool attr_set = false;
+  if (!attr_set) {
+    const hipError_t e = hipFuncSetAttribute((const void*)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, smem);
+    if (e != hipSuccess && lds_required) {
+      vlb_set_error("%s: cannot reserve %d bytes of LDS: %s", name, smem, hipGetErrorString(e));
+      return VLB_ERR_HIP;
+    }
+    attr_set = true;
+  }
+  p.ntm = vlb_cdiv(p.M, bm);
+  p.ntn = vlb_cdiv(p.N, bn);
+  p.tile_group = tile_group < 1 ? 1 : tile_group;
+  int gx = p.ntm * p.ntn;
+  if (gx > grid_cap) gx = grid_cap;
+  hipLaunchKernelGGL(KERNEL, dim3(gx, splits), dim3(block), smem, stream, p);
+  VLB_CHECK_LAUNCH(name);
+  return VLB_OK;
+}
+
+// Run-time epilogue class -> template argument: f(std::integral_constant<int, E>) for the E of the list that equals cls, `other` when
+// the list does not hold it.  The list IS the set of instantiations.
+template <int... E, typename F>
+static int dispatch_epi(int cls, std::integer_sequence<int, E...>, int other, F&& f) {
+  int rc = other;
+  (void)((cls == E && (rc = f(std::integral_constant<int, E>{}), true)) || ...);
+  return rc;
+}

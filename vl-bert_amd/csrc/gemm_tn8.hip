@@ -124,27 +124,21 @@ __global__ __launch_bounds__(512, 2) void gemm_tn8_kernel(const Tn8Group grp, co
 
   // item -> (gradient g, tile origin, K-tile range): per gradient slice-major (all tiles of a slice are concurrent and share their
   // operand rows in L2); inside a slice the tiles are walked in groups of `tile_group` tile rows, column-major inside a group
-  // Work item w (block b takes w = b, b + grid, ...; block b runs on XCD b % 8) -> position t in the item list: every XCD owns a
-  // CONTIGUOUS run of the list, i.e. tiles of the same gradient and K slice that share operand panels in that XCD's L2.  (The plain
-  // w -> t = w order spread neighbouring tiles over all 8 L2s: the profile showed 3.1x the algorithmic bytes on the fabric,
-  // 6.6 TB/s -- the kernel was memory-bound.)
+  // Work item w (block b takes w = b, b + grid, ...) -> position in the item list: every XCD owns a CONTIGUOUS run of the list
+  // (tile_order.h), i.e. tiles of the same gradient and K slice that share operand panels in that XCD's L2.
   const int nlong = grp.nlong;
-  auto xcd_order = [](int w, int n) {      // position of work item w (w & 7 = its XCD) when every XCD owns a contiguous run of n items
-    const int xcd = w & 7, q = n >> 3, r = n & 7;
-    return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (w >> 3);
-  };
   auto item_of = [&](int w, int& gi, int& m0, int& n0, int& kt0, int& nk) {
     int sp, t;
     gi = 0;
     if (nlong > 0 && w >= nlong) {          // a remainder slice (uneven mode): short list, tile-major per gradient
-      const int vs = xcd_order(w - nlong, nitems - nlong);
+      const int vs = vlb_xcd_order(w - nlong, nitems - nlong);
 #pragma unroll
       for (int q = 1; q < TN8_MAX_GROUP; ++q)
         if (q < grp.n && vs >= grp.d[q].short0) gi = q;
       sp = 2;
       t = vs - grp.d[gi].short0;
     } else {
-      w = xcd_order(w, nlong > 0 ? nlong : nitems);
+      w = vlb_xcd_order(w, nlong > 0 ? nlong : nitems);
       if constexpr (TABLE) {
         int lo = 0, hi = grp.n;
         while (hi - lo > 1) {
@@ -163,10 +157,10 @@ __global__ __launch_bounds__(512, 2) void gemm_tn8_kernel(const Tn8Group grp, co
       t = wl - sp * ntile;
     }
     const Tn8Desc d = D(gi);
-    const int gm = d.tile_group, per_group = gm * d.ntn, gid = t / per_group, first = gid * gm;
-    const int gsz = min(d.ntm - first, gm), rem = t - gid * per_group;
-    m0 = (first + rem % gsz) * 256;
-    n0 = (rem / gsz) * 256;
+    int tile_m, tile_n;
+    vlb_tile_of(t, d.ntm, d.ntn, d.tile_group, tile_m, tile_n);
+    m0 = tile_m * 256;
+    n0 = tile_n * 256;
     kt0 = sp * d.kt_per_split;
     nk = min((d.R >> 6) - kt0, d.kt_per_split);       // even, >= 2 (host guarantees)
   };
@@ -497,24 +491,8 @@ __global__ __launch_bounds__(512, 2) void gemm_tn8_kernel(const Tn8Group grp, co
   }
 }
 
-int env_int(const char* name, int dflt) {
-  const char* v = getenv(name);
-  return v ? atoi(v) : dflt;
-}
-
 }  // namespace
 
-static int g_tn8_mode = -1;      // VLB_GEMM_TN8 (0: 128x128 TN kernel only); run-time override: vlb_gemm_set_option("tn8_mode", v)
-void vlb_tn8_set_mode(int v) { g_tn8_mode = v; }
-static int g_tn8_uneven = -1;   // VLB_GEMM_TN8_UNEVEN: 1 = the uneven three-slice cut of grouped launches; 0 (default) equal slices --
-                                 // measured: no gain at batch 256 (21.07 vs 21.02 ms / step), 5-10 % slower launches at batch 64 / 32
-static int g_tn8_wgs = -1;       // VLB_GEMM_TN8_WGS: persistent workgroups per launch (default 256 = one per CU)
-void vlb_tn8_set_wgs(int v) { g_tn8_wgs = v; }
-void vlb_tn8_set_uneven(int v) { g_tn8_uneven = v; }
-static int g_tn8_m32 = -1;       // VLB_GEMM_TN8_M32: 1 = v_mfma_f32_32x32x16 form of the quadrant products, 0 (default) 16x16x32 (run-time: "tn8_m32")
-void vlb_tn8_set_m32(int v) { g_tn8_m32 = v; }
-static int g_tn8_ablate = 0;     // measurement builds (-DVLB_TN8_PROBE) only: see the kernel's ABL parameter
-void vlb_tn8_set_ablate(int v) { g_tn8_ablate = v; }
 static unsigned long long* g_tn8_stamps = nullptr;      // tools/tn8_probe.py: 4 x uint64 per workgroup, or null
 extern "C" int vlb_tn8_set_stamps(void* dev) {
   g_tn8_stamps = (unsigned long long*)dev;
@@ -541,14 +519,8 @@ int vlb_tn8_pick_splits(int Mo, int No, int R) {
 }
 
 static int tile_group_for(int ntm, int ntn) {
-  static const int group = env_int("VLB_GEMM_TN8_GROUP", 0);
-  int gm = group;
-  if (gm <= 0) {
-    gm = 1;
-    if (2 * ntn >= ntm) gm = (int)(sqrt((double)ntm * ntn / 8.0) + 0.5);
-  }
-  if (gm > ntm) gm = ntm;
-  return gm < 1 ? 1 : gm;
+  const int group = vlb_opt(VLB_OPT_TN8_GROUP);
+  return group > 0 ? (group < ntm ? group : ntm) : vlb_square_tile_group(ntm, ntn);
 }
 
 template <bool TABLE, bool M32, int ABL>
@@ -570,22 +542,21 @@ static int tn8_launch_k(Tn8Group& grp, const Tn8Desc* tab, int gx, hipStream_t s
 
 template <bool TABLE>
 static int tn8_launch_t(Tn8Group& grp, const Tn8Desc* tab, hipStream_t stream) {
-  if (g_tn8_wgs < 0) g_tn8_wgs = env_int("VLB_GEMM_TN8_WGS", 256);
-  if (g_tn8_m32 < 0) g_tn8_m32 = env_int("VLB_GEMM_TN8_M32", 0);
-  const int cap = (g_tn8_wgs >= 8 && g_tn8_wgs <= 256) ? g_tn8_wgs : 256;
+  const int wgs = vlb_opt(VLB_OPT_TN8_WGS), m32 = vlb_opt(VLB_OPT_TN8_M32);
+  const int cap = (wgs >= 8 && wgs <= 256) ? wgs : 256;
   const int gx = grp.nitems > cap ? cap : grp.nitems;
   grp.stamps = g_tn8_stamps;
 #ifdef VLB_TN8_PROBE
-  if (!TABLE && g_tn8_ablate) {
+  if (const int ablate = vlb_opt(VLB_OPT_TN8_ABLATE); !TABLE && ablate) {
 #define TN8_ABL(M, A) \
-  if ((g_tn8_m32 != 0) == (M != 0) && (g_tn8_ablate & 15) == A) return tn8_launch_k<false, M != 0, A>(grp, tab, gx, stream);
+  if ((m32 != 0) == (M != 0) && (ablate & 15) == A) return tn8_launch_k<false, M != 0, A>(grp, tab, gx, stream);
 #define TN8_ABLS(M) TN8_ABL(M, 1) TN8_ABL(M, 2) TN8_ABL(M, 3) TN8_ABL(M, 4) TN8_ABL(M, 5) TN8_ABL(M, 6) TN8_ABL(M, 8) TN8_ABL(M, 12) TN8_ABL(M, 14)
     TN8_ABLS(0) TN8_ABLS(1)
 #undef TN8_ABLS
 #undef TN8_ABL
   }
 #endif
-  return g_tn8_m32 ? tn8_launch_k<TABLE, true, 0>(grp, tab, gx, stream) : tn8_launch_k<TABLE, false, 0>(grp, tab, gx, stream);
+  return m32 ? tn8_launch_k<TABLE, true, 0>(grp, tab, gx, stream) : tn8_launch_k<TABLE, false, 0>(grp, tab, gx, stream);
 }
 
 static int tn8_launch(Tn8Group& grp, hipStream_t stream) { return tn8_launch_t<false>(grp, nullptr, stream); }
@@ -602,8 +573,7 @@ static bool tn8_shape_ok(long lda, long ldb, long ldc, int R) {
 // p: A = dY [R, Mo], B = X [R, No], M = Mo, N = No, K = R.
 int vlb_gemm_tn8_try(GemmParams& p, float* C, long ldc, float* colsum, float* workspace, long workspace_floats, int accumulate,
                      bool force_slab, hipStream_t stream) {
-  if (g_tn8_mode < 0) g_tn8_mode = env_int("VLB_GEMM_TN8", 1);
-  if (!g_tn8_mode) return 0;
+  if (!vlb_opt(VLB_OPT_TN8_MODE)) return 0;
   const int R = p.K, Mo = p.M, No = p.N;
   if (!tn8_shape_ok(p.lda, p.ldb, ldc, R)) return 0;
   const int ntm = vlb_cdiv(Mo, 256), ntn = vlb_cdiv(No, 256);
@@ -636,8 +606,7 @@ int vlb_gemm_tn8_try(GemmParams& p, float* C, long ldc, float* colsum, float* wo
 int vlb_gemm_tn8_group(int n, const void* const* A, const long* lda, const void* const* B, const long* ldb, float* const* C,
                        const long* ldc, int R, const int* Mo, const int* No, float* const* colsum, float* workspace,
                        long workspace_floats, int accumulate, int* slices, long* ws_off, hipStream_t stream) {
-  if (g_tn8_mode < 0) g_tn8_mode = env_int("VLB_GEMM_TN8", 1);
-  if (!g_tn8_mode || n < 1 || n > TN8_MAX_GROUP) return 0;
+  if (!vlb_opt(VLB_OPT_TN8_MODE) || n < 1 || n > TN8_MAX_GROUP) return 0;
   long tiles = 0;
   for (int i = 0; i < n; ++i) {
     if (!tn8_shape_ok(lda[i], ldb[i], ldc[i], R)) return 0;
@@ -653,12 +622,11 @@ int vlb_gemm_tn8_group(int n, const void* const* A, const long* lda, const void*
   splits = vlb_cdiv(pairs, per);
   // uneven three-way cut (see Tn8Group): two long slices of L pairs per tile, one workgroup each, and a remainder of pairs - 2 L
   // shared by the 256 - 2 T spare workgroups, k = ceil(T / spare) remainders each; L minimises max(L, k x remainder)
-  if (g_tn8_uneven < 0) g_tn8_uneven = env_int("VLB_GEMM_TN8_UNEVEN", 0);
   int nlong = 0;
   long slab_floats = 0;
   for (int i = 0; i < n; ++i) slab_floats += (long)Mo[i] * ((No[i] + 3) / 4 * 4);
-  if (g_tn8_wgs < 0) g_tn8_wgs = env_int("VLB_GEMM_TN8_WGS", 256);
-  if (g_tn8_uneven && splits == 2 && 2 * tiles < 256 && workspace && 3 * slab_floats <= workspace_floats && g_tn8_wgs == 256) {
+  if (vlb_opt(VLB_OPT_TN8_UNEVEN) && splits == 2 && 2 * tiles < 256 && workspace && 3 * slab_floats <= workspace_floats &&
+      vlb_opt(VLB_OPT_TN8_WGS) == 256) {
     const int spare = 256 - 2 * (int)tiles, k = vlb_cdiv((int)tiles, spare);
     const int L = vlb_cdiv(k * pairs, 2 * k + 1), rem = pairs - 2 * L;
     const int makespan = L > k * rem ? L : k * rem;

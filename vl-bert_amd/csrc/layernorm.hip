@@ -8,6 +8,7 @@
 // the pre-LN sum, and it is what backward re-reads (no separate x_hat tensor is stored).
 #include <stdlib.h>
 
+#include "options.h"
 #include "vlb_common.h"
 
 #define LN_MAX_IT 8  // H <= 2048
@@ -503,21 +504,13 @@ __global__ __launch_bounds__(256) void ln_param_finalize_kernel(const float* __r
 
 // rows per wave of the forward: VLB_LN_FWD_ROWS = 1 | 2 | 4 (0 / unset: 2 where at least two full rounds of single-row waves exist);
 // run-time override for A/B measurements and tests: vlb_gemm_set_option("ln_fwd_rows", v) / ("ln_bwd4", v)
-static int g_ln_fwd_rows = -1;
-static int g_ln_bwd4 = -1;      // VLB_LN_BWD4: 1 (default) the 4-column kernel (2: two rows in flight at H = 768 / 1024); 0 the 8-column kernel
-void vlb_ln_set_fwd_rows(int v) { g_ln_fwd_rows = v; }
-void vlb_ln_set_bwd4(int v) { g_ln_bwd4 = v; }
 
 extern "C" int vlb_layernorm_fwd(const void* x, long ldx, const float* gamma, const float* beta, void* y, long ldy,
                                  float* stats, int rows, int H, float eps, int x_f16, hipStream_t stream) {
   if (rows <= 0) return VLB_OK;
   VLB_CHECK_ARG(H > 0 && (H % 4) == 0 && H <= 256 * LN_MAX_IT, "vlb_layernorm_fwd: unsupported H=%d", H);
   VLB_CHECK_ARG((ldx % 4) == 0 && (ldy % 4) == 0, "vlb_layernorm_fwd: row strides must be multiples of 4");
-  if (g_ln_fwd_rows < 0) {
-    const char* e = getenv("VLB_LN_FWD_ROWS");
-    g_ln_fwd_rows = e ? atoi(e) : 0;
-  }
-  const int rpw_opt = g_ln_fwd_rows;
+  const int rpw_opt = vlb_opt(VLB_OPT_LN_FWD_ROWS);
   const int rpw = (rpw_opt == 1 || rpw_opt == 2 || rpw_opt == 4) ? rpw_opt : (rows >= 2 * 256 * 32 ? 2 : 1);
 #define LN_FWD_R(NIT, RPW)                                                                                                              \
   hipLaunchKernelGGL((layernorm_fwd_kernel<NIT, RPW>), dim3(vlb_cdiv(rows, 4 * RPW)), dim3(256), 0, stream, (const bf16_t*)x, ldx, gamma, \
@@ -560,7 +553,7 @@ static int ln_bwd_blocks(int rows) {
 }
 
 static void ln_lw(int H, int& LW, int& cpl_log2) {
-  if (g_ln_bwd4) {
+  if (vlb_opt(VLB_OPT_LN_BWD4)) {
     const int nit = vlb_cdiv(H, 256);
     LW = (nit <= 4 ? nit : 8) * 256;
     cpl_log2 = 2;
@@ -581,15 +574,12 @@ static int ln_bwd_impl(const void* dy, long lddy, int dy_f32, const void* x, lon
                 "vlb_layernorm_bwd: row strides must be multiples of 8");
   VLB_CHECK_ARG(!(drop_p > 0.f) || seed, "vlb_layernorm_bwd: dropout needs a device seed pointer");
   VLB_CHECK_ARG((long)rows * H < (1L << 32) || !(drop_p > 0.f), "vlb_layernorm_bwd: dropout index overflow");
-  if (g_ln_bwd4 < 0) {
-    const char* v = getenv("VLB_LN_BWD4");
-    g_ln_bwd4 = v ? atoi(v) : 1;
-  }
+  const int bwd4 = vlb_opt(VLB_OPT_LN_BWD4);
   const int blocks = ln_bwd_blocks(rows);
   float* ws = (workspace && (dgamma || dbeta) && blocks > 32) ? workspace : nullptr;
   const uint32_t thr = vlb_drop_thr(drop_p);
   int LW, cpl_log2;
-  if (g_ln_bwd4) {
+  if (bwd4) {
     const int nit = vlb_cdiv(H, 256);
 #define LN_BWD4(NIT, RIF)                                                                                                      \
   do {                                                                                                                          \
@@ -600,10 +590,10 @@ static int ln_bwd_impl(const void* dy, long lddy, int dy_f32, const void* x, lon
                        (const bf16_t*)x, ldx, stats, gamma, (bf16_t*)dx, lddx, (bf16_t*)dx_drop, lddd, thr, vlb_drop_scale(thr), \
                        seed, tag, dx_acc, ldacc, dgamma, dbeta, ws, rows, H, x_f16);                                             \
   } while (0)
-    // rows in flight per wave: 2 while the kernel stays near 128 VGPRs (4 waves per SIMD); g_ln_bwd4 == 2 forces 2 for H = 768 / 1024
+    // rows in flight per wave: 2 while the kernel stays near 128 VGPRs (4 waves per SIMD); ln_bwd4 == 2 forces 2 for H = 768 / 1024
     if (nit <= 1) LN_BWD4(1, 2); else if (nit == 2) LN_BWD4(2, 2);
-    else if (nit == 3) { if (g_ln_bwd4 == 2) LN_BWD4(3, 2); else LN_BWD4(3, 1); }
-    else if (nit == 4) { if (g_ln_bwd4 == 2) LN_BWD4(4, 2); else LN_BWD4(4, 1); }
+    else if (nit == 3) { if (bwd4 == 2) LN_BWD4(3, 2); else LN_BWD4(3, 1); }
+    else if (nit == 4) { if (bwd4 == 2) LN_BWD4(4, 2); else LN_BWD4(4, 1); }
     else LN_BWD4(8, 1);
 #undef LN_BWD4
   } else {
@@ -686,10 +676,6 @@ extern "C" int vlb_ln_param_finalize_batch(int n, const float* const* ws, const 
   if (n <= 0) return VLB_OK;
   VLB_CHECK_ARG(n <= 32 && ws && nslab && dgamma && dbeta, "vlb_ln_param_finalize_batch: 1..32 entries");
   VLB_CHECK_ARG(H > 0 && (H % 8) == 0 && H <= 2048, "vlb_ln_param_finalize_batch: unsupported H=%d", H);
-  if (g_ln_bwd4 < 0) {
-    const char* v = getenv("VLB_LN_BWD4");
-    g_ln_bwd4 = v ? atoi(v) : 1;
-  }
   LnFinalizeBatch b;
   for (int i = 0; i < n; ++i) {
     VLB_CHECK_ARG(ws[i] && nslab[i] > 0, "vlb_ln_param_finalize_batch: entry %d has no partial vectors", i);
