@@ -14,35 +14,48 @@
 enum { KIND_PAD = 0, KIND_TEXT = 1, KIND_OBJ = 2, KIND_END = 3 };
 
 // ------------------------------------------------------------------------------------------
-// layout: one thread block per sample; a single lane walks the (<= ~1k) mask entries.
+// layout: one wave per sample, lanes over the mask entries in chunks of 64; the slot of a set entry is the running count plus the
+// number of set entries in the lanes below it (ballot + popcount), i.e. the order a serial walk gives.
 //   code[b,s] = kind<<16 | source index (t for text, r for object)
 //   text_rows[b,t] = b*S+t (VisualLinguisticBert.forward :152-154 slices [:, :T]),
 //   obj_rows[b,r]  = row of the r-th object if object_mask[b,r] else -1 (:155-157)
 // ------------------------------------------------------------------------------------------
-__global__ void seq_layout_kernel(const uint8_t* __restrict__ text_mask, const uint8_t* __restrict__ obj_mask, int B, int T, int R,
-                                  int S, int32_t* __restrict__ code, int32_t* __restrict__ text_len, int32_t* __restrict__ nobj,
-                                  int32_t* __restrict__ text_rows, int32_t* __restrict__ obj_rows, float* __restrict__ attn_mask) {
-  const int b = blockIdx.x;
-  if (threadIdx.x != 0) return;
+__global__ __launch_bounds__(64) void seq_layout_kernel(const uint8_t* __restrict__ text_mask, const uint8_t* __restrict__ obj_mask, int B, int T,
+                                                        int R, int S, int32_t* __restrict__ code, int32_t* __restrict__ text_len,
+                                                        int32_t* __restrict__ nobj, int32_t* __restrict__ text_rows,
+                                                        int32_t* __restrict__ obj_rows, float* __restrict__ attn_mask) {
+  const int b = blockIdx.x, lane = threadIdx.x;
+  const unsigned long long below = (1ull << lane) - 1ull;
   int n = 0;
-  for (int t = 0; t < T; ++t)
-    if (text_mask[b * T + t]) code[b * S + n++] = (KIND_TEXT << 16) | t;
+  for (int t0 = 0; t0 < T; t0 += 64) {
+    const int t = t0 + lane;
+    const bool m = t < T && text_mask[b * T + t] != 0;
+    const unsigned long long bal = __ballot(m);
+    if (m) code[b * S + n + __popcll(bal & below)] = (KIND_TEXT << 16) | t;
+    n += __popcll(bal);
+  }
   const int tl = n;
-  for (int r = 0; r < R; ++r) {
-    if (obj_mask[b * R + r]) {
-      obj_rows[b * R + r] = b * S + n;
-      code[b * S + n++] = (KIND_OBJ << 16) | r;
-    } else {
-      obj_rows[b * R + r] = -1;
-    }
+  for (int r0 = 0; r0 < R; r0 += 64) {
+    const int r = r0 + lane;
+    const bool m = r < R && obj_mask[b * R + r] != 0;
+    const unsigned long long bal = __ballot(m);
+    const int s = n + __popcll(bal & below);
+    if (m) code[b * S + s] = (KIND_OBJ << 16) | r;
+    if (r < R) obj_rows[b * R + r] = m ? b * S + s : -1;
+    n += __popcll(bal);
   }
   const int no = n - tl;
-  code[b * S + n++] = (KIND_END << 16);
-  for (int s = n; s < S; ++s) code[b * S + s] = (KIND_PAD << 16);
-  for (int s = 0; s < S; ++s) attn_mask[b * S + s] = (s < n) ? 1.f : 0.f;
-  for (int t = 0; t < T; ++t) text_rows[b * T + t] = b * S + t;
-  text_len[b] = tl;
-  nobj[b] = no;
+  if (lane == 0) code[b * S + n] = (KIND_END << 16);
+  ++n;      // (S >= T + R + 1: the end token always fits)
+  for (int s = lane; s < S; s += 64) {
+    if (s >= n) code[b * S + s] = (KIND_PAD << 16);
+    attn_mask[b * S + s] = (s < n) ? 1.f : 0.f;
+  }
+  for (int t = lane; t < T; t += 64) text_rows[b * T + t] = b * S + t;
+  if (lane == 0) {
+    text_len[b] = tl;
+    nobj[b] = no;
+  }
 }
 
 // ------------------------------------------------------------------------------------------
@@ -50,7 +63,10 @@ __global__ void seq_layout_kernel(const uint8_t* __restrict__ text_mask, const u
 // (common/fast_rcnn.py:165-175 + common/utils/bbox.py:33-65); mvrc_ops==1 rows take
 // object_mask_visual_embedding instead of the precomputed feature
 // (resnet_vlbert_for_pretraining.py:114-117); hard-coded Dropout(p) of obj_downsample.
-// One 256-thread block per region: 8 coord + 8 feature elements per thread, 16/32-B accesses.
+// One 256-thread block per region.  The 256 frequencies 1000^(j/256) are computed once per block into LDS.  Coordinate half: wave
+// `which` owns coordinate `which`, its lane l the four frequencies 4l..4l+3 -- one angle per frequency feeds both the sine slot (j)
+// and the cosine slot (j + 256).  A lane pair then swaps halves (even lane: the 8 sines of frequencies 8p..8p+7, odd lane: their 8
+// cosines) so that every lane stores 16 bytes.  Feature half: 8 elements per thread, 32-B loads, 16-B stores.
 // ------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void obj_prep_fwd_kernel(const float* __restrict__ boxes, long ldbox, const float* __restrict__ im_info, long ldinfo,
                                                            const int64_t* __restrict__ mvrc_ops, const float* __restrict__ mask_emb,
@@ -67,50 +83,64 @@ __global__ __launch_bounds__(256) void obj_prep_fwd_kernel(const float* __restri
     *(uint4*)(o + 2048 + tid * 8) = make_uint4(0, 0, 0, 0);
     return;
   }
+  __shared__ __attribute__((aligned(16))) float freq[256];
+  freq[tid] = powf(1000.0f, (float)tid / 256.0f);
   const float W = im_info[b * ldinfo + 0], Hh = im_info[b * ldinfo + 1];
   const float x1 = bx[0], y1 = bx[1], x2 = bx[2], y2 = bx[3];
-  float pos[4];
-  pos[0] = (x1 + x2) / 2 / W * 100;
-  pos[1] = (y1 + y2) / 2 / Hh * 100;
-  pos[2] = (x2 - x1) / W * 100;
-  pos[3] = (y2 - y1) / Hh * 100;
+  const float pos0 = (x1 + x2) / 2 / W * 100;
+  const float pos1 = (y1 + y2) / 2 / Hh * 100;
+  const float pos2 = (x2 - x1) / W * 100;
+  const float pos3 = (y2 - y1) / Hh * 100;
   const bool masked = mvrc_ops && mvrc_ops[row] == 1;
   const float* feat = masked ? mask_emb : (bx + 4);
-  // thread t owns elements [4t,4t+4) and [1024+4t, ..+4) of both the coordinate half and the
-  // feature half: every wave-level access is a contiguous 1 KiB (fp32 in) / 512 B (bf16 out) run.
-#pragma unroll
-  for (int part = 0; part < 2; ++part) {
-    const int e0 = part * 1024 + tid * 4;  // element within a 2048-wide half
-    float cv[4], fv[4];
-    {
-      // coordinate half: e -> which = e/512, j = e%512, sin for j<256 else cos, frequency index j%256
-      const int which = e0 >> 9, j0 = e0 & 511;
-      const bool is_cos = j0 >= 256;
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        const float dim = powf(1000.0f, (float)((j0 & 255) + k) / 256.0f);
-        const float a = pos[which] / dim;
-        cv[k] = is_cos ? cosf(a) : sinf(a);
-      }
-      const float4 f = *(const float4*)(feat + e0);
-      fv[0] = f.x; fv[1] = f.y; fv[2] = f.z; fv[3] = f.w;
-    }
+  {
+    // feature half: thread t owns elements [8t, 8t+8)
+    const int e0 = tid * 8;
+    const float4 f0 = *(const float4*)(feat + e0), f1 = *(const float4*)(feat + e0 + 4);
+    float fv[8] = {f0.x, f0.y, f0.z, f0.w, f1.x, f1.y, f1.z, f1.w};
     if (drop_thr) {
-      const uint32_t ic = (uint32_t)row * 4096u + (uint32_t)e0, ifeat = ic + 2048u;
-      const uint32_t h0 = vlb_rng_pair(seed, tag, ic >> 1), h1 = vlb_rng_pair(seed, tag, (ic >> 1) + 1);
-      const uint32_t g0 = vlb_rng_pair(seed, tag, ifeat >> 1), g1 = vlb_rng_pair(seed, tag, (ifeat >> 1) + 1);
-      cv[0] = ((h0 & 0xffffu) >= drop_thr) ? cv[0] * drop_scale : 0.f;
-      cv[1] = ((h0 >> 16) >= drop_thr) ? cv[1] * drop_scale : 0.f;
-      cv[2] = ((h1 & 0xffffu) >= drop_thr) ? cv[2] * drop_scale : 0.f;
-      cv[3] = ((h1 >> 16) >= drop_thr) ? cv[3] * drop_scale : 0.f;
-      fv[0] = ((g0 & 0xffffu) >= drop_thr) ? fv[0] * drop_scale : 0.f;
-      fv[1] = ((g0 >> 16) >= drop_thr) ? fv[1] * drop_scale : 0.f;
-      fv[2] = ((g1 & 0xffffu) >= drop_thr) ? fv[2] * drop_scale : 0.f;
-      fv[3] = ((g1 >> 16) >= drop_thr) ? fv[3] * drop_scale : 0.f;
+      const uint32_t ifeat = (uint32_t)row * 4096u + 2048u + (uint32_t)e0;
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const uint32_t g = vlb_rng_pair(seed, tag, (ifeat >> 1) + q);
+        fv[2 * q] = ((g & 0xffffu) >= drop_thr) ? fv[2 * q] * drop_scale : 0.f;
+        fv[2 * q + 1] = ((g >> 16) >= drop_thr) ? fv[2 * q + 1] * drop_scale : 0.f;
+      }
     }
-    *(uint2*)(o + e0) = make_uint2(pack2bf(cv[0], cv[1]), pack2bf(cv[2], cv[3]));
-    *(uint2*)(o + 2048 + e0) = make_uint2(pack2bf(fv[0], fv[1]), pack2bf(fv[2], fv[3]));
+    *(uint4*)(o + 2048 + e0) = make_uint4(pack2bf(fv[0], fv[1]), pack2bf(fv[2], fv[3]), pack2bf(fv[4], fv[5]), pack2bf(fv[6], fv[7]));
   }
+  __syncthreads();
+  // coordinate half: element e -> which = e/512, j = e%512, sin for j<256 else cos, frequency index j%256
+  const int which = tid >> 6, j0 = (tid & 63) * 4;
+  const float p = which == 0 ? pos0 : (which == 1 ? pos1 : (which == 2 ? pos2 : pos3));
+  const float4 d4 = *(const float4*)(freq + j0);
+  const float dim[4] = {d4.x, d4.y, d4.z, d4.w};
+  float sv[4], cv[4];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const float a = p / dim[k];
+    sv[k] = sinf(a);
+    cv[k] = cosf(a);
+  }
+  if (drop_thr) {
+    const uint32_t is = (uint32_t)row * 4096u + (uint32_t)(which * 512 + j0), ic = is + 256u;
+    const uint32_t h0 = vlb_rng_pair(seed, tag, is >> 1), h1 = vlb_rng_pair(seed, tag, (is >> 1) + 1);
+    const uint32_t g0 = vlb_rng_pair(seed, tag, ic >> 1), g1 = vlb_rng_pair(seed, tag, (ic >> 1) + 1);
+    sv[0] = ((h0 & 0xffffu) >= drop_thr) ? sv[0] * drop_scale : 0.f;
+    sv[1] = ((h0 >> 16) >= drop_thr) ? sv[1] * drop_scale : 0.f;
+    sv[2] = ((h1 & 0xffffu) >= drop_thr) ? sv[2] * drop_scale : 0.f;
+    sv[3] = ((h1 >> 16) >= drop_thr) ? sv[3] * drop_scale : 0.f;
+    cv[0] = ((g0 & 0xffffu) >= drop_thr) ? cv[0] * drop_scale : 0.f;
+    cv[1] = ((g0 >> 16) >= drop_thr) ? cv[1] * drop_scale : 0.f;
+    cv[2] = ((g1 & 0xffffu) >= drop_thr) ? cv[2] * drop_scale : 0.f;
+    cv[3] = ((g1 >> 16) >= drop_thr) ? cv[3] * drop_scale : 0.f;
+  }
+  const uint32_t s01 = pack2bf(sv[0], sv[1]), s23 = pack2bf(sv[2], sv[3]), c01 = pack2bf(cv[0], cv[1]), c23 = pack2bf(cv[2], cv[3]);
+  // lanes 2p / 2p+1 hold frequencies 8p..8p+3 / 8p+4..8p+7: the even lane hands over its cosines and takes the odd lane's sines
+  const bool odd = tid & 1;
+  const uint32_t got0 = __shfl_xor(odd ? s01 : c01, 1, 64), got1 = __shfl_xor(odd ? s23 : c23, 1, 64);
+  const int e = which * 512 + (j0 & ~7) + (odd ? 256 : 0);
+  *(uint4*)(o + e) = odd ? make_uint4(got0, got1, c01, c23) : make_uint4(s01, s23, got0, got1);
 }
 
 // x[r, :] = 0 for the rows of padded boxes (boxes[r*ldbox] <= -1.5): obj_downsample is only applied to valid boxes in the reference and
@@ -133,21 +163,73 @@ extern "C" int vlb_zero_padded_rows_bf16(void* x, long ld, const float* boxes, l
 
 // colsum over rows r with sel[r]==1 of src[r][c] * dropmask(row, col_off + c):  dst[c] += ...
 // (gradient of object_mask_visual_embedding: sum over masked regions of dA[:, 2048:]).
+// A workgroup owns 64 * VEC columns (a lane VEC consecutive ones: 16-byte loads with VEC = 8; VEC = 1 is the scalar form for
+// C % 8 != 0 or rows that are not 16-byte aligned) and its four waves take chunks of 64 rows: every lane reads one sel entry of the
+// chunk, a ballot gives the selected rows as a wave-uniform bit mask, and only those rows are loaded, four at a time.  The lanes
+// accumulate in registers, the waves meet in LDS, and one atomicAdd per column and workgroup goes out.  The workgroups of a column
+// range finish in any order, so -- as with the one-atomic-per-row-group form before it -- the fp32 sums are not bit-reproducible
+// from run to run.
+template <int VEC>
 __global__ __launch_bounds__(256) void masked_colsum_kernel(const bf16_t* __restrict__ src, long lds, const int64_t* __restrict__ sel,
                                                             int rows, int C, float* __restrict__ dst, uint32_t drop_thr,
                                                             float drop_scale, const uint32_t* __restrict__ seedp, uint32_t tag,
                                                             uint32_t row_elems, uint32_t col_off) {
-  const int c = blockIdx.x * 256 + threadIdx.x;
-  if (c >= C) return;
+  __shared__ float part[4][64 * VEC];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int c0 = (blockIdx.x * 64 + lane) * VEC;      // (vector form: C % 8 == 0, so a lane's columns are all inside or all outside)
+  const bool live = c0 < C;
   const uint32_t seed = (drop_thr && seedp) ? *seedp : 0u;
-  float s = 0.f;
-  for (int r = blockIdx.y; r < rows; r += gridDim.y) {
-    if (sel[r] != 1) continue;
-    float v = bf2f(src[(long)r * lds + c]);
-    if (drop_thr) v = vlb_keep(seed, tag, (uint32_t)r * row_elems + col_off + (uint32_t)c, drop_thr) ? v * drop_scale : 0.f;
-    s += v;
+  float s[VEC];
+#pragma unroll
+  for (int k = 0; k < VEC; ++k) s[k] = 0.f;
+  for (int base = (blockIdx.y * 4 + wave) * 64; base < rows; base += 4 * gridDim.y * 64) {
+    const int rl = base + lane;
+    unsigned long long m = __ballot(rl < rows && sel[rl] == 1);
+    while (m) {
+      int r[4];
+      bool ok[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        ok[u] = m != 0;
+        r[u] = base + (ok[u] ? __builtin_ctzll(m) : 0);
+        m &= m - 1;      // (0 stays 0)
+      }
+      [[maybe_unused]] uint4 w[4];
+      [[maybe_unused]] bf16_t w1[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        if (ok[u] && live) {
+          if constexpr (VEC == 8) w[u] = *(const uint4*)(src + (long)r[u] * lds + c0);
+          else w1[u] = src[(long)r[u] * lds + c0];
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        if (ok[u] && live) {
+          float v[VEC];
+          if constexpr (VEC == 8) {
+            v[0] = bflo(w[u].x); v[1] = bfhi(w[u].x); v[2] = bflo(w[u].y); v[3] = bfhi(w[u].y);
+            v[4] = bflo(w[u].z); v[5] = bfhi(w[u].z); v[6] = bflo(w[u].w); v[7] = bfhi(w[u].w);
+          } else {
+            v[0] = bf2f(w1[u]);
+          }
+#pragma unroll
+          for (int k = 0; k < VEC; ++k) {
+            if (drop_thr)
+              v[k] = vlb_keep(seed, tag, (uint32_t)r[u] * row_elems + col_off + (uint32_t)(c0 + k), drop_thr) ? v[k] * drop_scale : 0.f;
+            s[k] += v[k];
+          }
+        }
+      }
+    }
   }
-  atomicAdd(dst + c, s);
+#pragma unroll
+  for (int k = 0; k < VEC; ++k) part[wave][lane * VEC + k] = s[k];
+  __syncthreads();
+  for (int i = threadIdx.x; i < 64 * VEC; i += 256) {
+    const int c = blockIdx.x * 64 * VEC + i;
+    if (c < C) atomicAdd(dst + c, (part[0][i] + part[1][i]) + (part[2][i] + part[3][i]));
+  }
 }
 
 // ------------------------------------------------------------------------------------------
@@ -633,9 +715,13 @@ extern "C" int vlb_masked_colsum(const void* src, long lds_, const int64_t* sel,
                                  const uint32_t* seed, uint32_t tag, uint32_t row_elems, uint32_t col_off, hipStream_t stream) {
   if (rows <= 0 || C <= 0) return VLB_OK;
   const uint32_t thr = vlb_drop_thr(drop_p);
-  int gy = rows < 64 ? rows : 64;
-  hipLaunchKernelGGL(masked_colsum_kernel, dim3(vlb_cdiv(C, 256), gy), dim3(256), 0, stream, (const bf16_t*)src, lds_, sel, rows, C,
-                     dst, thr, vlb_drop_scale(thr), seed, tag, row_elems, col_off);
+  const int chunks4 = vlb_cdiv(vlb_cdiv(rows, 64), 4), gy = chunks4 < 64 ? chunks4 : 64;      // one 64-row chunk per wave up to 16384 rows
+  if ((C % 8) == 0 && (lds_ % 8) == 0 && ((uintptr_t)src % 16) == 0)
+    hipLaunchKernelGGL(masked_colsum_kernel<8>, dim3(vlb_cdiv(C, 512), gy), dim3(256), 0, stream, (const bf16_t*)src, lds_, sel, rows, C,
+                       dst, thr, vlb_drop_scale(thr), seed, tag, row_elems, col_off);
+  else
+    hipLaunchKernelGGL(masked_colsum_kernel<1>, dim3(vlb_cdiv(C, 64), gy), dim3(256), 0, stream, (const bf16_t*)src, lds_, sel, rows, C,
+                       dst, thr, vlb_drop_scale(thr), seed, tag, row_elems, col_off);
   VLB_CHECK_LAUNCH("vlb_masked_colsum");
   return VLB_OK;
 }

@@ -481,14 +481,28 @@ __global__ __launch_bounds__(256, (NIT * RIF <= 3 ? 4 : 1)) void layernorm_bwd4_
 // produced NaN gradients after other tests had cooled the caches.  That is also why hipcc waits with vmcnt(0) wherever loads and stores are
 // pending together -- it is not being conservative.  DESIGN.md §3, "HBM-bound kernels".)
 
+// element q of the partial vectors r0, r0 + step, ... summed in that order (the order is part of the result: it is kept), with eight
+// loads in flight ahead of the adds
+__device__ __forceinline__ float ln_slab_colsum(const float* __restrict__ ws, int nslab, int LW, int q, int r0, int step) {
+  float s = 0.f;
+  for (int r = r0; r < nslab; r += 8 * step) {
+    float v[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) v[u] = (r + u * step < nslab) ? ws[(long)(r + u * step) * 2 * LW + q] : 0.f;
+#pragma unroll
+    for (int u = 0; u < 8; ++u)
+      if (r + u * step < nslab) s += v[u];
+  }
+  return s;
+}
+
 // dgamma/dbeta += column sums of the `nslab` lane-major partial vectors [2][LW]: grid (2 LW / 64, 8)
 __global__ __launch_bounds__(256) void ln_param_finalize_kernel(const float* __restrict__ ws, int nslab, int LW, float* __restrict__ dgamma,
                                                                 float* __restrict__ dbeta, int H, int cpl_log2) {
   __shared__ float part[4][64];
   const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
   const int q = blockIdx.x * 64 + tx;
-  float s = 0.f;
-  for (int r = blockIdx.y * 4 + ty; r < nslab; r += 4 * gridDim.y) s += ws[(long)r * 2 * LW + q];
+  float s = ln_slab_colsum(ws, nslab, LW, q, blockIdx.y * 4 + ty, 4 * gridDim.y);
   part[ty][tx] = s;
   __syncthreads();
   if (ty == 0) {
@@ -656,8 +670,7 @@ __global__ __launch_bounds__(256) void ln_param_finalize_batch_kernel(const LnFi
   const int nslab = b.nslab[e];
   const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
   const int q = blockIdx.x * 64 + tx;
-  float s = 0.f;
-  for (int r = blockIdx.y * 4 + ty; r < nslab; r += 4 * gridDim.y) s += ws[(long)r * 2 * LW + q];
+  float s = ln_slab_colsum(ws, nslab, LW, q, blockIdx.y * 4 + ty, 4 * gridDim.y);
   part[ty][tx] = s;
   __syncthreads();
   if (ty == 0) {

@@ -126,62 +126,74 @@ __global__ __launch_bounds__(256) void ce_fwd_bwd_kernel(bf16_t* __restrict__ lo
 //   counts[0] = labelled rows among positions [0, n_split) (image-caption samples), counts[1] = among [n_split, n) (text-only
 //   auxiliary samples of the multitask wrapper); *overflow |= (count > cap): the rows that did not fit are NOT trained on, so the
 //   host treats the flag as an error (engine.loss_values) -- capacity is a contract with the data pipeline (masking probability).
-// One 1024-thread block: every thread owns a contiguous run of positions, block scan of the run counts.
+// One 1024-thread block walks the positions in tiles of 16384: wave w owns the 16 consecutive 64-position chunks 16 w .. 16 w + 15 of
+// the tile, reads each with one coalesced load (all 16 in flight) and keeps the labels in registers -- they are read once.  A ballot
+// per chunk gives the labelled positions as a bit mask; the slot of a position is (rows of the tiles before) + (rows of the waves
+// below, from 16 wave totals in LDS) + (rows of the wave's chunks before, a running popcount) + (set bits below the lane).
 // ------------------------------------------------------------------------------------------------------------------
+#define MLM_TILE_CHUNKS 16      // chunks per wave and tile
 __global__ __launch_bounds__(1024) void mlm_compact_kernel(const int64_t* __restrict__ labels, const int32_t* __restrict__ src_rows, int n,
                                                            int n_split, int V, int cap, int32_t* __restrict__ sel_pos,
                                                            int32_t* __restrict__ sel_src, int64_t* __restrict__ labels_c,
                                                            float* __restrict__ count0, float* __restrict__ count1,
                                                            int32_t* __restrict__ overflow) {
-  __shared__ int wsum[16];
-  __shared__ int total_s, n0_s;
+  __shared__ int wsum[16], wsum0[16];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int per = (n + 1023) / 1024, lo = tid * per, hi = min(n, lo + per);
-  int c = 0, c0 = 0;
-  for (int i = lo; i < hi; ++i) {
-    const bool lab = labels[i] >= 0 && labels[i] < V;
-    c += lab;
-    c0 += lab && i < n_split;
-  }
-  // inclusive scan of c across the block
-  int incl = c;
+  const unsigned long long below = (1ull << lane) - 1ull;
+  int total = 0, n0 = 0;      // labelled positions so far: all, and those in front of n_split
+  for (int tile0 = 0; tile0 < n; tile0 += 1024 * MLM_TILE_CHUNKS) {
+    const int first = tile0 + wave * MLM_TILE_CHUNKS * 64;      // the wave's first position (may lie beyond n)
+    int lab[MLM_TILE_CHUNKS];                                    // a kept label is in [0, V): 32 bits hold it
+    unsigned long long bal[MLM_TILE_CHUNKS];
+    int wtot = 0, wtot0 = 0;
 #pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int t = __shfl_up(incl, o, 64);
-    if (lane >= o) incl += t;
-  }
-  if (lane == 63) wsum[wave] = incl;
-  const float f0 = wave_sum((float)c0);
-  __syncthreads();
-  if (tid == 0) {
-    int run = 0;
-    for (int w = 0; w < 16; ++w) { const int t = wsum[w]; wsum[w] = run; run += t; }
-    total_s = run;
-    n0_s = 0;
-  }
-  __syncthreads();
-  if (lane == 0 && f0 != 0.f) atomicAdd(&n0_s, (int)f0);
-  __syncthreads();
-  int k = wsum[wave] + incl - c;      // exclusive prefix of this thread's run
-  for (int i = lo; i < hi; ++i) {
-    const long lb = labels[i];
-    if (lb >= 0 && lb < V) {
-      if (k < cap) {
-        sel_pos[k] = i;
-        sel_src[k] = src_rows[i];
-        labels_c[k] = lb;
+    for (int i = 0; i < MLM_TILE_CHUNKS; ++i) {
+      const int idx = first + i * 64 + lane;
+      const int64_t l = (idx < n) ? labels[idx] : (int64_t)-1;
+      lab[i] = (int)l;
+      bal[i] = __ballot(l >= 0 && l < V);
+    }
+#pragma unroll
+    for (int i = 0; i < MLM_TILE_CHUNKS; ++i) {
+      const int d = n_split - (first + i * 64);                  // positions of the chunk in front of the split
+      const unsigned long long front = d <= 0 ? 0ull : (d >= 64 ? ~0ull : (1ull << d) - 1ull);
+      wtot += __popcll(bal[i]);
+      wtot0 += __popcll(bal[i] & front);
+    }
+    __syncthreads();      // (the previous tile's totals have been read)
+    if (lane == 0) {
+      wsum[wave] = wtot;
+      wsum0[wave] = wtot0;
+    }
+    __syncthreads();
+    int k = total;
+#pragma unroll
+    for (int w = 0; w < 16; ++w) {
+      if (w < wave) k += wsum[w];
+      total += wsum[w];
+      n0 += wsum0[w];
+    }
+#pragma unroll
+    for (int i = 0; i < MLM_TILE_CHUNKS; ++i) {
+      if ((bal[i] >> lane) & 1ull) {
+        const int kk = k + __popcll(bal[i] & below), idx = first + i * 64 + lane;
+        if (kk < cap) {
+          sel_pos[kk] = idx;
+          sel_src[kk] = src_rows[idx];
+          labels_c[kk] = (int64_t)lab[i];
+        }
       }
-      ++k;
+      k += __popcll(bal[i]);
     }
   }
-  const int total = total_s;
   for (int q = total + tid; q < cap; q += 1024) {   // padding behind the labelled rows
     sel_pos[q] = -1;
     sel_src[q] = -1;
     labels_c[q] = -1;
   }
   if (tid == 0) {
-    const int kept = min(total, cap), n0 = min(n0_s, kept);
+    const int kept = min(total, cap);
+    n0 = min(n0, kept);
     *count0 = (float)n0;
     *count1 = (float)(kept - n0);
     if (total > cap) *overflow = 1;
@@ -216,8 +228,17 @@ __global__ __launch_bounds__(256) void soft_valid_kernel(const float* __restrict
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
   if (row >= rows) return;
   const float* t = target + (long)row * ldt;
+  // a lane adds its columns lane, lane + 64, ... in ascending order (the sum decides validity: keep that order), eight loads in
+  // flight ahead of the adds
   float s = 0.f;
-  for (int c = lane; c < C; c += 64) s += t[c];
+  for (int c = lane; c < C; c += 512) {
+    float v[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) v[u] = (c + 64 * u < C) ? t[c + 64 * u] : 0.f;
+#pragma unroll
+    for (int u = 0; u < 8; ++u)
+      if (c + 64 * u < C) s += v[u];
+  }
   s = wave_sum(s);
   if (lane == 0) {
     tsum[row] = s;

@@ -398,6 +398,9 @@ class PretrainEngine:
         self.side = torch.cuda.Stream(device=d) if (d.type == "cuda" and os.environ.get("VLB_WGRAD_STREAM", "1") != "0") else None
         self.wg_ws_main = zf(max(need_dec, 4)) if self.side is not None else self.wg_ws    # decoder dgrad split-K (main stream)
         self._hazards = SideStreams()
+        # VLB_FRONT_JOIN=1: the front of the backward waits for the whole side stream instead of for the launches that wrote the
+        # gradients it adds into (A/B runs)
+        self._front_join = os.environ.get("VLB_FRONT_JOIN", "0") != "0"
         self.ln_ws = zf(ops.ln_bwd_workspace_floats(H))     # per-workgroup partial dgamma/dbeta sums of the LayerNorm backward
         # The encoder's LayerNorm backwards (2 per layer + the MLM head's) leave their partial sums in a workspace slice of their
         # own; one batched launch (ops.ln_param_finalize_batch) adds them into the gradients when those are next needed -- a
@@ -792,7 +795,7 @@ class PretrainEngine:
     # ------------------------------------------------------------------------------------------
     def _on_side(self, launch, items):
         """launch() on the side stream (inline without one); whoever overwrites a gradient operand `dy` of `items` next waits for it."""
-        self._hazards.run(self.side, launch, [dy for dy, _, _, _ in items])
+        self._hazards.run(self.side, launch, [dy for dy, _, _, _ in items], writes=[g for _, _, gw, gb in items for g in (gw, gb)])
 
     def _wgrad(self, dy, x, gw, gb):
         """gw[N,K] (+)= dy^T x ; gb[N] += colsum(dy), straight from the row-major operands (LDS transpose reads), bias gradient fused."""
@@ -974,7 +977,13 @@ class PretrainEngine:
                 if on_layer_done and (will_launch is None or will_launch(lf)):
                     self._join_side()       # the bucket's weight gradients must be complete before its all-reduce reads them
                     on_layer_done(lf)
-        self._join_side()               # embed_bwd adds into the word-embedding gradient the decoder wgrad wrote
+        # embed_bwd adds into the word-embedding gradient the decoder weight-gradient launch wrote: the front waits for the side
+        # launches that wrote one of ITS gradient tensors, not for the encoder's last weight-gradient launch, which it runs beside.
+        # With a bucket hook the exchange reads whole buckets behind the front: everything on the side stream completes first.
+        if on_layer_done or self._front_join:
+            self._join_side()
+        else:
+            self._hazards.before_accumulate(*self._front_grads())
         if self.core:
             self._front_core_bwd(dx, p_h)
         else:
@@ -985,6 +994,18 @@ class PretrainEngine:
         if on_layer_done:
             on_layer_done("embed")
             on_layer_done("vision")
+
+    FRONT_GRADS = ("vlbert.word_embeddings.weight", "vlbert.position_embeddings.weight", "vlbert.token_type_embeddings.weight",
+                   "vlbert.end_embedding.weight", "vlbert.embedding_LayerNorm.weight", "vlbert.embedding_LayerNorm.bias",
+                   "vlbert.visual_ln_text.weight", "vlbert.visual_ln_text.bias", "vlbert.visual_ln_object.weight",
+                   "vlbert.visual_ln_object.bias", "object_linguistic_embeddings.weight", "object_mask_word_embedding.weight",
+                   "aux_text_visual_embedding.weight", "object_mask_visual_embedding.weight", "image_feature_extractor.obj_downsample.1.weight",
+                   "image_feature_extractor.obj_downsample.1.bias")
+
+    def _front_grads(self):
+        """Every gradient tensor _front_core_bwd / _front_pretrain_bwd add into or overwrite on the main stream (or hand to a side
+        launch of their own)."""
+        return [self.g32[n] for n in self.FRONT_GRADS if n in self.g32]
 
     def _front_core_bwd(self, dx, p_h):
         cfg, T, R, S, Bt = self.cfg, self.T, self.R, self.S, self.Bt
