@@ -361,6 +361,60 @@ int vlb_sgd_momentum_step(float* p, const float* g, float* momentum_buf, void* p
  * 1 = WarmupConstantSchedule, 2 = WarmupLinearSchedule (common/nlp/bert/optimization.py:27-62).  Call before
  * vlb_adamw_step; graph-replayable (no host value changes between steps). */
 int vlb_lr_schedule_step(float* state, int kind, float base_lr, float warmup_steps, float t_total, vlb_stream_t stream);
+
+/* ---- dynamic loss scaling of the fp16 build (Apex FP16_Optimizer(dynamic_loss_scale=True), the reference's
+ *      TRAIN.FP16_LOSS_SCALE: 'dynamic') -- skip decision, scale, unscale and schedule counter on the device ----------------------
+ * scaler: DEVICE float[VLB_SCALER_FLOATS] next to `state`; the counters are integers held as fp32 (exact up to 2^24):
+ *   [0] scale   [1] growth_factor   [2] backoff_factor   [3] growth_interval   [4] unskipped (clean steps since the last change)
+ *   [5] skipped_total   [6] skipped_in_a_row   [7] min_scale   [8] max_scale
+ * The rule is Apex LossScaler.update_scale, evaluated once per optimizer step after the update:
+ *   overflow:   scale = max(min_scale, scale * backoff_factor); unskipped = 0; skipped_total += 1; skipped_in_a_row += 1;
+ *               the update is skipped: p, m, v, the 16-bit copy and state[5] (step) are not touched;
+ *   otherwise:  unskipped += 1; skipped_in_a_row = 0; if unskipped == growth_interval: scale = min(max_scale, scale * growth_factor),
+ *               unskipped = 0.
+ * Overflow = the squared gradient norm state[7] (`sumsq`; the all-reduced one under data parallelism) is not finite -- the sum the
+ * clip computes anyway, so no further pass over the gradient.  A finite gradient whose fp32 sum of squares overflows is skipped as
+ * well: conservative and harmless (the scale halves and the step is retried on the next batch).
+ * Defaults are Apex's (scale 2^16, factors 2 / 0.5, interval 2000, max 2^24).  Two deviations: min_scale defaults to 1 (Apex has no
+ * floor), and a step is one OPTIMIZER step on the accumulated gradient (Apex checks every micro-batch under accumulation).
+ * The *_scaled steps read the gradient as loss-scaled: coef = grad_scale * (1 / scale) (one division), the clip norm from the same
+ * unscaled value -- at scale S the bits of the plain entry point called with grad_scale / S when S is a power of two.
+ * vlb_adamw_step_ranges_scaled on a skipped step still writes p_bf16_compact = cast(unchanged p): the weight all-gather reads that
+ * image, and before the first step that is really taken nothing else has filled it.
+ * update_scaler = 0: the rule is not applied (all but the last of several flat runs that share one scaler); the step count and sumsq
+ * are handled either way.  vlb_sgd_momentum_step_scaled needs `sumsq` (it carries the decision) and leaves it to the caller.
+ * vlb_lr_schedule_step_scaled: lambda(step + skipped_total + 1) -- the reference's scheduler steps on every iteration
+ * (common/trainer.py:131-136) while a skipped optimizer.step() leaves Adam's state['step'] alone. */
+#define VLB_SCALER_FLOATS 9
+#define VLB_SCALER_SCALE 0
+#define VLB_SCALER_GROWTH_FACTOR 1
+#define VLB_SCALER_BACKOFF_FACTOR 2
+#define VLB_SCALER_GROWTH_INTERVAL 3
+#define VLB_SCALER_UNSKIPPED 4
+#define VLB_SCALER_SKIPPED_TOTAL 5
+#define VLB_SCALER_SKIPPED_IN_A_ROW 6
+#define VLB_SCALER_MIN_SCALE 7
+#define VLB_SCALER_MAX_SCALE 8
+int vlb_adamw_step_scaled(float* p, const void* g, int g_is_bf16, float* m, float* v, void* p_bf16, long n, float* state, float* scaler,
+                          int update_scaler, float grad_scale, vlb_stream_t stream);
+int vlb_adamw_step_ranges_scaled(float* p, const void* g, int g_is_bf16, float* m, float* v, void* p_bf16_compact, const int64_t* ranges,
+                                 const int32_t* block_start, int n, int total_blocks, int chunk, float* state, float* scaler,
+                                 float grad_scale, vlb_stream_t stream);
+int vlb_sgd_momentum_step_scaled(float* p, const float* g, float* momentum_buf, void* p_bf16, long n, float lr, float momentum,
+                                 float weight_decay, const float* sumsq, float max_norm, float grad_scale, float* scaler, int update_scaler,
+                                 vlb_stream_t stream);
+int vlb_lr_schedule_step_scaled(float* state, const float* scaler, int kind, float base_lr, float warmup_steps, float t_total,
+                                vlb_stream_t stream);
+/* the loss kernels with the gradient scale gscale * *dscale (dscale: DEVICE float, e.g. &scaler[0]; NULL = the plain form): the product
+ * is formed once per block and used where gscale is, so a launch at *dscale = S gives the bits of the plain launch given gscale * S */
+int vlb_ce_fwd_bwd_ds(void* logits, long ld, int rows, int V, const int64_t* labels, float* counts, float gscale, const float* dscale,
+                      float* loss_out, void* logits_copy, long ldcopy, vlb_stream_t stream);
+int vlb_ce_fwd_bwd_compact_ds(void* logits, long ld, int rows, int V, const int64_t* labels_c, const float* count0, const float* count1,
+                              float gscale, const float* dscale, float* loss_out0, float* loss_out1, vlb_stream_t stream);
+int vlb_soft_ce_fwd_bwd_ds(void* logits, long ld, int rows, int C, const float* target, long ldt, float* tsum, float* counts, float gscale,
+                           const float* dscale, float* loss_out, void* logits_copy, long ldcopy, vlb_stream_t stream);
+int vlb_bce_logits_fwd_bwd_ds(void* logits, long ld, int rows, int A, const float* label, long ldl, float gscale, const float* dscale,
+                              float pos_weight, float* loss_out, void* logits_copy, long ldcopy, vlb_stream_t stream);
 int vlb_cast_f32_bf16(const float* in, void* out, long n, vlb_stream_t stream);
 int vlb_cast_bf16_f32(const void* in, float* out, long n, vlb_stream_t stream);
 int vlb_rng_advance(uint32_t* seed, vlb_stream_t stream);

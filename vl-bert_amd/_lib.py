@@ -82,6 +82,15 @@ _SIGS = {
     "vlb_sumsq_ranges_det": "pippiiipips",
     "vlb_adamw_step_ranges": "ppipppppiiipfs",
     "vlb_lr_schedule_step": "pifffs",
+    # dynamic loss scaling (device-resident scaler state, include/vlbert_hip.h)
+    "vlb_adamw_step_scaled": "ppippplppifs",
+    "vlb_adamw_step_ranges_scaled": "ppipppppiiippfs",
+    "vlb_sgd_momentum_step_scaled": "pppplfffpffpis",
+    "vlb_lr_schedule_step_scaled": "ppifffs",
+    "vlb_ce_fwd_bwd_ds": "pliippfpppls",
+    "vlb_ce_fwd_bwd_compact_ds": "pliipppfppps",
+    "vlb_soft_ce_fwd_bwd_ds": "pliiplppfpppls",
+    "vlb_bce_logits_fwd_bwd_ds": "pliiplfpfppls",
     "vlb_conv_weight_prepare": "pppppfppppiiiis",
     "vlb_conv_weight_prepare_batched": "ppiifs",
     "vlb_conv_wgrad_finalize": "pppiiiis",

@@ -21,6 +21,8 @@ from collections import OrderedDict
 
 import torch
 
+from ..loss_scale import put_in_checkpoint, values_from_checkpoint
+
 
 _RESNET_BLOCKS = {18: None, 34: None, 50: (3, 4, 6, 3), 101: (3, 4, 23, 3), 152: (3, 8, 36, 3)}
 
@@ -209,9 +211,12 @@ def save_checkpoint(eng, prefix, epoch, rank=0, extra=None):
     """`Checkpoint(prefix, frequent)(epoch, net, optimizer, ...)`: writes `{prefix}-{epoch:04d}.model` on rank 0.  Call on EVERY rank."""
     sd = eng.state_dict()                 # (gathers the master slices first with the sharded optimizer)
     osd = optimizer_state_dict(eng)
+    scaler = getattr(eng, "scaler", None)
     path = checkpoint_path(prefix, epoch)
     if rank == 0:
         ck = OrderedDict(state_dict=OrderedDict((k, t.detach().cpu()) for k, t in sd.items()), optimizer=osd)
+        # dynamic loss scale: its state under a top-level key of its own (the reference's loader reads the two keys above only)
+        put_in_checkpoint(ck, scaler.values() if scaler is not None else None)
         if extra:
             ck.update(extra)
         d = os.path.dirname(os.path.abspath(path))
@@ -230,6 +235,9 @@ def load_checkpoint(eng, path, with_optimizer=True):
     eng.load_state_dict({k: t.to(eng.dev) for k, t in sd.items()})
     if with_optimizer and "optimizer" in ck:
         load_optimizer_state_dict(eng, ck["optimizer"])
+    scaler = getattr(eng, "scaler", None)
+    if scaler is not None:      # restored when the file carries it, else (a checkpoint of a static or of the reference's run) the initial state
+        scaler.load_values(values_from_checkpoint(ck if with_optimizer else None, scaler.spec))
     eng.sync_weights()
     return ck
 

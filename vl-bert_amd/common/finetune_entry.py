@@ -150,7 +150,8 @@ def resolve(task, config, world, args):
     return dict(task=task, module=config.MODULE, per_gpu_batch=B, accumulate=accum, world=world, lr=float(tr.LR) * world * B * accum,
                 optimizer=tr.OPTIMIZER, momentum=float(tr.MOMENTUM), weight_decay=float(tr.WD), clip_grad_norm=float(tr.CLIP_GRAD_NORM),
                 lr_schedule=tr.LR_SCHEDULE, warmup_steps=int(tr.WARMUP_STEPS) if tr.WARMUP else 0, compute=compute,
-                loss_scale=float(tr.FP16_LOSS_SCALE) if isinstance(tr.FP16_LOSS_SCALE, (int, float)) else 128.0,
+                loss_scale=(float(tr.FP16_LOSS_SCALE) if isinstance(tr.FP16_LOSS_SCALE, (int, float)) else
+                            "dynamic" if str(tr.FP16_LOSS_SCALE).strip().lower() == "dynamic" else 128.0),
                 precomputed=bool(config.NETWORK.IMAGE_FEAT_PRECOMPUTED), seed=int(config.RNG_SEED))
 
 
@@ -240,13 +241,18 @@ def main(task, argv=None):
     net.train()
     if world > 1:
         net = importlib.import_module(pkg + ".parallel").DistributedDataParallel(net)
+    # FP16_LOSS_SCALE: 'dynamic' (fp16 only, like the static value): a device-resident scaler shared by the loss and the optimizer
+    scaler = None
+    if r["compute"] == "fp16" and r["loss_scale"] == "dynamic":
+        LS = importlib.import_module(pkg + ".loss_scale")
+        scaler = LS.LossScaler(LS.DynamicLossScale(), dev)
     if r["optimizer"] == "AdamW":
-        opt = OPT.FusedAdamW(net.parameters(), lr=r["lr"], betas=(0.9, 0.999), eps=1e-6, weight_decay=r["weight_decay"])
+        opt = OPT.FusedAdamW(net.parameters(), lr=r["lr"], betas=(0.9, 0.999), eps=1e-6, weight_decay=r["weight_decay"], loss_scaler=scaler)
     else:
-        opt = OPT.FusedSGD(net.parameters(), lr=r["lr"], momentum=r["momentum"], weight_decay=r["weight_decay"])
+        opt = OPT.FusedSGD(net.parameters(), lr=r["lr"], momentum=r["momentum"], weight_decay=r["weight_decay"], loss_scaler=scaler)
     f = lr_lambda(config, args.steps_per_epoch)
     B, accum = r["per_gpu_batch"], r["accumulate"]
-    scale = r["loss_scale"] if r["compute"] == "fp16" else 1.0
+    scale = r["loss_scale"] if (r["compute"] == "fp16" and scaler is None) else 1.0
     Hi, Wi = int(config.SCALES[0]), int(config.SCALES[1])
 
     def batch(i):
@@ -259,7 +265,8 @@ def main(task, argv=None):
     if rank == 0:
         print("%s/train_end2end: %s | %d GPU(s) x batch %d x accumulate %d | %s lr %.3e wd %.1e clip %.1f | schedule %s warmup %d | compute %s" %
               (task, config.MODULE, world, B, accum, r["optimizer"], r["lr"], r["weight_decay"], r["clip_grad_norm"], r["lr_schedule"],
-               r["warmup_steps"], r["compute"]), flush=True)
+               r["warmup_steps"], r["compute"] + (" (loss scale dynamic (%s))" % scaler.spec.describe() if scaler is not None else "")),
+              flush=True)
     # validation at the epoch ends ({vqa,vcr,refcoco}/function/train.py: val_metrics_list + ValidationMonitor + Checkpoint)
     monitor, prefix, epoch_files = None, config.get("MODEL_PREFIX", "") or ("vl-bert_" + task), 0
     if args.val_steps > 0:
@@ -303,7 +310,10 @@ def main(task, argv=None):
             else:
                 image, boxes, masks, question, answers, label, im_info = b
                 outputs, loss = net(image, boxes, masks, question, None, answers, None, label, im_info)
-            (loss * (scale / accum)).backward()
+            if scaler is not None:      # the upstream gradient is the device scale: no host value of it exists
+                (loss * (scaler.scale.reshape(()) * (1.0 / accum))).backward()
+            else:
+                (loss * (scale / accum)).backward()
             last = loss.detach()
         if r["clip_grad_norm"] > 0:
             OPT.clip_grad_norm_(net.parameters(), r["clip_grad_norm"], opt, grad_scale=(1.0 / scale) if scale != 1.0 else None)
@@ -311,8 +321,11 @@ def main(task, argv=None):
             opt.grad_scale = 1.0 / scale
         opt.step()
         if rank == 0 and ((step + 1) % max(1, min(int(config.LOG_FREQUENT), args.steps)) == 0 or step + 1 == args.steps):
-            print("step %d  lr %.3e  loss %.4f  %.1f samples/s" % (step + 1, opt.param_groups[0]["lr"], float(last),
-                                                                   (step + 1) * B * accum * world / (time.time() - t0)), flush=True)
+            ss = scaler.read() if scaler is not None else None      # (float(last) below synchronises anyway)
+            print("step %d  lr %.3e  loss %.4f  %.1f samples/s%s" % (step + 1, opt.param_groups[0]["lr"], float(last),
+                                                                     (step + 1) * B * accum * world / (time.time() - t0),
+                                                                     "  loss scale %g (%d skipped)" % (ss["scale"], ss["skipped_total"])
+                                                                     if ss is not None else ""), flush=True)
         if monitor is not None and (step + 1) % max(1, args.steps_per_epoch) == 0:
             epoch_files += epoch_end((step + 1) // max(1, args.steps_per_epoch) - 1)
     if args.model_dir and rank == 0 and not epoch_files:      # (with epoch checkpoints written, {prefix}-0000.model is epoch 0's: kept)

@@ -58,10 +58,16 @@ __global__ void count_labels_kernel(const int64_t* __restrict__ labels, int n, f
 // out: loss_sum += row_loss / n_valid ;  logits <- dlogits * (gscale / n_valid).
 // Two-group form (compacted MLM rows of the multitask wrapper): rows [0, *n_valid) belong to group 0 (mean over n_valid ->
 // loss_out), the rows behind them to group 1 (mean over *n_valid2 -> loss_out2); n_valid2 == nullptr: one group.
+// DS (dynamic loss scale): the gradient scale is gscale * *dscale, a device value formed once per block and used exactly where gscale
+// is -- the same bits as a launch given the product from the host, and no second pass over the logits.  The static instantiation
+// never reads the trailing argument.
+template <bool DS = false>
 __global__ __launch_bounds__(256) void ce_fwd_bwd_kernel(bf16_t* __restrict__ logits, long ld, int V, const int64_t* __restrict__ labels,
                                                          const float* __restrict__ n_valid, float gscale, float* __restrict__ loss_out,
                                                          bf16_t* __restrict__ logits_copy, long ldcopy,
-                                                         const float* __restrict__ n_valid2 = nullptr, float* __restrict__ loss_out2 = nullptr) {
+                                                         const float* __restrict__ n_valid2 = nullptr, float* __restrict__ loss_out2 = nullptr,
+                                                         const float* __restrict__ dscale = nullptr) {
+  if (DS) gscale = __fmul_rn(gscale, *dscale);
   __shared__ float sh[16];
   const int row = blockIdx.x;
   if (n_valid2 && (float)row >= *n_valid) {
@@ -211,15 +217,31 @@ extern "C" int vlb_mlm_compact(const int64_t* labels, const int32_t* src_rows, i
 }
 
 // CE forward + backward on COMPACTED rows: counts are given (vlb_mlm_compact wrote them), two groups with their own means.
-extern "C" int vlb_ce_fwd_bwd_compact(void* logits, long ld, int rows, int V, const int64_t* labels_c, const float* count0,
-                                      const float* count1, float gscale, float* loss_out0, float* loss_out1, hipStream_t stream) {
+static int ce_fwd_bwd_compact(void* logits, long ld, int rows, int V, const int64_t* labels_c, const float* count0, const float* count1,
+                              float gscale, const float* dscale, float* loss_out0, float* loss_out1, hipStream_t stream) {
   if (rows <= 0) return VLB_OK;
   VLB_CHECK_ARG(logits && labels_c && count0 && count1 && loss_out0 && loss_out1, "vlb_ce_fwd_bwd_compact: null argument");
   VLB_CHECK_ARG(ld >= V && (ld % 8) == 0, "vlb_ce_fwd_bwd_compact: ld=%ld must be >= V=%d and a multiple of 8", ld, V);
-  hipLaunchKernelGGL(ce_fwd_bwd_kernel, dim3(rows), dim3(256), 0, stream, (bf16_t*)logits, ld, V, labels_c, count0, gscale, loss_out0,
-                     (bf16_t*)nullptr, 0L, count1, loss_out1);
+  if (dscale)
+    hipLaunchKernelGGL(ce_fwd_bwd_kernel<true>, dim3(rows), dim3(256), 0, stream, (bf16_t*)logits, ld, V, labels_c, count0, gscale, loss_out0,
+                       (bf16_t*)nullptr, 0L, count1, loss_out1, dscale);
+  else
+    hipLaunchKernelGGL(ce_fwd_bwd_kernel<false>, dim3(rows), dim3(256), 0, stream, (bf16_t*)logits, ld, V, labels_c, count0, gscale, loss_out0,
+                       (bf16_t*)nullptr, 0L, count1, loss_out1, (const float*)nullptr);
   VLB_CHECK_LAUNCH("vlb_ce_fwd_bwd_compact");
   return VLB_OK;
+}
+
+extern "C" int vlb_ce_fwd_bwd_compact(void* logits, long ld, int rows, int V, const int64_t* labels_c, const float* count0,
+                                      const float* count1, float gscale, float* loss_out0, float* loss_out1, hipStream_t stream) {
+  return ce_fwd_bwd_compact(logits, ld, rows, V, labels_c, count0, count1, gscale, nullptr, loss_out0, loss_out1, stream);
+}
+
+// (the *_ds forms: gscale * *dscale from a device scalar, nullable = the plain form -- the dynamic loss scale of an fp16 run)
+extern "C" int vlb_ce_fwd_bwd_compact_ds(void* logits, long ld, int rows, int V, const int64_t* labels_c, const float* count0,
+                                         const float* count1, float gscale, const float* dscale, float* loss_out0, float* loss_out1,
+                                         hipStream_t stream) {
+  return ce_fwd_bwd_compact(logits, ld, rows, V, labels_c, count0, count1, gscale, dscale, loss_out0, loss_out1, stream);
 }
 
 // row validity for the soft-label loss: valid[r] = |sum_c t[r,c] - 1| < 0.1 ; counts[0] += #valid
@@ -248,11 +270,13 @@ __global__ __launch_bounds__(256) void soft_valid_kernel(const float* __restrict
 
 // One block per row.  logits bf16 [rows, ld] -> in place d(logits); target fp32 [rows, ldt].
 //   loss_row = lse * sum(t) - sum(t * x);  dlogit_c = (softmax_c * sum(t) - t_c) / n_valid
+template <bool DS = false>
 __global__ __launch_bounds__(256) void soft_ce_fwd_bwd_kernel(bf16_t* __restrict__ logits, long ld, int C, const float* __restrict__ target,
                                                               long ldt, const float* __restrict__ tsum, const float* __restrict__ n_valid,
                                                               float gscale, float* __restrict__ loss_out, bf16_t* __restrict__ logits_copy,
-                                                              long ldcopy) {
+                                                              long ldcopy, const float* __restrict__ dscale = nullptr) {
   __shared__ float sh[16];
+  if (DS) gscale = __fmul_rn(gscale, *dscale);
   const int row = blockIdx.x;
   bf16_t* x = logits + (long)row * ld;
   const float* t = target + (long)row * ldt;
@@ -285,32 +309,61 @@ __global__ __launch_bounds__(256) void soft_ce_fwd_bwd_kernel(bf16_t* __restrict
   }
 }
 
-extern "C" int vlb_ce_fwd_bwd(void* logits, long ld, int rows, int V, const int64_t* labels, float* counts, float gscale,
-                              float* loss_out, void* logits_copy, long ldcopy, hipStream_t stream) {
+static int ce_fwd_bwd(void* logits, long ld, int rows, int V, const int64_t* labels, float* counts, float gscale, const float* dscale,
+                      float* loss_out, void* logits_copy, long ldcopy, hipStream_t stream) {
   if (rows <= 0) return VLB_OK;
   VLB_CHECK_ARG(logits && labels && counts && loss_out, "vlb_ce_fwd_bwd: null argument");
   VLB_CHECK_ARG(ld >= V && (ld % 8) == 0, "vlb_ce_fwd_bwd: ld=%ld must be >= V=%d and a multiple of 8", ld, V);
   (void)hipMemsetAsync(counts, 0, sizeof(float), stream);
   hipLaunchKernelGGL(count_labels_kernel, dim3(vlb_cdiv(rows, 256) > 64 ? 64 : vlb_cdiv(rows, 256)), dim3(256), 0, stream, labels, rows,
                      counts);
-  hipLaunchKernelGGL(ce_fwd_bwd_kernel, dim3(rows), dim3(256), 0, stream, (bf16_t*)logits, ld, V, labels, counts, gscale, loss_out,
-                     (bf16_t*)logits_copy, ldcopy);
+  if (dscale)
+    hipLaunchKernelGGL(ce_fwd_bwd_kernel<true>, dim3(rows), dim3(256), 0, stream, (bf16_t*)logits, ld, V, labels, counts, gscale, loss_out,
+                       (bf16_t*)logits_copy, ldcopy, (const float*)nullptr, (float*)nullptr, dscale);
+  else
+    hipLaunchKernelGGL(ce_fwd_bwd_kernel<false>, dim3(rows), dim3(256), 0, stream, (bf16_t*)logits, ld, V, labels, counts, gscale, loss_out,
+                       (bf16_t*)logits_copy, ldcopy, (const float*)nullptr, (float*)nullptr, (const float*)nullptr);
   VLB_CHECK_LAUNCH("vlb_ce_fwd_bwd");
+  return VLB_OK;
+}
+
+extern "C" int vlb_ce_fwd_bwd(void* logits, long ld, int rows, int V, const int64_t* labels, float* counts, float gscale,
+                              float* loss_out, void* logits_copy, long ldcopy, hipStream_t stream) {
+  return ce_fwd_bwd(logits, ld, rows, V, labels, counts, gscale, nullptr, loss_out, logits_copy, ldcopy, stream);
+}
+
+extern "C" int vlb_ce_fwd_bwd_ds(void* logits, long ld, int rows, int V, const int64_t* labels, float* counts, float gscale,
+                                 const float* dscale, float* loss_out, void* logits_copy, long ldcopy, hipStream_t stream) {
+  return ce_fwd_bwd(logits, ld, rows, V, labels, counts, gscale, dscale, loss_out, logits_copy, ldcopy, stream);
+}
+
+static int soft_ce_fwd_bwd(void* logits, long ld, int rows, int C, const float* target, long ldt, float* tsum, float* counts, float gscale,
+                           const float* dscale, float* loss_out, void* logits_copy, long ldcopy, hipStream_t stream) {
+  if (rows <= 0) return VLB_OK;
+  VLB_CHECK_ARG(logits && target && tsum && counts && loss_out, "vlb_soft_ce_fwd_bwd: null argument");
+  VLB_CHECK_ARG(ld >= C && ldt >= C, "vlb_soft_ce_fwd_bwd: bad leading dimensions");
+  (void)hipMemsetAsync(counts, 0, sizeof(float), stream);
+  hipLaunchKernelGGL(soft_valid_kernel, dim3(vlb_cdiv(rows, 4)), dim3(256), 0, stream, target, ldt, C, rows, tsum, counts);
+  if (dscale)
+    hipLaunchKernelGGL(soft_ce_fwd_bwd_kernel<true>, dim3(rows), dim3(256), 0, stream, (bf16_t*)logits, ld, C, target, ldt, tsum, counts,
+                       gscale, loss_out, (bf16_t*)logits_copy, ldcopy, dscale);
+  else
+    hipLaunchKernelGGL(soft_ce_fwd_bwd_kernel<false>, dim3(rows), dim3(256), 0, stream, (bf16_t*)logits, ld, C, target, ldt, tsum, counts,
+                       gscale, loss_out, (bf16_t*)logits_copy, ldcopy, (const float*)nullptr);
+  VLB_CHECK_LAUNCH("vlb_soft_ce_fwd_bwd");
   return VLB_OK;
 }
 
 extern "C" int vlb_soft_ce_fwd_bwd(void* logits, long ld, int rows, int C, const float* target, long ldt, float* tsum,
                                    float* counts, float gscale, float* loss_out, void* logits_copy, long ldcopy,
                                    hipStream_t stream) {
-  if (rows <= 0) return VLB_OK;
-  VLB_CHECK_ARG(logits && target && tsum && counts && loss_out, "vlb_soft_ce_fwd_bwd: null argument");
-  VLB_CHECK_ARG(ld >= C && ldt >= C, "vlb_soft_ce_fwd_bwd: bad leading dimensions");
-  (void)hipMemsetAsync(counts, 0, sizeof(float), stream);
-  hipLaunchKernelGGL(soft_valid_kernel, dim3(vlb_cdiv(rows, 4)), dim3(256), 0, stream, target, ldt, C, rows, tsum, counts);
-  hipLaunchKernelGGL(soft_ce_fwd_bwd_kernel, dim3(rows), dim3(256), 0, stream, (bf16_t*)logits, ld, C, target, ldt, tsum, counts,
-                     gscale, loss_out, (bf16_t*)logits_copy, ldcopy);
-  VLB_CHECK_LAUNCH("vlb_soft_ce_fwd_bwd");
-  return VLB_OK;
+  return soft_ce_fwd_bwd(logits, ld, rows, C, target, ldt, tsum, counts, gscale, nullptr, loss_out, logits_copy, ldcopy, stream);
+}
+
+extern "C" int vlb_soft_ce_fwd_bwd_ds(void* logits, long ld, int rows, int C, const float* target, long ldt, float* tsum, float* counts,
+                                      float gscale, const float* dscale, float* loss_out, void* logits_copy, long ldcopy,
+                                      hipStream_t stream) {
+  return soft_ce_fwd_bwd(logits, ld, rows, C, target, ldt, tsum, counts, gscale, dscale, loss_out, logits_copy, ldcopy, stream);
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -319,10 +372,13 @@ extern "C" int vlb_soft_ce_fwd_bwd(void* logits, long ld, int rows, int C, const
 // the CE kernels: logits (bf16 [rows, ld], columns >= A are padding and are zeroed) are overwritten by gscale * d(loss)/dx, the
 // untouched logits are copied out when asked for (label_logits of the reference's outputs dict).  One block per row.
 // ------------------------------------------------------------------------------------------------------------------
+template <bool DS = false>
 __global__ __launch_bounds__(256) void bce_logits_fwd_bwd_kernel(bf16_t* __restrict__ logits, long ld, int A, const float* __restrict__ label,
                                                                  long ldl, int rows, float gscale, float pos_weight,
-                                                                 float* __restrict__ loss_out, bf16_t* __restrict__ logits_copy, long ldcopy) {
+                                                                 float* __restrict__ loss_out, bf16_t* __restrict__ logits_copy, long ldcopy,
+                                                                 const float* __restrict__ dscale = nullptr) {
   __shared__ float sh[4];
+  if (DS) gscale = __fmul_rn(gscale, *dscale);
   const int row = blockIdx.x;
   bf16_t* x = logits + (long)row * ld;
   const float* y = label + (long)row * ldl;
@@ -346,15 +402,30 @@ __global__ __launch_bounds__(256) void bce_logits_fwd_bwd_kernel(bf16_t* __restr
   if (threadIdx.x == 0) atomicAdd(loss_out, s * inv_rows);
 }
 
-extern "C" int vlb_bce_logits_fwd_bwd(void* logits, long ld, int rows, int A, const float* label, long ldl, float gscale, float pos_weight,
-                                      float* loss_out, void* logits_copy, long ldcopy, hipStream_t stream) {
+static int bce_logits_fwd_bwd(void* logits, long ld, int rows, int A, const float* label, long ldl, float gscale, const float* dscale,
+                              float pos_weight, float* loss_out, void* logits_copy, long ldcopy, hipStream_t stream) {
   if (rows <= 0) return VLB_OK;
   VLB_CHECK_ARG(logits && label && loss_out && A > 0 && ld >= A && ldl >= A, "vlb_bce_logits_fwd_bwd: bad argument");
   VLB_CHECK_ARG(!logits_copy || ldcopy >= A, "vlb_bce_logits_fwd_bwd: ldcopy too small");
-  hipLaunchKernelGGL(bce_logits_fwd_bwd_kernel, dim3(rows), dim3(256), 0, stream, (bf16_t*)logits, ld, A, label, ldl, rows, gscale,
-                     pos_weight, loss_out, (bf16_t*)logits_copy, ldcopy);
+  if (dscale)
+    hipLaunchKernelGGL(bce_logits_fwd_bwd_kernel<true>, dim3(rows), dim3(256), 0, stream, (bf16_t*)logits, ld, A, label, ldl, rows, gscale,
+                       pos_weight, loss_out, (bf16_t*)logits_copy, ldcopy, dscale);
+  else
+    hipLaunchKernelGGL(bce_logits_fwd_bwd_kernel<false>, dim3(rows), dim3(256), 0, stream, (bf16_t*)logits, ld, A, label, ldl, rows, gscale,
+                       pos_weight, loss_out, (bf16_t*)logits_copy, ldcopy, (const float*)nullptr);
   VLB_CHECK_LAUNCH("vlb_bce_logits_fwd_bwd");
   return VLB_OK;
+}
+
+extern "C" int vlb_bce_logits_fwd_bwd(void* logits, long ld, int rows, int A, const float* label, long ldl, float gscale, float pos_weight,
+                                      float* loss_out, void* logits_copy, long ldcopy, hipStream_t stream) {
+  return bce_logits_fwd_bwd(logits, ld, rows, A, label, ldl, gscale, nullptr, pos_weight, loss_out, logits_copy, ldcopy, stream);
+}
+
+extern "C" int vlb_bce_logits_fwd_bwd_ds(void* logits, long ld, int rows, int A, const float* label, long ldl, float gscale,
+                                         const float* dscale, float pos_weight, float* loss_out, void* logits_copy, long ldcopy,
+                                         hipStream_t stream) {
+  return bce_logits_fwd_bwd(logits, ld, rows, A, label, ldl, gscale, dscale, pos_weight, loss_out, logits_copy, ldcopy, stream);
 }
 
 // y = x * keep(idx) / (1 - p) with the counter RNG (element index = position in the [n] array); the same call on dy is the backward.

@@ -20,6 +20,20 @@ struct VlbAdamState {   // device-resident, 8 floats
   float sumsq;          // sum of squares of the gradient (written by vlb_sumsq_f32)
 };
 
+// Dynamic loss scale of an fp16 run (Apex LossScaler.update_scale), device-resident so that a replayed hipGraph carries the skip
+// decision, the scale and the counters without a host round trip.  9 floats (include/vlbert_hip.h: VLB_SCALER_*); the counters are
+// fp32 integers (exact up to 2^24).  The rule, evaluated once per optimizer step by scaler_advance_kernel:
+//   overflow (the step's squared gradient norm is not finite):  scale = max(min_scale, scale * backoff_factor), unskipped = 0,
+//       skipped_total += 1, skipped_in_a_row += 1, and nothing else is updated;
+//   otherwise:  unskipped += 1, skipped_in_a_row = 0, and at unskipped == growth_interval:
+//       scale = min(max_scale, scale * growth_factor), unskipped = 0.
+struct VlbScaler {
+  float scale, growth_factor, backoff_factor, growth_interval, unskipped, skipped_total, skipped_in_a_row, min_scale, max_scale;
+};
+
+// (exponent all ones: inf or NaN; a bit test, so no floating-point mode of the build can fold it away)
+__device__ __forceinline__ bool vlb_nonfinite(float x) { return (__float_as_uint(x) & 0x7f800000u) == 0x7f800000u; }
+
 __global__ __launch_bounds__(256) void sumsq_kernel(const float* __restrict__ g, long n, float* __restrict__ out) {
   __shared__ float sh[4];
   float s = 0.f;
@@ -108,6 +122,11 @@ __device__ __forceinline__ void adamw_scalars(const VlbAdamState* st, float grad
   step_size = __fdiv_rn(__fmul_rn(st->lr, __fsqrt_rn(1.0f - powf(st->beta2, step))), 1.0f - powf(st->beta1, step));      // bias correction
 }
 
+// with a scaler: the gradient carries the loss scale; coef = grad_scale * (1 / scale), the clip norm from the same unscaled value
+__device__ __forceinline__ void adamw_scalars(const VlbAdamState* st, const VlbScaler* sc, float grad_scale, float& coef, float& step_size) {
+  adamw_scalars(st, __fmul_rn(grad_scale, __fdiv_rn(1.0f, sc->scale)), coef, step_size);
+}
+
 __device__ __forceinline__ void adamw_update(float& p, float g, float& m, float& v, float coef, float b1, float b2, float eps,
                                              float step_size, float lr_wd) {
   const float gg = __fmul_rn(g, coef);
@@ -124,13 +143,17 @@ __device__ __forceinline__ void adamw_update(float& p, float g, float& m, float&
 // in particular: 6.6 vs 4.5 TB/s for a pure fill) -- profiles/r04_hbm_stream_probe.txt.
 constexpr int ADAMW_UNITS = 2;
 
-template <typename GT>
+// DYN (a loss scaler is attached, `scaler` non-null): a step whose squared norm is not finite returns before its first load -- p, m,
+// v and the 16-bit copy stay as they are.  The static instantiation is the kernel as it was (the trailing argument is never read).
+template <typename GT, bool DYN = false>
 __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const GT* __restrict__ g, float* __restrict__ m,
                                                     float* __restrict__ v, bf16_t* __restrict__ p16, long n, VlbAdamState* __restrict__ st,
-                                                    float grad_scale) {
+                                                    float grad_scale, const VlbScaler* __restrict__ scaler = nullptr) {
+  if (DYN && vlb_nonfinite(st->sumsq)) return;
   const float lr = st->lr, b1 = st->beta1, b2 = st->beta2, eps = st->eps, wd = st->weight_decay;
   float coef, step_size;
-  adamw_scalars(st, grad_scale, coef, step_size);
+  if (DYN) adamw_scalars(st, scaler, grad_scale, coef, step_size);
+  else adamw_scalars(st, grad_scale, coef, step_size);
   const long i0 = ((long)blockIdx.x * (256 * ADAMW_UNITS) + threadIdx.x) * 4;
   float pv[ADAMW_UNITS][4], gv[ADAMW_UNITS][4], mv[ADAMW_UNITS][4], vv[ADAMW_UNITS][4];
 #pragma unroll
@@ -175,9 +198,16 @@ __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const
 // dampening 0, no Nesterov):  d = coef * g + wd * p ;  buf = momentum * buf + d ;  p -= lr * buf   -- one pass over (p, g, buf),
 // the bf16 working copy refreshed in the same pass.  coef = grad_scale x the clip_grad_norm_ factor from the device-resident
 // squared norm (common/trainer.py:139-145), so no host round trip sits between the gradient norm and the update.
+// DYN: as in adamw_kernel (sumsq is then required: it carries the overflow decision, clip or no clip).
+template <bool DYN = false>
 __global__ __launch_bounds__(256) void sgd_momentum_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ buf,
                                                            bf16_t* __restrict__ p16, long n, float lr, float momentum, float wd,
-                                                           const float* __restrict__ sumsq, float max_norm, float grad_scale) {
+                                                           const float* __restrict__ sumsq, float max_norm, float grad_scale,
+                                                           const VlbScaler* __restrict__ scaler = nullptr) {
+  if (DYN) {
+    if (vlb_nonfinite(*sumsq)) return;
+    grad_scale = __fmul_rn(grad_scale, __fdiv_rn(1.0f, scaler->scale));
+  }
   float coef = grad_scale;
   if (sumsq && max_norm > 0.f) coef *= fminf(max_norm / (sqrtf(*sumsq) * grad_scale + 1e-6f), 1.0f);
   const long stride = (long)gridDim.x * 256 * 4;
@@ -211,13 +241,45 @@ __global__ void adam_advance_kernel(VlbAdamState* st) {
   st->sumsq = 0.f;
 }
 
+// The same place in the stream when a loss scaler is attached: applies the scaler's rule (see VlbScaler), counts the step only when it
+// was taken, sumsq = 0.  st (nullable: SGD keeps no device step) / sumsq (the value the update kernels decided on) / update == 0: only
+// the step count and sumsq (an optimizer of several flat runs shares one scaler and updates it once, after its last run).
+__global__ void scaler_advance_kernel(VlbAdamState* st, const float* sumsq, VlbScaler* sc, int update) {
+  const bool overflow = vlb_nonfinite(*sumsq);
+  if (update) {
+    if (overflow) {
+      sc->scale = fmaxf(sc->min_scale, sc->scale * sc->backoff_factor);
+      sc->unskipped = 0.f;
+      sc->skipped_total += 1.0f;
+      sc->skipped_in_a_row += 1.0f;
+    } else {
+      const float u = sc->unskipped + 1.0f;
+      sc->skipped_in_a_row = 0.f;
+      if (u == sc->growth_interval) {
+        sc->scale = fminf(sc->max_scale, sc->scale * sc->growth_factor);
+        sc->unskipped = 0.f;
+      } else {
+        sc->unskipped = u;
+      }
+    }
+  }
+  if (st) {
+    if (!overflow) st->step += 1.0f;
+    st->sumsq = 0.f;
+  }
+}
+
 // Learning-rate schedule evaluated ON THE DEVICE from the step counter, so that a captured hipGraph replays
 // with the right lr each step.  The reference steps its scheduler BEFORE optimizer.step() (common/trainer.py:131-135),
 // and LambdaLR starts at last_epoch = 0, so optimizer step k (1-based) runs with base_lr * lambda(k) where
 // k = steps already taken + 1.  kind: 0 ConstantLRSchedule | 1 WarmupConstantSchedule | 2 WarmupLinearSchedule
 // (common/nlp/bert/optimization.py:27-62; "triangle" in pretrain/function/train.py:316-320).
-__global__ void lr_schedule_kernel(VlbAdamState* st, int kind, float base_lr, float warmup_steps, float t_total) {
-  const float k = st->step + 1.0f;
+// With a loss scaler k = steps taken + steps skipped + 1: the reference's scheduler steps on every iteration while a skipped
+// optimizer.step() leaves Adam's own state['step'] (the bias correction) alone.
+template <bool DYN = false>
+__global__ void lr_schedule_kernel(VlbAdamState* st, int kind, float base_lr, float warmup_steps, float t_total,
+                                   const VlbScaler* scaler = nullptr) {
+  const float k = DYN ? st->step + scaler->skipped_total + 1.0f : st->step + 1.0f;
   float f = 1.0f;
   if (kind != 0) {
     if (k < warmup_steps) f = k / fmaxf(1.0f, warmup_steps);
@@ -301,8 +363,8 @@ extern "C" int vlb_adamw_step(float* p, const float* g, float* m, float* v, void
                               hipStream_t stream) {
   if (n <= 0) return VLB_OK;
   VLB_CHECK_ARG(p && g && m && v && state, "vlb_adamw_step: null argument");
-  hipLaunchKernelGGL(adamw_kernel<float>, dim3(adamw_grid(n)), dim3(256), 0, stream, p, g, m, v, (bf16_t*)p_bf16, n,
-                     (VlbAdamState*)state, grad_scale);
+  hipLaunchKernelGGL((adamw_kernel<float, false>), dim3(adamw_grid(n)), dim3(256), 0, stream, p, g, m, v, (bf16_t*)p_bf16, n,
+                     (VlbAdamState*)state, grad_scale, (const VlbScaler*)nullptr);
   hipLaunchKernelGGL(adam_advance_kernel, dim3(1), dim3(1), 0, stream, (VlbAdamState*)state);
   VLB_CHECK_LAUNCH("vlb_adamw_step");
   return VLB_OK;
@@ -313,8 +375,8 @@ extern "C" int vlb_sgd_momentum_step(float* p, const float* g, float* momentum_b
   if (n <= 0) return VLB_OK;
   VLB_CHECK_ARG(p && g && momentum_buf, "vlb_sgd_momentum_step: null argument");
   VLB_CHECK_ARG(momentum >= 0.f && lr >= 0.f && weight_decay >= 0.f, "vlb_sgd_momentum_step: negative hyper-parameter");
-  hipLaunchKernelGGL(sgd_momentum_kernel, dim3(grid_for((n + 3) / 4)), dim3(256), 0, stream, p, g, momentum_buf, (bf16_t*)p_bf16, n, lr,
-                     momentum, weight_decay, sumsq, max_norm, grad_scale);
+  hipLaunchKernelGGL(sgd_momentum_kernel<false>, dim3(grid_for((n + 3) / 4)), dim3(256), 0, stream, p, g, momentum_buf, (bf16_t*)p_bf16, n, lr,
+                     momentum, weight_decay, sumsq, max_norm, grad_scale, (const VlbScaler*)nullptr);
   VLB_CHECK_LAUNCH("vlb_sgd_momentum_step");
   return VLB_OK;
 }
@@ -325,8 +387,8 @@ extern "C" int vlb_adamw_step_gbf16(float* p, const void* g_bf16, float* m, floa
   if (n <= 0) return VLB_OK;
   VLB_CHECK_ARG(p && g_bf16 && m && v && state, "vlb_adamw_step_gbf16: null argument");
   VLB_CHECK_ARG(((uintptr_t)g_bf16 % 8) == 0, "vlb_adamw_step_gbf16: gradient must be 8-byte aligned");
-  hipLaunchKernelGGL(adamw_kernel<bf16_t>, dim3(adamw_grid(n)), dim3(256), 0, stream, p, (const bf16_t*)g_bf16, m, v,
-                     (bf16_t*)p_bf16, n, (VlbAdamState*)state, grad_scale);
+  hipLaunchKernelGGL((adamw_kernel<bf16_t, false>), dim3(adamw_grid(n)), dim3(256), 0, stream, p, (const bf16_t*)g_bf16, m, v,
+                     (bf16_t*)p_bf16, n, (VlbAdamState*)state, grad_scale, (const VlbScaler*)nullptr);
   hipLaunchKernelGGL(adam_advance_kernel, dim3(1), dim3(1), 0, stream, (VlbAdamState*)state);
   VLB_CHECK_LAUNCH("vlb_adamw_step_gbf16");
   return VLB_OK;
@@ -373,14 +435,35 @@ __global__ __launch_bounds__(256) void sumsq_ranges_partial_kernel(const GT* __r
   if (threadIdx.x == 0) partials[blockIdx.x] = (sh[0] + sh[1]) + (sh[2] + sh[3]);
 }
 
-template <typename GT>
+// DYN: see adamw_kernel, with one exception -- a skipped step still writes the compact 16-bit image, as the cast of the UNCHANGED
+// master: gather_params all-gathers that image, and it holds nothing valid before the first step that is really taken (the first
+// steps of a run at scale 2^16 routinely skip).  p, m, v are not written and g, m, v not read.
+template <typename GT, bool DYN = false>
 __global__ __launch_bounds__(256) void adamw_ranges_kernel(float* __restrict__ p, const GT* __restrict__ g, float* __restrict__ m,
                                                            float* __restrict__ v, bf16_t* __restrict__ p16c,
                                                            const long* __restrict__ ranges, const int* __restrict__ block_start, int n,
-                                                           int chunk, const VlbAdamState* __restrict__ st, float grad_scale) {
+                                                           int chunk, const VlbAdamState* __restrict__ st, float grad_scale,
+                                                           const VlbScaler* __restrict__ scaler = nullptr) {
+  if (DYN && vlb_nonfinite(st->sumsq)) {
+    if (!p16c) return;
+    const int r = range_of_block(block_start, n, blockIdx.x);
+    const long p0 = ranges[3 * r], g0 = ranges[3 * r + 1], len = ranges[3 * r + 2];
+    const long base = (long)(blockIdx.x - block_start[r]) * chunk;
+    const long end = min(base + (long)chunk, len);
+    for (long i = base + threadIdx.x * 4; i < end; i += 1024) {
+      if (end - i >= 4) {
+        const float4 a = *(const float4*)(p + p0 + i);
+        *(uint2*)(p16c + g0 + i) = make_uint2(pack2bf(a.x, a.y), pack2bf(a.z, a.w));
+      } else {
+        for (long k = i; k < end; ++k) p16c[g0 + k] = f2bf(p[p0 + k]);
+      }
+    }
+    return;
+  }
   const float lr = st->lr, b1 = st->beta1, b2 = st->beta2, eps = st->eps, wd = st->weight_decay;
   float coef, step_size;
-  adamw_scalars(st, grad_scale, coef, step_size);
+  if (DYN) adamw_scalars(st, scaler, grad_scale, coef, step_size);
+  else adamw_scalars(st, grad_scale, coef, step_size);
   const int r = range_of_block(block_start, n, blockIdx.x);
   const long p0 = ranges[3 * r], g0 = ranges[3 * r + 1], len = ranges[3 * r + 2];
   const long base = (long)(blockIdx.x - block_start[r]) * chunk;
@@ -449,14 +532,98 @@ extern "C" int vlb_adamw_step_ranges(float* p, const void* g, int g_is_bf16, flo
     VLB_CHECK_ARG(chunk >= 1024 && (chunk % 1024) == 0, "vlb_adamw_step_ranges: chunk must be a positive multiple of 1024");
     VLB_CHECK_ARG(((uintptr_t)g % 16) == 0 && ((uintptr_t)p % 16) == 0, "vlb_adamw_step_ranges: buffers must be 16-byte aligned");
     if (g_is_bf16)
-      hipLaunchKernelGGL(adamw_ranges_kernel<bf16_t>, dim3(total_blocks), dim3(256), 0, stream, p, (const bf16_t*)g, m, v,
-                         (bf16_t*)p_bf16_compact, (const long*)ranges, (const int*)block_start, n, chunk, (const VlbAdamState*)state, grad_scale);
+      hipLaunchKernelGGL((adamw_ranges_kernel<bf16_t, false>), dim3(total_blocks), dim3(256), 0, stream, p, (const bf16_t*)g, m, v,
+                         (bf16_t*)p_bf16_compact, (const long*)ranges, (const int*)block_start, n, chunk, (const VlbAdamState*)state, grad_scale,
+                         (const VlbScaler*)nullptr);
     else
-      hipLaunchKernelGGL(adamw_ranges_kernel<float>, dim3(total_blocks), dim3(256), 0, stream, p, (const float*)g, m, v,
-                         (bf16_t*)p_bf16_compact, (const long*)ranges, (const int*)block_start, n, chunk, (const VlbAdamState*)state, grad_scale);
+      hipLaunchKernelGGL((adamw_ranges_kernel<float, false>), dim3(total_blocks), dim3(256), 0, stream, p, (const float*)g, m, v,
+                         (bf16_t*)p_bf16_compact, (const long*)ranges, (const int*)block_start, n, chunk, (const VlbAdamState*)state, grad_scale,
+                         (const VlbScaler*)nullptr);
   }
   hipLaunchKernelGGL(adam_advance_kernel, dim3(1), dim3(1), 0, stream, (VlbAdamState*)state);
   VLB_CHECK_LAUNCH("vlb_adamw_step_ranges");
+  return VLB_OK;
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// The same steps with a dynamic loss scaler attached (scaler: device float[9], see VlbScaler).  The gradient carries the scale; an
+// overflowed step (non-finite sumsq) leaves p / m / v / step alone.  update_scaler != 0: the scaler's rule is applied after the update
+// (0 for all but the last of several flat runs that share one scaler).
+// ------------------------------------------------------------------------------------------------------------------
+static int check_scaler_arg(const float* scaler, const char* who) {
+  VLB_CHECK_ARG(scaler && ((uintptr_t)scaler % 4) == 0, "%s: null or misaligned scaler", who);
+  return VLB_OK;
+}
+
+extern "C" int vlb_adamw_step_scaled(float* p, const void* g, int g_is_bf16, float* m, float* v, void* p_bf16, long n, float* state,
+                                     float* scaler, int update_scaler, float grad_scale, hipStream_t stream) {
+  VLB_CHECK_ARG(state, "vlb_adamw_step_scaled: null state");
+  if (check_scaler_arg(scaler, "vlb_adamw_step_scaled") != VLB_OK) return VLB_ERR_ARG;
+  if (n > 0) {
+    VLB_CHECK_ARG(p && g && m && v, "vlb_adamw_step_scaled: null argument");
+    VLB_CHECK_ARG(!g_is_bf16 || ((uintptr_t)g % 8) == 0, "vlb_adamw_step_scaled: gradient must be 8-byte aligned");
+    if (g_is_bf16)
+      hipLaunchKernelGGL((adamw_kernel<bf16_t, true>), dim3(adamw_grid(n)), dim3(256), 0, stream, p, (const bf16_t*)g, m, v, (bf16_t*)p_bf16, n,
+                         (VlbAdamState*)state, grad_scale, (const VlbScaler*)scaler);
+    else
+      hipLaunchKernelGGL((adamw_kernel<float, true>), dim3(adamw_grid(n)), dim3(256), 0, stream, p, (const float*)g, m, v, (bf16_t*)p_bf16, n,
+                         (VlbAdamState*)state, grad_scale, (const VlbScaler*)scaler);
+  }
+  hipLaunchKernelGGL(scaler_advance_kernel, dim3(1), dim3(1), 0, stream, (VlbAdamState*)state, (const float*)(state + 7), (VlbScaler*)scaler,
+                     update_scaler);
+  VLB_CHECK_LAUNCH("vlb_adamw_step_scaled");
+  return VLB_OK;
+}
+
+extern "C" int vlb_adamw_step_ranges_scaled(float* p, const void* g, int g_is_bf16, float* m, float* v, void* p_bf16_compact,
+                                            const int64_t* ranges, const int32_t* block_start, int n, int total_blocks, int chunk,
+                                            float* state, float* scaler, float grad_scale, hipStream_t stream) {
+  VLB_CHECK_ARG(state, "vlb_adamw_step_ranges_scaled: null state");
+  if (check_scaler_arg(scaler, "vlb_adamw_step_ranges_scaled") != VLB_OK) return VLB_ERR_ARG;
+  if (n > 0 && total_blocks > 0) {
+    VLB_CHECK_ARG(p && g && m && v && ranges && block_start, "vlb_adamw_step_ranges_scaled: null argument");
+    VLB_CHECK_ARG(chunk >= 1024 && (chunk % 1024) == 0, "vlb_adamw_step_ranges_scaled: chunk must be a positive multiple of 1024");
+    VLB_CHECK_ARG(((uintptr_t)g % 16) == 0 && ((uintptr_t)p % 16) == 0, "vlb_adamw_step_ranges_scaled: buffers must be 16-byte aligned");
+    if (g_is_bf16)
+      hipLaunchKernelGGL((adamw_ranges_kernel<bf16_t, true>), dim3(total_blocks), dim3(256), 0, stream, p, (const bf16_t*)g, m, v,
+                         (bf16_t*)p_bf16_compact, (const long*)ranges, (const int*)block_start, n, chunk, (const VlbAdamState*)state, grad_scale,
+                         (const VlbScaler*)scaler);
+    else
+      hipLaunchKernelGGL((adamw_ranges_kernel<float, true>), dim3(total_blocks), dim3(256), 0, stream, p, (const float*)g, m, v,
+                         (bf16_t*)p_bf16_compact, (const long*)ranges, (const int*)block_start, n, chunk, (const VlbAdamState*)state, grad_scale,
+                         (const VlbScaler*)scaler);
+  }
+  hipLaunchKernelGGL(scaler_advance_kernel, dim3(1), dim3(1), 0, stream, (VlbAdamState*)state, (const float*)(state + 7), (VlbScaler*)scaler, 1);
+  VLB_CHECK_LAUNCH("vlb_adamw_step_ranges_scaled");
+  return VLB_OK;
+}
+
+// sumsq is required (it carries the overflow decision) and is left as it is: the caller owns it
+extern "C" int vlb_sgd_momentum_step_scaled(float* p, const float* g, float* momentum_buf, void* p_bf16, long n, float lr, float momentum,
+                                            float weight_decay, const float* sumsq, float max_norm, float grad_scale, float* scaler,
+                                            int update_scaler, hipStream_t stream) {
+  VLB_CHECK_ARG(sumsq, "vlb_sgd_momentum_step_scaled: the squared gradient norm is required");
+  if (check_scaler_arg(scaler, "vlb_sgd_momentum_step_scaled") != VLB_OK) return VLB_ERR_ARG;
+  VLB_CHECK_ARG(momentum >= 0.f && lr >= 0.f && weight_decay >= 0.f, "vlb_sgd_momentum_step_scaled: negative hyper-parameter");
+  if (n > 0) {
+    VLB_CHECK_ARG(p && g && momentum_buf, "vlb_sgd_momentum_step_scaled: null argument");
+    hipLaunchKernelGGL(sgd_momentum_kernel<true>, dim3(grid_for((n + 3) / 4)), dim3(256), 0, stream, p, g, momentum_buf, (bf16_t*)p_bf16, n,
+                       lr, momentum, weight_decay, sumsq, max_norm, grad_scale, (const VlbScaler*)scaler);
+  }
+  if (update_scaler)
+    hipLaunchKernelGGL(scaler_advance_kernel, dim3(1), dim3(1), 0, stream, (VlbAdamState*)nullptr, sumsq, (VlbScaler*)scaler, 1);
+  VLB_CHECK_LAUNCH("vlb_sgd_momentum_step_scaled");
+  return VLB_OK;
+}
+
+extern "C" int vlb_lr_schedule_step_scaled(float* state, const float* scaler, int kind, float base_lr, float warmup_steps, float t_total,
+                                           hipStream_t stream) {
+  VLB_CHECK_ARG(state && scaler, "vlb_lr_schedule_step_scaled: null state / scaler");
+  VLB_CHECK_ARG(kind >= 0 && kind <= 2, "vlb_lr_schedule_step_scaled: kind must be 0 (constant), 1 (warmup-constant) or 2 (warmup-linear)");
+  VLB_CHECK_ARG(base_lr >= 0.f && warmup_steps >= 0.f, "vlb_lr_schedule_step_scaled: negative base_lr / warmup_steps");
+  hipLaunchKernelGGL(lr_schedule_kernel<true>, dim3(1), dim3(1), 0, stream, (VlbAdamState*)state, kind, base_lr, warmup_steps, t_total,
+                     (const VlbScaler*)scaler);
+  VLB_CHECK_LAUNCH("vlb_lr_schedule_step_scaled");
   return VLB_OK;
 }
 
@@ -464,7 +631,8 @@ extern "C" int vlb_lr_schedule_step(float* state, int kind, float base_lr, float
   VLB_CHECK_ARG(state, "vlb_lr_schedule_step: null state");
   VLB_CHECK_ARG(kind >= 0 && kind <= 2, "vlb_lr_schedule_step: kind must be 0 (constant), 1 (warmup-constant) or 2 (warmup-linear)");
   VLB_CHECK_ARG(base_lr >= 0.f && warmup_steps >= 0.f, "vlb_lr_schedule_step: negative base_lr / warmup_steps");
-  hipLaunchKernelGGL(lr_schedule_kernel, dim3(1), dim3(1), 0, stream, (VlbAdamState*)state, kind, base_lr, warmup_steps, t_total);
+  hipLaunchKernelGGL(lr_schedule_kernel<false>, dim3(1), dim3(1), 0, stream, (VlbAdamState*)state, kind, base_lr, warmup_steps, t_total,
+                     (const VlbScaler*)nullptr);
   VLB_CHECK_LAUNCH("vlb_lr_schedule_step");
   return VLB_OK;
 }

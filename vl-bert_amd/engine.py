@@ -186,9 +186,21 @@ class PretrainEngine:
         # grad_scale divides it out (clip norm included).  1 in the bf16 build (fp32 exponent range); 4096 by default in the fp16
         # build (VLB_PRECISION=f16): d(logits) ~ 1/n_valid ~ 4e-4 at batch 256 would sit in fp16's subnormals otherwise.  Engines behind
         # the autograd mirrors (flat=... / core=True) hand their parameter gradients to torch unscaled, so they default to 1.
-        if loss_scale is None:
-            loss_scale = 4096.0 if (ops.BF16 == torch.float16 and flat is None and not core) else 1.0
-        self.loss_scale = float(loss_scale)
+        # loss_scale="dynamic" / a loss_scale.DynamicLossScale (the reference's FP16_LOSS_SCALE: 'dynamic', Apex's dynamic scaler): the
+        # scale lives in a device array (self.scaler) that the loss kernels multiply by and the optimizer kernels divide out; a step
+        # whose squared gradient norm is not finite is skipped on the device, the scale halves, and doubles again after a window of
+        # clean steps (loss_scale.py).  Static engines run exactly the launches they ran before.
+        from . import loss_scale as LS
+        self._scaler_spec = LS.resolve(loss_scale)
+        self.scaler = None
+        if self._scaler_spec is not None:
+            if flat is not None or core:
+                raise ValueError("loss_scale='dynamic' needs an engine that owns its optimizer step (not the flat=... / core=True modes)")
+            self._loss_scale = None
+        else:
+            if loss_scale is None:
+                loss_scale = 4096.0 if (ops.BF16 == torch.float16 and flat is None and not core) else 1.0
+            self._loss_scale = float(loss_scale)
         # multitask: B_aux text-only samples are appended after the B image-caption samples; they have no
         # objects, their text-visual embedding is the learned aux_text_visual_embedding and their MLM loss is
         # accounted separately (resnet_vlbert_for_pretraining_multitask.py:96-290).  T = max(caption, aux) length.
@@ -268,6 +280,8 @@ class PretrainEngine:
         self.seed = torch.tensor([((seed * 2 + 1) & 0x7FFFFFFF)], dtype=torch.int32, device=d)
         self.adam = torch.tensor([lr, betas[0], betas[1], eps, weight_decay, 0.0, max_grad_norm, 0.0], dtype=F32, device=d)
         self.hyper = dict(betas=(float(betas[0]), float(betas[1])), eps=float(eps), weight_decay=float(weight_decay))   # as given (checkpoints)
+        if self._scaler_spec is not None:
+            self.scaler = LS.LossScaler(self._scaler_spec, d)
         self.sumsq_ws = zf(2048)  # per-block partial sums of the gradient norm
         self.losses = zf(4)       # mlm (with visual content), mvrc, mlm (aux text), relationship
         self.counts = zf(4)       # n_valid mlm, n_valid mvrc, n_valid mlm aux
@@ -593,7 +607,7 @@ class PretrainEngine:
         train = self.train if train is None else train
         self._forward_to_logits(train)
         if not self.core:
-            self._losses_fwd_bwd(gscale * self.loss_scale, True)
+            self._losses_fwd_bwd(gscale if self.scaler is not None else gscale * self.loss_scale, True)
 
     def _forward_to_logits(self, train):
         """Everything of a forward up to the logits (loss slots zeroed, losses not yet computed): shared by forward() and eval_step()."""
@@ -773,22 +787,23 @@ class PretrainEngine:
             self.mvrc_logits.copy_(self.mvrc_logits_copy)
             losses, mcopy, vcopy = torch.zeros_like(self.losses), None, None
         nw = B * T     # rows of the image-caption samples; the aux rows follow and get their own mean (multitask.py:224-246)
+        ds = self.scaler.scale if self.scaler is not None else None      # dynamic loss scale: multiplied into gscale on the device
         if self._mlm_compact_now:      # labelled rows only: caption rows first, then the aux rows, each group with its own mean
             ops.ce_fwd_bwd_compact(self.mlm_logits[:self.mlm_cap], V, self.labels_c, self.counts[0:1], self.counts[2:3], losses[0:1],
-                                   losses[2:3], gscale=gscale)
+                                   losses[2:3], gscale=gscale, dscale=ds)
         else:
             ops.ce_fwd_bwd(self.mlm_logits[:nw], V, self.in_mlm_labels.view(-1)[:nw], self.counts[0:1], losses[0:1], gscale=gscale,
-                           logits_copy=mcopy[:nw] if mcopy is not None else None)
+                           logits_copy=mcopy[:nw] if mcopy is not None else None, dscale=ds)
             if Ba:
                 ops.ce_fwd_bwd(self.mlm_logits[nw:], V, self.in_mlm_labels.view(-1)[nw:], self.counts[2:3], losses[2:3],
-                               gscale=gscale, logits_copy=mcopy[nw:] if mcopy is not None else None)
+                               gscale=gscale, logits_copy=mcopy[nw:] if mcopy is not None else None, dscale=ds)
         ops.soft_ce_fwd_bwd(self.mvrc_logits, C, self.in_mvrc_labels.view(self.BR, C), self.mvrc_tsum, self.counts[1:2],
-                            losses[1:2], gscale=gscale, logits_copy=vcopy)
+                            losses[1:2], gscale=gscale, logits_copy=vcopy, dscale=ds)
         if self.cfg.with_rel_loss:     # F.cross_entropy(relationship_logits, relationship_label) (resnet_vlbert_for_pretraining.py:160-161)
             if not keep:
                 self.rel_logits.copy_(self.rel_logits_copy)
             ops.ce_fwd_bwd(self.rel_logits, 2, self.in_rel_label, self.counts[3:4], losses[3:4], gscale=gscale,
-                           logits_copy=self.rel_logits_copy if keep else None)
+                           logits_copy=self.rel_logits_copy if keep else None, dscale=ds)
 
     # ------------------------------------------------------------------------------------------
     # backward (explicit; weight gradients are ACCUMULATED into the flat fp32 grad buffer)
@@ -1204,9 +1219,13 @@ class PretrainEngine:
             if self.lr_kind is not None:
                 raise ValueError("optimizer_step(lr=...) conflicts with the device-side lr_schedule of this engine")
             self.adam[0:1].fill_(lr)
+        sc = self.scaler.state if self.scaler is not None else None
         if self.lr_kind is not None:
-            ops.lr_schedule_step(self.adam, self.lr_kind, self.base_lr, self.warmup_steps, self.t_total)
-        scale = (self.buckets.grad_scale if self.buckets is not None else 1.0) / self.loss_scale
+            ops.lr_schedule_step(self.adam, self.lr_kind, self.base_lr, self.warmup_steps, self.t_total, scaler=sc)
+        # dynamic loss scale: the kernels divide the device scale out themselves, skip the update when the (all-reduced) squared norm
+        # is not finite -- every rank sees the same value, so every rank takes the same branch -- and then apply the scaler's rule.
+        # Everything else in the step (weight refresh / gather, dropout seed) runs as usual, on unchanged data after a skip.
+        scale = (self.buckets.grad_scale if self.buckets is not None else 1.0) / (1.0 if sc is not None else self.loss_scale)
         self._check_mlm_overflow_now_and_then()
         if self.buckets is not None and self.buckets.pending:
             self.buckets.wait()
@@ -1216,7 +1235,7 @@ class PretrainEngine:
             g = self.buckets.grad_shard
             self.shard_tbl.sumsq(g, self.sumsq_ws, self.adam[7:8])
             self.buckets.all_reduce_scalar(self.adam[7:8])
-            self.shard_tbl.adamw(self.P.master, g, self.P.m, self.P.v, self.wshard, self.adam, grad_scale=scale)
+            self.shard_tbl.adamw(self.P.master, g, self.P.m, self.P.v, self.wshard, self.adam, grad_scale=scale, scaler=sc)
             self.buckets.gather_params(self.P.w16, self.wshard, master=self.P.master, vision_master=self.vision is not None)
             self._wT_stale = self._gather_pending = True
             self._vision_stale = self.vision is not None
@@ -1225,7 +1244,7 @@ class PretrainEngine:
         # data parallel: the reduced gradient is read where the exchange left it (the bf16 wire image by default, parallel.py)
         grad = self.buckets.reduced if self.buckets is not None else self.P.grad
         ops.sumsq_det(grad, self.sumsq_ws, self.adam[7:8])     # fixed summation order: replicas stay bit-identical
-        ops.adamw_step(self.P.master, grad, self.P.m, self.P.v, self.P.w16, self.adam, grad_scale=scale)
+        ops.adamw_step(self.P.master, grad, self.P.m, self.P.v, self.P.w16, self.adam, grad_scale=scale, scaler=sc)
         self._refresh_transposes()
         if self.vision is not None:
             self.vision.refresh_weights(trainable_only=True)
@@ -1235,11 +1254,27 @@ class PretrainEngine:
         """MLM head compaction with device-resident labels: the overflow flag (a batch with more labelled positions than mlm_cap ran
         truncated) is otherwise only read by loss_values(); loops that never call it get the check every `every` optimizer steps
         (one 4-byte readback)."""
-        if self.mlm_cap is None:
+        if self.mlm_cap is None and self.scaler is None:
             return
         self._opt_steps = getattr(self, "_opt_steps", 0) + 1
         if self._opt_steps % every == 0 and not torch.cuda.is_current_stream_capturing():
+            self._periodic_host_checks()
+
+    def _periodic_host_checks(self):
+        if self.mlm_cap is not None:
             self._raise_on_mlm_overflow()
+        if self.scaler is not None:
+            self._raise_on_stuck_scaler()
+
+    def _raise_on_stuck_scaler(self):
+        """Dynamic loss scale: skipped_in_a_row >= 32 with the scale on its floor means the gradients still are not finite after every
+        halving there was to take -- a run that would otherwise go on forever without training (one 36-byte readback).  A scale that
+        is still above its floor (a gentle backoff factor, a very large start) is a run that is still recovering."""
+        from .loss_scale import stuck
+        v = self.scaler.values()
+        if stuck(v):
+            raise FloatingPointError("dynamic loss scale: %d optimizer steps in a row were skipped for non-finite gradients and the scale "
+                                     "is at its floor (%g): the gradients are inf / NaN for a reason no loss scale can fix" % (int(v[6]), v[0]))
 
     def _raise_on_mlm_overflow(self):
         if int(self.mlm_overflow.cpu()) != 0:
@@ -1283,7 +1318,7 @@ class PretrainEngine:
         import torch.distributed as dist
         if not (dist.is_available() and dist.is_initialized()) or dist.get_world_size(self.pg) == 1:
             return
-        for t in (self.P.master, self.P.m, self.P.v, self.adam):
+        for t in (self.P.master, self.P.m, self.P.v, self.adam) + ((self.scaler.state,) if self.scaler is not None else ()):
             dist.broadcast(t, src=src, group=self.pg)
         if self.vision is not None:
             for t in self.vision.broadcast_tensors():
@@ -1331,8 +1366,28 @@ class PretrainEngine:
             out.update(mlm_loss_wvc=float(l[0]), mlm_loss_aux=float(l[2]))
         return out
 
+    @property
+    def loss_scale(self):
+        """The loss scale as a plain float: the constructor's value for a static engine; for a dynamic one the device value (one
+        4-byte readback: not for the timed loop)."""
+        if self.scaler is not None:
+            return float(self.scaler.scale.cpu())
+        return self._loss_scale
+
+    @loss_scale.setter
+    def loss_scale(self, value):
+        if self.scaler is not None:
+            raise AttributeError("the loss scale of a dynamic engine lives on the device (eng.scaler)")
+        self._loss_scale = float(value)
+
+    def scaler_state(self):
+        """{scale, growth_factor, backoff_factor, growth_interval, unskipped, skipped_total, skipped_in_a_row, min_scale, max_scale} of a
+        dynamic engine, with one readback; None for a static one."""
+        return self.scaler.read() if self.scaler is not None else None
+
     def grads(self):
-        """Parameter gradients of the local batch (the loss scale divided out)."""
+        """Parameter gradients of the local batch (the loss scale divided out).  With a dynamic loss scale this and grad_norm() divide
+        by the CURRENT device scale: valid between backward() and optimizer_step(), which may halve or grow it."""
         inv = 1.0 / self.loss_scale
         return OrderedDict((k, v.detach().clone() * inv if inv != 1.0 else v.detach().clone()) for k, v in self.g32.items())
 
@@ -1443,5 +1498,6 @@ class _SegmentedStep:
         # optimizer_step's periodic host-side checks ran once, at capture: the replay loop carries them itself (MLM head compaction
         # overflow flag, one 4-byte readback every CHECK_EVERY replays -- never a silent truncation of the labelled positions)
         self.replays += 1
-        if self.eng.mlm_cap is not None and self.replays % self.CHECK_EVERY == 0:
-            self.eng._raise_on_mlm_overflow()
+        # (and, with a dynamic loss scale, the scaler's skipped_in_a_row counter: a run pinned at the floor must not go on silently)
+        if self.replays % self.CHECK_EVERY == 0 and (self.eng.mlm_cap is not None or self.eng.scaler is not None):
+            self.eng._periodic_host_checks()

@@ -383,8 +383,13 @@ def mul_bf16(a, b, out):
     return out
 
 
-def ce_fwd_bwd(logits, V, labels, counts, loss_out, gscale=1.0, logits_copy=None):
+def ce_fwd_bwd(logits, V, labels, counts, loss_out, gscale=1.0, logits_copy=None, dscale=None):
+    """dscale (fp32 device scalar, e.g. the scale slot of a loss scaler): the gradient scale is gscale * dscale, formed on the device."""
     rows = logits.shape[0]
+    if dscale is not None:
+        _lib.call("vlb_ce_fwd_bwd_ds", _p(logits, BF16), _ld(logits), rows, V, _p(labels, torch.int64), _p(counts, torch.float32),
+                  float(gscale), _p(dscale, torch.float32), _p(loss_out, torch.float32), _p(logits_copy, BF16), _ld(logits_copy), _stream())
+        return
     _lib.call("vlb_ce_fwd_bwd", _p(logits, BF16), _ld(logits), rows, V, _p(labels, torch.int64), _p(counts, torch.float32),
               float(gscale), _p(loss_out, torch.float32), _p(logits_copy, BF16), _ld(logits_copy), _stream())
 
@@ -396,7 +401,12 @@ def mlm_compact(labels, src_rows, n_split, V, sel_pos, sel_src, labels_c, count0
               _p(count1, torch.float32), _p(overflow, torch.int32), _stream())
 
 
-def ce_fwd_bwd_compact(logits, V, labels_c, count0, count1, loss_out0, loss_out1, gscale=1.0):
+def ce_fwd_bwd_compact(logits, V, labels_c, count0, count1, loss_out0, loss_out1, gscale=1.0, dscale=None):
+    if dscale is not None:
+        _lib.call("vlb_ce_fwd_bwd_compact_ds", _p(logits, BF16), _ld(logits), logits.shape[0], V, _p(labels_c, torch.int64),
+                  _p(count0, torch.float32), _p(count1, torch.float32), float(gscale), _p(dscale, torch.float32),
+                  _p(loss_out0, torch.float32), _p(loss_out1, torch.float32), _stream())
+        return
     _lib.call("vlb_ce_fwd_bwd_compact", _p(logits, BF16), _ld(logits), logits.shape[0], V, _p(labels_c, torch.int64),
               _p(count0, torch.float32), _p(count1, torch.float32), float(gscale), _p(loss_out0, torch.float32),
               _p(loss_out1, torch.float32), _stream())
@@ -407,8 +417,13 @@ def scatter_rows(src, idx, out):
     return out
 
 
-def soft_ce_fwd_bwd(logits, C, target, tsum, counts, loss_out, gscale=1.0, logits_copy=None):
+def soft_ce_fwd_bwd(logits, C, target, tsum, counts, loss_out, gscale=1.0, logits_copy=None, dscale=None):
     rows = logits.shape[0]
+    if dscale is not None:
+        _lib.call("vlb_soft_ce_fwd_bwd_ds", _p(logits, BF16), _ld(logits), rows, C, _p(target, torch.float32), _ld(target),
+                  _p(tsum, torch.float32), _p(counts, torch.float32), float(gscale), _p(dscale, torch.float32),
+                  _p(loss_out, torch.float32), _p(logits_copy, BF16), _ld(logits_copy), _stream())
+        return
     _lib.call("vlb_soft_ce_fwd_bwd", _p(logits, BF16), _ld(logits), rows, C, _p(target, torch.float32), _ld(target),
               _p(tsum, torch.float32), _p(counts, torch.float32), float(gscale), _p(loss_out, torch.float32),
               _p(logits_copy, BF16), _ld(logits_copy), _stream())
@@ -471,10 +486,15 @@ def joint_hits(pred_a, label_a, pred_r, label_r, acc):
               _p(acc, torch.int64), _stream())
 
 
-def bce_logits_fwd_bwd(logits, A, label, loss_out, gscale=1.0, logits_copy=None, pos_weight=1.0):
+def bce_logits_fwd_bwd(logits, A, label, loss_out, gscale=1.0, logits_copy=None, pos_weight=1.0, dscale=None):
     """logits bf16 [rows, >=A] <- gscale * w * (sigmoid(x) - y) / rows in place; loss_out += BCE-with-logits * A (reference convention);
-    w = pos_weight on the positive labels (VCR), 1 elsewhere."""
+    w = pos_weight on the positive labels (VCR), 1 elsewhere.  dscale: fp32 device scalar multiplied into gscale on the device."""
     rows = logits.shape[0]
+    if dscale is not None:
+        _lib.call("vlb_bce_logits_fwd_bwd_ds", _p(logits, BF16), _ld(logits), rows, A, _p(label, torch.float32), _ld(label), float(gscale),
+                  _p(dscale, torch.float32), float(pos_weight), _p(loss_out, torch.float32), _p(logits_copy, BF16), _ld(logits_copy),
+                  _stream())
+        return
     _lib.call("vlb_bce_logits_fwd_bwd", _p(logits, BF16), _ld(logits), rows, A, _p(label, torch.float32), _ld(label), float(gscale),
               float(pos_weight), _p(loss_out, torch.float32), _p(logits_copy, BF16), _ld(logits_copy), _stream())
 
@@ -543,7 +563,14 @@ def sumsq_det(g, partials, out):
               _stream())
 
 
-def adamw_step(p, g, m, v, p16, state, grad_scale=1.0):
+def adamw_step(p, g, m, v, p16, state, grad_scale=1.0, scaler=None, update_scaler=True):
+    """scaler (fp32 device [SCALER_FLOATS], loss_scale.py): the gradient carries the dynamic loss scale; an overflowed step is skipped on
+    the device and the scaler's rule applied after the update (vlb_adamw_step_scaled)."""
+    if scaler is not None:
+        _lib.call("vlb_adamw_step_scaled", _p(p, torch.float32), _p(g), 1 if g.dtype == BF16 else 0, _p(m, torch.float32),
+                  _p(v, torch.float32), _p(p16, BF16), p.numel(), _p(state, torch.float32), _scaler_p(scaler), 1 if update_scaler else 0,
+                  float(grad_scale), _stream())
+        return
     if g.dtype == BF16:
         _lib.call("vlb_adamw_step_gbf16", _p(p, torch.float32), _p(g, BF16), _p(m, torch.float32), _p(v, torch.float32),
                   _p(p16, BF16), p.numel(), _p(state, torch.float32), float(grad_scale), _stream())
@@ -552,17 +579,36 @@ def adamw_step(p, g, m, v, p16, state, grad_scale=1.0):
               _p(p16, BF16), p.numel(), _p(state, torch.float32), float(grad_scale), _stream())
 
 
-def sgd_momentum_step(p, g, buf, lr, momentum=0.9, weight_decay=0.0, p16=None, sumsq=None, max_norm=0.0, grad_scale=1.0):
-    """torch.optim.SGD(lr, momentum, weight_decay) on flat fp32 tensors (vlb_sgd_momentum_step); sumsq: device scalar for the clip."""
+def sgd_momentum_step(p, g, buf, lr, momentum=0.9, weight_decay=0.0, p16=None, sumsq=None, max_norm=0.0, grad_scale=1.0, scaler=None,
+                      update_scaler=True):
+    """torch.optim.SGD(lr, momentum, weight_decay) on flat fp32 tensors (vlb_sgd_momentum_step); sumsq: device scalar for the clip.
+    scaler: dynamic loss scaler (see adamw_step); sumsq is then required."""
+    if scaler is not None:
+        _lib.call("vlb_sgd_momentum_step_scaled", _p(p, torch.float32), _p(g, torch.float32), _p(buf, torch.float32), _p(p16, BF16),
+                  p.numel(), float(lr), float(momentum), float(weight_decay), _p(sumsq, torch.float32), float(max_norm), float(grad_scale),
+                  _scaler_p(scaler), 1 if update_scaler else 0, _stream())
+        return
     _lib.call("vlb_sgd_momentum_step", _p(p, torch.float32), _p(g, torch.float32), _p(buf, torch.float32), _p(p16, BF16), p.numel(),
               float(lr), float(momentum), float(weight_decay), _p(sumsq, torch.float32), float(max_norm), float(grad_scale), _stream())
 
 
 LR_CONSTANT, LR_WARMUP_CONSTANT, LR_WARMUP_LINEAR = 0, 1, 2
+SCALER_FLOATS = 9      # include/vlbert_hip.h: VLB_SCALER_*
 
 
-def lr_schedule_step(state, kind, base_lr, warmup_steps=0, t_total=0):
-    """state[0] = base_lr * lambda(steps_taken + 1) on the device (common/nlp/bert/optimization.py:27-62)."""
+def _scaler_p(scaler):
+    if scaler.numel() < SCALER_FLOATS or not scaler.is_contiguous():
+        raise RuntimeError("loss scaler: expected %d contiguous fp32 values" % SCALER_FLOATS)
+    return _p(scaler, torch.float32)
+
+
+def lr_schedule_step(state, kind, base_lr, warmup_steps=0, t_total=0, scaler=None):
+    """state[0] = base_lr * lambda(steps_taken + 1) on the device (common/nlp/bert/optimization.py:27-62); with a loss scaler the
+    skipped steps count too (the reference's scheduler steps on every iteration)."""
+    if scaler is not None:
+        _lib.call("vlb_lr_schedule_step_scaled", _p(state, torch.float32), _scaler_p(scaler), int(kind), float(base_lr),
+                  float(warmup_steps), float(t_total), _stream())
+        return
     _lib.call("vlb_lr_schedule_step", _p(state, torch.float32), int(kind), float(base_lr), float(warmup_steps), float(t_total),
               _stream())
 
@@ -792,7 +838,12 @@ class ShardRanges:
         _lib.call("vlb_sumsq_ranges_det", _p(g), 1 if g.dtype == BF16 else 0, self.ranges.data_ptr(), self.starts.data_ptr(), self.n,
                   self.total_blocks, self.chunk, _p(partials, torch.float32), partials.numel(), _p(out, torch.float32), _stream())
 
-    def adamw(self, p, g, m, v, p16c, state, grad_scale=1.0):
+    def adamw(self, p, g, m, v, p16c, state, grad_scale=1.0, scaler=None):
+        if scaler is not None:
+            _lib.call("vlb_adamw_step_ranges_scaled", _p(p, torch.float32), _p(g), 1 if g.dtype == BF16 else 0, _p(m, torch.float32),
+                      _p(v, torch.float32), _p(p16c, BF16), self.ranges.data_ptr(), self.starts.data_ptr(), self.n, self.total_blocks,
+                      self.chunk, _p(state, torch.float32), _scaler_p(scaler), float(grad_scale), _stream())
+            return
         _lib.call("vlb_adamw_step_ranges", _p(p, torch.float32), _p(g), 1 if g.dtype == BF16 else 0, _p(m, torch.float32),
                   _p(v, torch.float32), _p(p16c, BF16), self.ranges.data_ptr(), self.starts.data_ptr(), self.n, self.total_blocks,
                   self.chunk, _p(state, torch.float32), float(grad_scale), _stream())

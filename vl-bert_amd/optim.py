@@ -56,14 +56,16 @@ def clip_grad_norm_(parameters, max_norm, optimizer, grad_scale=None):
     optimizer's parameters -- `parameters` is accepted for signature parity), kept on the device, and the step's kernel multiplies
     every gradient by min(1, max_norm / (norm + 1e-6)) as it reads it -- no pass over the gradients to rescale them, no host sync.
     grad_scale: an fp16 loss scale to divide out first (norm and clip are computed on the unscaled gradients).  Returns the total norm
-    (0-dim device tensor, unscaled).  The gradients themselves are left as they are."""
+    (0-dim device tensor, unscaled).  The gradients themselves are left as they are.  With a dynamic loss scaler on the optimizer
+    (`loss_scaler=`) the device scale is divided out as well -- on the device, without a host round trip."""
     if not isinstance(optimizer, (FusedAdamW, FusedSGD)):
         raise TypeError("clip_grad_norm_ fuses into FusedAdamW / FusedSGD")
     if grad_scale is not None:
         optimizer.grad_scale = float(grad_scale)
     total = optimizer._sumsq_all()
     optimizer._clip = (float(max_norm), total)
-    return total.sqrt() * optimizer.grad_scale
+    norm = total.sqrt() * optimizer.grad_scale
+    return norm / optimizer.loss_scaler.scale if optimizer.loss_scaler is not None else norm
 
 
 class _FlatStateMixin:
@@ -74,6 +76,17 @@ class _FlatStateMixin:
 
     grad_scale = 1.0      # multiplies every gradient inside the step kernel (1 / loss scale of an fp16 run; 1 / world of a DP sum)
     _clip = None          # (max_norm, device sum of squares) left by clip_grad_norm_ for the next step()
+    # loss_scale.LossScaler (dynamic loss scale of an fp16 run; the object whose .scale multiplied the loss): step() then ALWAYS takes the
+    # squared gradient norm, clip or no clip -- it carries the overflow decision -- and runs the scaler forms of the kernels: the device
+    # scale is divided out next to grad_scale, a step with a non-finite norm leaves parameters and optimizer state untouched, and the
+    # scaler's rule (halve / count / grow) is applied once, after the last flat run.
+    loss_scaler = None
+
+    def _scaler_setup(self, clip):
+        """-> (clip or (0.0, fresh squared norm), number of flat runs of this step)"""
+        if clip is None:
+            clip = (0.0, self._sumsq_all())
+        return clip, sum(len(self._group_runs(gi, g, type(self).__name__)[1]) for gi, g in enumerate(self.param_groups))
 
     def _group_runs(self, gi, group, who):
         ps = [p for p in group["params"] if p.grad is not None]
@@ -139,13 +152,20 @@ def _check_fp32_gpu(ps, who):
 
 
 class FusedAdamW(_FlatStateMixin, torch.optim.Optimizer):
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-6, weight_decay=0.0, correct_bias=True):
+    """loss_scaler: see _FlatStateMixin.  With it the per-parameter state['step'] counts the steps ATTEMPTED (the host never learns
+    which were skipped); the device-resident count of each flat run, which the bias correction uses, only counts the steps taken.
+    That device count is seeded from state['step'] whenever a run's buffers are (re-)created -- the first step, the first step after
+    load_state_dict(), re-allocated gradients -- so after such a point the bias correction is ahead by the steps skipped until then
+    (for Adam's 1 - beta^t factors, which tend to 1, a difference that fades with t)."""
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-6, weight_decay=0.0, correct_bias=True, loss_scaler=None):
         if lr < 0.0 or eps < 0.0 or not (0.0 <= betas[0] < 1.0) or not (0.0 <= betas[1] < 1.0):
             raise ValueError("invalid hyper-parameter")          # the reference's checks (optimization.py:117-124)
         if not correct_bias:
             raise NotImplementedError("FusedAdamW implements correct_bias=True (every shipped configuration)")
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, correct_bias=correct_bias))
         self._runs = {}
+        self.loss_scaler = loss_scaler
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -154,6 +174,9 @@ class FusedAdamW(_FlatStateMixin, torch.optim.Optimizer):
             with torch.enable_grad():
                 loss = closure()
         clip, self._clip = self._clip, None
+        scaler, left = self.loss_scaler, 0
+        if scaler is not None:
+            clip, left = self._scaler_setup(clip)
         for gi, group in enumerate(self.param_groups):
             ps, runs = self._group_runs(gi, group, "FusedAdamW")
             hyper = (float(group["lr"]), float(group["betas"][0]), float(group["betas"][1]), float(group["eps"]), float(group["weight_decay"]))
@@ -189,7 +212,12 @@ class FusedAdamW(_FlatStateMixin, torch.optim.Optimizer):
                 elif float(st["hyper_clip"] if "hyper_clip" in st else 0.0) != 0.0:
                     st["dev"][6:7].zero_()
                 st["hyper_clip"] = clip[0] if clip is not None else 0.0
-                ops.adamw_step(pf, gf, st["flat_m"], st["flat_v"], None, st["dev"], grad_scale=self.grad_scale)      # (advances the run's step count)
+                if scaler is not None:
+                    left -= 1
+                    ops.adamw_step(pf, gf, st["flat_m"], st["flat_v"], None, st["dev"], grad_scale=self.grad_scale, scaler=scaler.state,
+                                   update_scaler=left == 0)
+                else:
+                    ops.adamw_step(pf, gf, st["flat_m"], st["flat_v"], None, st["dev"], grad_scale=self.grad_scale)      # (advances the run's step count)
                 for p in ps[a:b]:
                     self.state[p]["step"] += 1
                     torch.autograd.graph.increment_version(p)
@@ -197,13 +225,14 @@ class FusedAdamW(_FlatStateMixin, torch.optim.Optimizer):
 
 
 class FusedSGD(_FlatStateMixin, torch.optim.Optimizer):
-    def __init__(self, params, lr=1e-3, momentum=0.0, dampening=0.0, weight_decay=0.0, nesterov=False):
+    def __init__(self, params, lr=1e-3, momentum=0.0, dampening=0.0, weight_decay=0.0, nesterov=False, loss_scaler=None):
         if dampening != 0.0 or nesterov:
             raise NotImplementedError("FusedSGD implements dampening = 0, nesterov = False (the reference's configuration)")
         if lr < 0.0 or momentum < 0.0 or weight_decay < 0.0:
             raise ValueError("negative hyper-parameter")
         super().__init__(params, dict(lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay, nesterov=nesterov))
         self._runs = {}
+        self.loss_scaler = loss_scaler
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -212,6 +241,9 @@ class FusedSGD(_FlatStateMixin, torch.optim.Optimizer):
             with torch.enable_grad():
                 loss = closure()
         clip, self._clip = self._clip, None
+        scaler, left = self.loss_scaler, 0
+        if scaler is not None:
+            clip, left = self._scaler_setup(clip)
         for gi, group in enumerate(self.param_groups):
             ps, runs = self._group_runs(gi, group, "FusedSGD")
             for a, b, n in runs:
@@ -228,9 +260,11 @@ class FusedSGD(_FlatStateMixin, torch.optim.Optimizer):
                         self.state[p]["momentum_buffer"] = view
                 pf = first.data.as_strided((n,), (1,), first.storage_offset())
                 gf = first.grad.as_strided((n,), (1,), first.grad.storage_offset())
+                left -= 1
                 ops.sgd_momentum_step(pf, gf, st["flat_buffer"], group["lr"], group["momentum"], group["weight_decay"],
                                       sumsq=clip[1] if clip is not None else None, max_norm=clip[0] if clip is not None else 0.0,
-                                      grad_scale=self.grad_scale)
+                                      grad_scale=self.grad_scale, scaler=scaler.state if scaler is not None else None,
+                                      update_scaler=left == 0)
                 for p in ps[a:b]:      # the kernel wrote through raw pointers: tell autograd (the module mirrors key their bf16 /
                     torch.autograd.graph.increment_version(p)      # transposed weight copies on the parameters' version counters)
         return loss

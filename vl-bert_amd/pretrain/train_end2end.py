@@ -110,7 +110,17 @@ def resolve(config, world, args):
                 e2e=not config.NETWORK.IMAGE_FEAT_PRECOMPUTED, image_size=tuple(config.SCALES), multitask=multitask,
                 fp16_requested=bool(tr.FP16), seed=int(config.RNG_SEED),
                 compute=(("fp16" if tr.FP16 else "fp32") if args.compute == "cfg" else args.compute),
-                loss_scale=(float(tr.FP16_LOSS_SCALE) if isinstance(tr.get("FP16_LOSS_SCALE", None), (int, float)) else None))
+                loss_scale=_loss_scale_of(tr.get("FP16_LOSS_SCALE", None)))
+
+
+def _loss_scale_of(value):
+    """TRAIN.FP16_LOSS_SCALE the reference's way (pretrain/function/train.py:345-352): a number = static, 'dynamic' = Apex's dynamic
+    scaler (the device-side one of loss_scale.py); anything else: the build's default."""
+    if isinstance(value, (int, float)):
+        return float(value)
+    if isinstance(value, str) and value.strip().lower() == "dynamic":
+        return "dynamic"
+    return None
 
 
 def _names_val_set(ds):
@@ -276,7 +286,8 @@ def main(argv=None):
     if rank == 0:
         print("train_end2end: %s | %d GPU(s) x batch %d | lr %.3e wd %.1e clip %.1f | schedule %s warmup %d t_total %d%s" %
               (config.MODULE, world, B + B_aux, r["lr"], r["weight_decay"], r["clip_grad_norm"], r["lr_schedule"], r["warmup_steps"], r["t_total"],
-               " | compute %s%s" % (r["compute"], " (loss scale %g)" % eng.loss_scale if eng.loss_scale != 1.0 else "")), flush=True)
+               " | compute %s%s" % (r["compute"], (" (loss scale dynamic (%s))" % eng.scaler.spec.describe()) if eng.scaler is not None
+                                    else (" (loss scale %g)" % eng.loss_scale if eng.loss_scale != 1.0 else ""))), flush=True)
     # checkpoints in the reference's format + resume (common/callbacks/epoch_end_callbacks/checkpoint.py, common/utils/load.py:20-54)
     ckpt = importlib.import_module(pkg + ".common.checkpoint")
     spe = max(1, int(r["steps_per_epoch"] // r["accumulate"]))           # optimizer steps per epoch
@@ -392,9 +403,11 @@ def main(argv=None):
                     print("epoch %d done: checkpoint %s" % (epoch, path), flush=True)
         if (step + 1 - first_step) % max(1, min(int(config.LOG_FREQUENT), args.steps)) == 0 or step + 1 == first_step + args.steps:
             lv = eng.loss_values()          # host sync, like the reference's Speedometer + metric readout
+            ss = eng.scaler_state()         # (dynamic loss scale: read where the loop synchronises anyway)
             if rank == 0:
-                print("step %d  lr %.3e  loss %.4f (mlm %.4f mvrc %.4f)  %.1f samples/s" %
-                      (step + 1, float(eng.adam[0]), lv["loss"], lv["mlm_loss"], lv["mvrc_loss"], seen / (time.time() - t0)), flush=True)
+                print("step %d  lr %.3e  loss %.4f (mlm %.4f mvrc %.4f)  %.1f samples/s%s" %
+                      (step + 1, float(eng.adam[0]), lv["loss"], lv["mlm_loss"], lv["mvrc_loss"], seen / (time.time() - t0),
+                       "  loss scale %g (%d skipped)" % (ss["scale"], ss["skipped_total"]) if ss is not None else ""), flush=True)
         if monitor is not None and (step + 1) % spe == 0:      # after the step's log line: validation overwrites the loss slots
             monitor((step + 1) // spe - 1, eng)
             eng.loss_values()               # (raises if a validation batch overflowed the MLM compaction capacity)
