@@ -141,7 +141,9 @@ int vlb_ln_param_finalize_batch(int n, const float* const* ws, const int* nslab,
 /* ---- BertSelfAttention core (modeling.py:300-316) --------------------------------------------
  * qkv [B*S, 3H] bf16 (q | k | v, head h at columns h*64), mask [B,S] fp32 (1 attend / 0 -> -10000),
  * ctx [B*S, H] bf16, lse [B, heads, S] fp32 (row log-sum-exp, saved for backward).
- * S <= 128, head dim 64.  bwd recomputes the probabilities; writes dqkv [B*S, 3H] bf16. */
+ * 1 <= S <= 512, head dim 64, B * heads * S * S < 2^32 (dropout element index); S <= 256 runs the whole-sequence kernels of
+ * csrc/attention.hip, 257..512 the streaming kernels of csrc/attention_long.hip; a longer S is refused (VLB_ERR_ARG).
+ * bwd recomputes the probabilities; writes dqkv [B*S, 3H] bf16. */
 int vlb_attention_fwd(const void* qkv, const float* mask, void* ctx, float* lse, int B, int S, int H, int nh,
                       float drop_p, const uint32_t* seed, uint32_t tag, vlb_stream_t stream);
 int vlb_attention_bwd(const void* qkv, const float* mask, const void* ctx, const float* lse, const void* dctx,

@@ -27,7 +27,8 @@ from .. import ops
 from .heads import cfg_get as _get
 
 _PREFIX = "vlbert."
-_MAX_S = 256      # longest packed sequence the attention kernels cover (attention.hip: ATT_SP_MAX)
+_SHORT_S = 256    # longest packed sequence of the whole-sequence attention kernels (attention.hip: ATT_SP_MAX)
+_MAX_S = 512      # longest packed sequence the attention kernels cover (attention_long.hip: ATT_LONG_MAX)
 
 
 def shape_buckets():
@@ -42,7 +43,10 @@ def shape_buckets():
 def bucketed(T, R):
     bt, br, _ = shape_buckets()
     Tp, Rp = (T + bt - 1) // bt * bt, (R + br - 1) // br * br
-    if Tp + Rp + 1 > _MAX_S:          # rounding must not push a sequence that fits over the kernels' limit
+    # rounding must not push a sequence over a limit it fits: neither from the whole-sequence kernels (<= 256 positions) onto the
+    # streaming ones (257..512: seven products per tile pair instead of five), nor over the longest sequence the kernels cover
+    limit = _SHORT_S if T + R + 1 <= _SHORT_S else _MAX_S
+    if Tp + Rp + 1 > limit:
         Tp, Rp = T, R
     return Tp, Rp
 
@@ -186,7 +190,7 @@ class VisualLinguisticBert(nn.Module):
                       lambda: _engine.PretrainEngine(self.cfg, B, T, R, device=str(self.device_), flat=self.flat, core=True,
                                                      core_heads=self.WITH_HEADS, core_sequence=sequence,
                                                      seed=ops.rank_seed(1234) // 2,         # per-rank dropout stream
-                                                     encoder_fp32=self.fp32_encoder))
+                                                     encoder_fp32=self.fp32_encoder, max_seq=_MAX_S))
         eng._dp_hook = getattr(self, "_dp_hook", None)          # parallel.DistributedDataParallel: gradient buckets leave from backward
         version = self.flat.master._version
         if getattr(eng, "_synced_version", None) != version:
@@ -236,6 +240,9 @@ class VisualLinguisticBert(nn.Module):
         returned WITHOUT autograd history (train with the default call forms)."""
         B, T = text_input_ids.shape
         R = object_vl_embeddings.shape[1]
+        if T + R + 1 > _SHORT_S:
+            raise ValueError("output_all_encoded_layers / output_attention_probs run on the fp32 encoder, which handles sequences of at "
+                             "most %d positions (got %d+%d+1); the default call forms go up to %d" % (_SHORT_S, T, R, _MAX_S))
         key = ("inspect", B, T, R)
         eng = lru_get(self._engines, key, lambda: _engine.PretrainEngine(self.cfg, B, T, R, device=str(self.device_), flat=self.flat, core=True,
                                                                          core_heads=False, core_sequence=True,

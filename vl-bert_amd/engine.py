@@ -28,7 +28,8 @@ from . import ops
 from .side_streams import SideStreams
 
 F32 = torch.float32
-VIS_DIM = 2048            # hard-coded in the reference (common/fast_rcnn.py:107, resnet_vlbert_for_pretraining.py:25)
+MAX_SEQ = 512           # longest packed sequence of the fused attention kernels (csrc/attention_common.h: ATT_LONG_MAX)
+VIS_DIM = 2048          # hard-coded in the reference (common/fast_rcnn.py:107, resnet_vlbert_for_pretraining.py:25)
 TAG_EMBED, TAG_DOWNSAMPLE = 1000, 1001
 
 
@@ -167,8 +168,14 @@ class PretrainEngine:
     def __init__(self, cfg, B, T, R, device="cuda:0", train=True, lr=1e-4, weight_decay=1e-4, max_grad_norm=10.0,
                  betas=(0.9, 0.999), eps=1e-6, seed=1234, grad_accum=1, process_group=None, keep_logits=False, flat=None,
                  B_aux=0, core=False, core_heads=True, core_sequence=False, lr_schedule=None, warmup_steps=0, t_total=0,
-                 image_size=None, dp_mode="default", dp_wire="default", loss_scale=None, encoder_fp32=False):
+                 image_size=None, dp_mode="default", dp_wire="default", loss_scale=None, encoder_fp32=False, max_seq=256):
         cfg.validate()
+        # max_seq: the longest packed sequence S = T + R + 1 this engine may be built for, 256..512.  Up to 256 positions attention runs
+        # the whole-sequence kernels (csrc/attention.hip), 257..512 the streaming ones (csrc/attention_long.hip: seven products per tile
+        # pair instead of five).  The default stays 256 so that a caller opts into the long path knowingly.
+        if not (isinstance(max_seq, int) and 256 <= max_seq <= MAX_SEQ):
+            raise ValueError("max_seq must be an integer in 256..%d (got %r)" % (MAX_SEQ, max_seq))
+        self.max_seq = max_seq
         if cfg.e2e and (core or image_size is None):
             raise ValueError("e2e needs image_size=(H, W) and a pretraining wrapper (plain or multitask; not the core module mode)")
         # lr_schedule: None (host sets lr) | "constant" | "warmup_constant" | "triangle" (WarmupLinearSchedule,
@@ -216,8 +223,11 @@ class PretrainEngine:
             raise ValueError("B_aux > 0 needs ModelConfig(multitask=True)")
         self.Bt = B + B_aux
         self.S = T + R + 1
-        if self.S > 256:
-            raise ValueError("sequence %d+%d+1 > 256: the fused attention kernels handle S <= 256" % (T, R))
+        if self.S > MAX_SEQ:
+            raise ValueError("sequence %d+%d+1 > %d: the fused attention kernels handle S <= %d" % (T, R, MAX_SEQ, MAX_SEQ))
+        if self.S > max_seq:
+            raise ValueError("sequence %d+%d+1 > max_seq=%d: build the engine with max_seq up to %d for longer sequences"
+                             % (T, R, max_seq, MAX_SEQ))
         self.dev = torch.device(device)
         self.train = train
         self.grad_accum = grad_accum

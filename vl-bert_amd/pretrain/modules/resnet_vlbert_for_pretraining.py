@@ -212,7 +212,8 @@ class ResNetVLBERTForPretraining(nn.Module):
     def _engine_for(self, B, T, R, B_aux=0, image_size=None):
         eng = lru_get(self._engines, (B, T, R, B_aux, image_size),
                       lambda: _engine.PretrainEngine(self.cfg, B, T, R, device=str(self.device_), keep_logits=True, flat=self.flat,
-                                                     B_aux=B_aux, image_size=image_size, seed=ops.rank_seed(1234) // 2))   # per-rank dropout stream
+                                                     B_aux=B_aux, image_size=image_size, seed=ops.rank_seed(1234) // 2,   # per-rank dropout stream
+                                                     max_seq=_engine.MAX_SEQ))
         if self.e2e and getattr(eng, "_buffers_version", None) != self._buffers_version:
             eng.vision.load_state_dict(self._vision_buffers, strict=False)      # BatchNorm tensors + frozen stages (trainables live in flat)
             eng._buffers_version = self._buffers_version

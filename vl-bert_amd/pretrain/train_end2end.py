@@ -264,7 +264,7 @@ def main(argv=None):
                                 lr_schedule=r["lr_schedule"], warmup_steps=r["warmup_steps"], t_total=max(r["t_total"], r["warmup_steps"] + 1),
                                 image_size=r["image_size"] if r["e2e"] else None, grad_accum=r["accumulate"],
                                 encoder_fp32=r["compute"] == "fp32", dp_mode="allreduce" if r["compute"] == "fp32" else "default",
-                                loss_scale=r["loss_scale"] if r["compute"] == "fp16" else None)
+                                loss_scale=r["loss_scale"] if r["compute"] == "fp16" else None, max_seq=engine.MAX_SEQ)
     eng.init_random(seed=r["seed"], visual_ln_init=float(g("visual_scale_object_init", 0.0)))
     # NETWORK.PARTIAL_PRETRAIN (+ _PREFIX_CHANGES): start from a pre-trained checkpoint's matching tensors (pretrain/function/train.py:297-313,
     # common/utils/load.py:57-81).  Empty in every shipped pre-training YAML; a configured file that does not exist is reported and skipped

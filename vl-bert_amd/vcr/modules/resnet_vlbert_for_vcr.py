@@ -9,7 +9,7 @@ Composition, as in the reference (:226-399):
   per answer choice `[CLS] q [SEP] a [SEP]`, each token's visual embedding = the object its tag points at (index plumbing in
   torch, :116-167), object linguistic embedding = row clamp(class) of the 1-row / 81-row table (:303-308)
   `TimeDistributed` (common/nlp/time_distributed.py): the C answer choices fold into the batch -- the SAME engine rows, B*C
-  sequences of up to 256 positions -- around the VisualLinguisticBert mirror with the pooler
+  sequences of up to 512 positions (beyond 256 on the streaming attention kernels) -- around the VisualLinguisticBert mirror with the pooler
   `final_mlp` on the pooled [CLS] -> logits [B,C]; sigmoid BCE with the positive-class weight (:344-356) or softmax CE (:358)
   ENABLE_CNN_REG_LOSS + CNN_LOSS_TOP (the shipped cfgs/vcr/*.yaml): every valid object's final hidden state -> transform
   (Linear + GELU) -> Dropout -> Linear(H, 81) -> CE against its detector class, one autograd node on the library (bf16 GEMMs with
