@@ -91,8 +91,10 @@ def test_grounding_kernels_match_torch(B, R, R0, H, p):
     du, dw2, db2 = outs[0]
     s = (0.37 * dlogit.double())[:, None]
     du_ref = s * w2.double()[None, :] * (mask * scale).double() * dg.double()
-    ulp = 2.0 ** -7 if act_dtype() == torch.bfloat16 else 2.0 ** -10
-    assert ((du.double() - du_ref).abs() <= du_ref.abs() * ulp + 1e-30).all()
+    fi = torch.finfo(act_dtype())
+    ulp = fi.eps                                           # 2^-7 (bfloat16) | 2^-10 (fp16)
+    sub = max(1e-30, fi.tiny * fi.eps)                     # 1 ulp of a subnormal result: 2^-24 in fp16 (|du| here goes below 2^-14)
+    assert ((du.double() - du_ref).abs() <= du_ref.abs() * ulp + sub).all()
     dw2_ref = (s * x1.double()).sum(0)
     assert float((dw2.double() - dw2_ref).abs().max()) <= 1e-5 * float(dw2_ref.abs().max())
     assert abs(float(db2) - float(s.sum())) <= 1e-5 * max(abs(float(s.sum())), 1e-6)

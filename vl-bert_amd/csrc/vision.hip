@@ -628,11 +628,11 @@ __global__ __launch_bounds__(128) void roi_axis_tables_kernel(const float* __res
   }
 }
 
-__device__ __forceinline__ void fma4_bf16(float (&acc)[4], float w, const uint2& v) {
-  acc[0] += w * __uint_as_float(v.x << 16);
-  acc[1] += w * __uint_as_float(v.x & 0xFFFF0000u);
-  acc[2] += w * __uint_as_float(v.y << 16);
-  acc[3] += w * __uint_as_float(v.y & 0xFFFF0000u);
+__device__ __forceinline__ void fma4_h16(float (&acc)[4], float w, const uint2& v) {      // 4 elements of the build's 16-bit type
+  acc[0] += w * bflo(v.x);
+  acc[1] += w * bfhi(v.x);
+  acc[2] += w * bflo(v.y);
+  acc[3] += w * bfhi(v.y);
 }
 
 __global__ __launch_bounds__(256) void roi_align_nhwc_bwd_gather_kernel(const bf16_t* __restrict__ dout, const float* __restrict__ Wy,
@@ -677,10 +677,10 @@ __global__ __launch_bounds__(256) void roi_align_nhwc_bwd_gather_kernel(const bf
             const uint2 v01 = *(const uint2*)(dk + ((long)ph * pw_n + pw1) * C);
             const uint2 v10 = *(const uint2*)(dk + ((long)ph1 * pw_n + pw) * C);
             const uint2 v11 = *(const uint2*)(dk + ((long)ph1 * pw_n + pw1) * C);
-            fma4_bf16(acc, wy0 * wx0, v00);
-            fma4_bf16(acc, wy0 * wx1, v01);
-            fma4_bf16(acc, wy1 * wx0, v10);
-            fma4_bf16(acc, wy1 * wx1, v11);
+            fma4_h16(acc, wy0 * wx0, v00);
+            fma4_h16(acc, wy0 * wx1, v01);
+            fma4_h16(acc, wy1 * wx0, v10);
+            fma4_h16(acc, wy1 * wx1, v11);
           }
         }
       }
@@ -691,10 +691,10 @@ __global__ __launch_bounds__(256) void roi_align_nhwc_bwd_gather_kernel(const bf
     if (out_bf) {
       if (act) {                                      // gradient through the ReLU that produced `act` (vlb_relu_mask_cast)
         const uint2 a = *(const uint2*)(act + o);
-        if (!(__uint_as_float(a.x << 16) > 0.f)) acc[0] = 0.f;
-        if (!(__uint_as_float(a.x & 0xFFFF0000u) > 0.f)) acc[1] = 0.f;
-        if (!(__uint_as_float(a.y << 16) > 0.f)) acc[2] = 0.f;
-        if (!(__uint_as_float(a.y & 0xFFFF0000u) > 0.f)) acc[3] = 0.f;
+        if (!(bflo(a.x) > 0.f)) acc[0] = 0.f;
+        if (!(bfhi(a.x) > 0.f)) acc[1] = 0.f;
+        if (!(bflo(a.y) > 0.f)) acc[2] = 0.f;
+        if (!(bfhi(a.y) > 0.f)) acc[3] = 0.f;
       }
       uint2 r;
       r.x = (unsigned)f2bf(acc[0]) | ((unsigned)f2bf(acc[1]) << 16);
