@@ -149,6 +149,14 @@ int vlb_attention_fwd(const void* qkv, const float* mask, void* ctx, float* lse,
 int vlb_attention_bwd(const void* qkv, const float* mask, const void* ctx, const float* lse, const void* dctx,
                       void* dqkv, int B, int S, int H, int nh, float drop_p, const uint32_t* seed, uint32_t tag,
                       vlb_stream_t stream);
+/* The probabilities of that forward, written out for inspection (csrc/attention_probs.hip): qkv, mask and lse exactly as
+ * vlb_attention_fwd reads and writes them; probs fp32 [B, heads, n, ldp] (row stride ldp floats, head stride n * ldp):
+ * probs[b,h,q,k] = exp(Q.K / 8 + (1 - mask[b,k]) * -10000 - lse[b,h,q]) for q < n, k < S and 0 for S <= k < ldp; nothing else is
+ * written.  1 <= n <= S <= 512, n <= ldp <= 512, ldp % 4 == 0, probs 16-byte aligned (callers pass n rounded up to 32: rows start on a 128-byte line).
+ * drop_p > 0: times keep / (1 - p) with the forward's masks under the same (seed, tag) -- the fp32 product, which the forward
+ * rounds to the 16-bit type before P.V.  Anything else is refused (VLB_ERR_ARG) before any launch. */
+int vlb_attention_probs(const void* qkv, const float* mask, const float* lse, float* probs, int B, int S, int H, int nh, int n,
+                        int ldp, float drop_p, const uint32_t* seed, uint32_t tag, vlb_stream_t stream);
 
 /* ---- embedding side (common/visual_linguistic_bert.py:173-241, common/fast_rcnn.py:136-187) ---
  * vlb_seq_layout: masks (uint8 [B,T], [B,R]) -> code [B,S] (kind<<16 | src index; kind 0 pad,

@@ -49,6 +49,7 @@ _SIGS = {
     "vlb_gemm_nt_bf16_ex": "plplpliiipiplplplpppifpuiis",
     "vlb_attention_fwd": "ppppiiiifpus",
     "vlb_attention_bwd": "ppppppiiiifpus",
+    "vlb_attention_probs": "ppppiiiiiifpus",
     "vlb_seq_layout": "ppiiiipppppps",
     "vlb_obj_prep_fwd": "plplpppiifpus",
     "vlb_masked_colsum": "plpiipfpuuus",

@@ -98,8 +98,11 @@ class _CoreFn(torch.autograd.Function):
 class VisualLinguisticBert(nn.Module):
     WITH_HEADS = False
 
-    def __init__(self, config, language_pretrained_model_path=None, device=None):
+    def __init__(self, config, language_pretrained_model_path=None, device=None, inspect_fused=False):
         super().__init__()
+        # inspection call forms (output_all_encoded_layers / output_attention_probs) on the fused 16-bit path at EVERY length, not only
+        # beyond the fp32 encoder's 256 positions (_inspect_fused); VLB_INSPECT_FUSED=1 turns it on from outside
+        self.inspect_fused = bool(inspect_fused) or os.environ.get("VLB_INSPECT_FUSED", "0") == "1"
         if _get(config, "visual_size", _get(config, "hidden_size")) != _get(config, "hidden_size"):
             raise NotImplementedError("visual_size != hidden_size (visual_1x1 projections) is not supported")
         if not _get(config, "visual_ln", True):
@@ -240,6 +243,9 @@ class VisualLinguisticBert(nn.Module):
         returned WITHOUT autograd history (train with the default call forms)."""
         B, T = text_input_ids.shape
         R = object_vl_embeddings.shape[1]
+        if (self.inspect_fused or T + R + 1 > _SHORT_S) and not self.fp32_encoder:
+            return self._inspect_fused(text_input_ids, text_token_type_ids, text_visual_embeddings, text_mask, object_vl_embeddings,
+                                       object_mask, all_layers, separately, probs)
         if T + R + 1 > _SHORT_S:
             raise ValueError("output_all_encoded_layers / output_attention_probs run on the fp32 encoder, which handles sequences of at "
                              "most %d positions (got %d+%d+1); the default call forms go up to %d" % (_SHORT_S, T, R, _MAX_S))
@@ -274,6 +280,45 @@ class VisualLinguisticBert(nn.Module):
             if not all_layers:
                 texts, objs = texts[0], objs[0]
             return (texts, objs, pooled, out_probs) if probs else (texts, objs, pooled)
+        enc_out = layers if all_layers else layers[0]
+        return (enc_out, pooled, out_probs) if probs else (enc_out, pooled)
+
+    @torch.no_grad()
+    def _inspect_fused(self, text_input_ids, text_token_type_ids, text_visual_embeddings, text_mask, object_vl_embeddings,
+                       object_mask, all_layers, separately, probs):
+        """The same call forms on the fused 16-bit path (sequences of 257..512 positions, or `inspect_fused` at any length): the
+        forward the model is trained and deployed with, then the engine's encoded_layers() / attention_probs(), which read what that
+        forward left behind (QKV, lse, X per layer; ../csrc/attention_probs.hip).  Return tuples, trimming to the batch's longest
+        packed sequence, object placement and the no-autograd contract are _inspect's."""
+        B, T = text_input_ids.shape
+        R = object_vl_embeddings.shape[1]
+        key = ("inspect_fused", B, T, R)
+        eng = lru_get(self._engines, key, lambda: _engine.PretrainEngine(self.cfg, B, T, R, device=str(self.device_), flat=self.flat, core=True,
+                                                                         core_heads=False, core_sequence=True,
+                                                                         seed=ops.rank_seed(1234) // 2, max_seq=_MAX_S))
+        version = self.flat.master._version
+        if getattr(eng, "_synced_version", None) != version:
+            eng.sync_weights()
+            eng._synced_version = version
+        eng._weights_dirty = False
+        eng.set_core_inputs(text_input_ids, text_token_type_ids, text_visual_embeddings, text_mask, object_vl_embeddings, object_mask)
+        eng.mirror_pre_forward(self.training)
+        eng.forward_core(train=self.training)
+        H, S, L = self.cfg.hidden_size, eng.S, self.cfg.num_hidden_layers
+        n = eng.longest_sequence()
+        which = list(range(L)) if all_layers else [L - 1]
+        pooled = eng.pooled.float().clone() if self.with_pooler else None
+        out_probs = eng.attention_probs(n=n) if probs else None
+        if separately:
+            rows = eng.lay["obj_rows"][:B].long()                            # packed row of object r of sample b, -1 = no object
+            texts, objs = [], []
+            for full in eng.encoded_layers(which, n=S):
+                texts.append(full[:, :T].clone())
+                objs.append(full.reshape(B * S, H)[rows.clamp(min=0).view(-1)].view(B, R, H) * (rows >= 0).unsqueeze(-1))
+            if not all_layers:
+                texts, objs = texts[0], objs[0]
+            return (texts, objs, pooled, out_probs) if probs else (texts, objs, pooled)
+        layers = eng.encoded_layers(which, n=n)
         enc_out = layers if all_layers else layers[0]
         return (enc_out, pooled, out_probs) if probs else (enc_out, pooled)
 

@@ -288,6 +288,8 @@ class PretrainEngine:
         # odd (the advance kernel keeps it odd) and injective in `seed`: `seed | 1` collapsed ranks 2k / 2k+1 of a
         # seed = RNG_SEED + rank launch onto one dropout stream
         self.seed = torch.tensor([((seed * 2 + 1) & 0x7FFFFFFF)], dtype=torch.int32, device=d)
+        self._seed_prev = torch.zeros_like(self.seed)      # the seed of the last forward once a step has advanced it (_advance_seed)
+        self._last_p_a, self._seed_moved = None, False
         self.adam = torch.tensor([lr, betas[0], betas[1], eps, weight_decay, 0.0, max_grad_norm, 0.0], dtype=F32, device=d)
         self.hyper = dict(betas=(float(betas[0]), float(betas[1])), eps=float(eps), weight_decay=float(weight_decay))   # as given (checkpoints)
         if self._scaler_spec is not None:
@@ -731,6 +733,7 @@ class PretrainEngine:
         # --- encoder -------------------------------------------------------------------------------------
         mask = self.lay["attn_mask"]
         stale = self._gather_pending
+        self._last_p_a, self._seed_moved = p_a, False      # attention_probs() recomputes this forward's dropout masks
         if self.enc32 is not None:
             self.enc32.forward(p_h, p_a)
         for l in range(L if self.enc32 is None else 0):
@@ -1150,6 +1153,45 @@ class PretrainEngine:
         """Last encoder layer as the packed [B, S, H] sequence (text || objects || END || padding), bf16 view."""
         return self.X[self.cfg.num_hidden_layers].view(self.Bt, self.S, self.cfg.hidden_size)
 
+    # ------------------------------------------------------------------------------------------
+    # inspection of the last forward (16-bit encoder): no per-layer state beyond what the forward leaves behind anyway
+    # ------------------------------------------------------------------------------------------
+    def longest_sequence(self):
+        """The batch's longest packed sequence, text + objects + END (common/visual_linguistic_bert.py:202; one host synchronisation)."""
+        return int((self.lay["text_len"] + self.lay["nobj"]).max()) + 1
+
+    def _inspect_args(self, what, layers, n):
+        if self.enc32 is not None:
+            raise ValueError("%s() reads the 16-bit encoder's buffers; an encoder_fp32 engine keeps fp32 ones: read enc32.P "
+                             "(enc32.Pd after dropout) / enc32.X" % what)
+        if self._last_p_a is None:
+            raise RuntimeError("%s() needs a forward first" % what)
+        L = self.cfg.num_hidden_layers
+        layers = list(range(L)) if layers is None else [int(l) for l in ([layers] if isinstance(layers, int) else layers)]
+        if any(l < 0 or l >= L for l in layers):
+            raise ValueError("%s(): layers must lie in 0..%d (got %r)" % (what, L - 1, layers))
+        n = self.longest_sequence() if n is None else int(n)
+        if not 1 <= n <= self.S:
+            raise ValueError("%s(): n=%d outside 1..S=%d" % (what, n, self.S))
+        return layers, n
+
+    def attention_probs(self, layers=None, n=None):
+        """Attention probabilities of the last forward (full step, eval_step or core), recomputed from the QKV and lse it left behind
+        (csrc/attention_probs.hip): a list of fp32 [Bt, heads, n, n], one per layer in `layers` (default: all).  With the dropout
+        probability, seed and tag of that forward: after a training-mode forward these are the probabilities AFTER their dropout, what
+        the reference returns (modeling.py:311-316) -- also once optimizer_step() has advanced the seed: the forward's value is kept.  n defaults to the batch's longest packed sequence.  Each layer's buffer is
+        allocated by the call; ask for one layer at a time where all of them together would not fit."""
+        layers, n = self._inspect_args("attention_probs", layers, n)
+        cfg = self.cfg
+        seed = self._seed_prev if self._seed_moved else self.seed      # optimizer_step has moved on: the forward's value was kept
+        return [ops.attention_probs(self.QKV[l], self.lay["attn_mask"], self.LSE[l], self.Bt, self.S, cfg.hidden_size,
+                                    cfg.num_attention_heads, n=n, drop_p=self._last_p_a, seed=seed, tag=l * 8 + 0) for l in layers]
+
+    def encoded_layers(self, layers=None, n=None):
+        """Outputs of the encoder layers of the last forward: fp32 copies of X[l + 1] as [Bt, n, H], one per layer in `layers`."""
+        layers, n = self._inspect_args("encoded_layers", layers, n)
+        return [self.X[l + 1].view(self.Bt, self.S, self.cfg.hidden_size)[:, :n].float() for l in layers]
+
     def backward_core_sequence(self, d_seq, d_pooled=None, train=None):
         """core_sequence=True: d(sequence_output) [B, <=S, H] (rows beyond the given length are zero) -> input gradients."""
         H = self.cfg.hidden_size
@@ -1249,7 +1291,7 @@ class PretrainEngine:
             self.buckets.gather_params(self.P.w16, self.wshard, master=self.P.master, vision_master=self.vision is not None)
             self._wT_stale = self._gather_pending = True
             self._vision_stale = self.vision is not None
-            ops.rng_advance(self.seed)
+            self._advance_seed()
             return
         # data parallel: the reduced gradient is read where the exchange left it (the bf16 wire image by default, parallel.py)
         grad = self.buckets.reduced if self.buckets is not None else self.P.grad
@@ -1258,7 +1300,14 @@ class PretrainEngine:
         self._refresh_transposes()
         if self.vision is not None:
             self.vision.refresh_weights(trainable_only=True)
+        self._advance_seed()
+
+    def _advance_seed(self):
+        """Fresh dropout masks for the next step.  The value the last forward drew from is kept (4 bytes, on the device, graph-
+        replayable) so that attention_probs() can still regenerate that forward's masks after the step has finished."""
+        self._seed_prev.copy_(self.seed)
         ops.rng_advance(self.seed)
+        self._seed_moved = True
 
     def _check_mlm_overflow_now_and_then(self, every=64):
         """MLM head compaction with device-resident labels: the overflow flag (a batch with more labelled positions than mlm_cap ran

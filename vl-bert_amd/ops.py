@@ -282,6 +282,20 @@ def attention_bwd(qkv, mask, ctx, lse, dctx, dqkv, B, S, H, nh, drop_p=0.0, seed
     return dqkv
 
 
+def attention_probs(qkv, mask, lse, B, S, H, nh, n=None, drop_p=0.0, seed=None, tag=0, out=None):
+    """The probabilities of the attention_fwd that wrote `lse` from the same qkv / mask (vlb_attention_probs): the fp32 view
+    [B, nh, n, n] of a buffer [B, nh, n, ldp], ldp = n rounded up to 32 (rows start on a 128-byte line).  `out`: a contiguous fp32
+    [B, nh, n, ldp] buffer to write into (ldp % 4 == 0; its columns n..ldp are written too: zeros from S on).  drop_p / seed / tag
+    of the forward give the probabilities after its dropout."""
+    n = S if n is None else int(n)
+    if out is None:
+        out = torch.empty((B, nh, n, (n + 31) // 32 * 32), dtype=torch.float32, device=qkv.device)
+    assert out.dim() == 4 and out.is_contiguous() and tuple(out.shape[:3]) == (B, nh, n), tuple(out.shape)
+    _lib.call("vlb_attention_probs", _p(qkv, BF16), _p(mask, torch.float32), _p(lse, torch.float32), _p(out, torch.float32),
+              B, S, H, nh, n, out.shape[3], float(drop_p), _p(seed), int(tag), _stream())
+    return out[:, :, :, :n]
+
+
 def seq_layout(text_mask, obj_mask, S):
     """masks: uint8/bool [B,T], [B,R] -> dict of layout tensors (all device int32 / fp32)."""
     B, T = text_mask.shape

@@ -98,6 +98,9 @@ def resolve(config, world, args):
     if sched is None:
         raise NotImplementedError("TRAIN.LR_SCHEDULE %s (supported: triangle, constant)" % tr.LR_SCHEDULE)
     multitask = config.MODULE == "ResNetVLBERTForPretrainingMultitask"
+    if config.MODULE == "ResNetVLBERTForAttentionVis":
+        raise NotImplementedError("MODULE ResNetVLBERTForAttentionVis has no loss to train on: write its attention maps with "
+                                  "`python -m vl-bert_amd.pretrain.vis_attention_maps --cfg <yaml> --save-dir <dir>`")
     if config.MODULE not in ("ResNetVLBERTForPretraining", "ResNetVLBERTForPretrainingMultitask"):
         raise NotImplementedError("MODULE %s" % config.MODULE)
     if not multitask:
