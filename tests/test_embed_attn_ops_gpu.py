@@ -12,10 +12,6 @@ Bars (derived in the header of tests/test_ops_gpu.py): 16-bit outputs 1e-3 + 1e-
 SUB-TENSOR being reported (a d_type row, a group of d_pos rows, a table row, the masked positions of attention), so that a large
 destination does not hide a small one.  The file runs unchanged on the fp16 build (VLB_PRECISION=f16).
 """
-import os
-import re
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -364,20 +360,3 @@ def test_attention_masks_and_short_sequences(ops, B, S, nh, p):
                 report(name + nm + " " + gname, got, ref, max(R.bar(ref, (2e-3, 2e-2)), 4 * err32), 0.0)
             else:
                 report(name + nm + " " + gname, got, ref, 2e-3, 2e-2)
-
-
-def test_two_orientation_backward_in_a_child_process():
-    """attn_bwd_kernel<4,1>, the two-orientation backward at S <= 128, is only reachable through VLB_ATTN_BWD2=0, which the library
-    reads once per process: the attention battery above runs again in a fresh child process with the variable set (kept rather than
-    deleted: tests/test_isa_cpu.py pins that instantiation's prologue and register budget)."""
-    if os.environ.get("VLB_ATTN_BWD2") == "0":
-        pytest.fail("the parent process already runs with VLB_ATTN_BWD2=0")
-    env = dict(os.environ, VLB_ATTN_BWD2="0")
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    cmd = [sys.executable, "-m", "pytest", os.path.abspath(__file__), "-m", "gpu", "-q", "-k", "test_attention_masks_and_short_sequences"]
-    r = subprocess.run(cmd, env=env, cwd=root, capture_output=True, text=True, timeout=600)
-    print(r.stdout[-3000:])
-    print(r.stderr[-1000:])
-    assert r.returncode == 0, r.stdout[-3000:]
-    m = re.search(r"(\d+) passed", r.stdout)
-    assert m and int(m.group(1)) == 18 and "failed" not in r.stdout and "skipped" not in r.stdout, r.stdout[-500:]

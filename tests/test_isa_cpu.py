@@ -32,13 +32,11 @@ def layernorm():
 def test_attention_prologues_issue_their_loads_in_one_burst(attention):
     fwd = L.find(attention, r"attn_fwd_kernelILi4ELi1E")
     bwd2 = L.find(attention, r"attn_bwd2_kernel")
-    bwd = L.find(attention, r"attn_bwd_kernelILi4ELi1E")
     # forward: K and V tiles (4 x 16 B per thread), the first Q fragment (2) and the mask row before the first wait
     assert L.loads_before_first_wait(fwd["body"]) >= 7
     # backward: Q, K, V, dO tiles (8), O for the row dots (2), mask and lse rows (2)
     assert L.loads_before_first_wait(bwd2["body"]) >= 12
-    assert L.loads_before_first_wait(bwd["body"]) >= 12
-    for k in (fwd, bwd2, bwd):
+    for k in (fwd, bwd2):
         assert L.serialized_loads(k["body"]) == 0
         assert k["spill"] == 0 and k["scratch"] == 0
     # the first wait of the backward is a COUNTED one (the oldest load of the burst, not the whole queue)
@@ -51,7 +49,6 @@ def test_attention_register_budgets(attention):
     # launch geometry: forward 4 workgroups of 8 waves per CU (<= 64 VGPRs), backward 2 (<= 128)
     assert L.find(attention, r"attn_fwd_kernelILi4ELi1E")["vgpr"] <= 64
     assert L.find(attention, r"attn_bwd2_kernel")["vgpr"] <= 128
-    assert L.find(attention, r"attn_bwd_kernelILi4ELi1E")["vgpr"] <= 128
     assert L.find(attention, r"attn_fwd_kernelILi8ELi2E")["vgpr"] <= 128
     assert L.find(attention, r"attn_bwd_kernelILi8ELi2E")["vgpr"] <= 128
 
@@ -75,18 +72,18 @@ def test_layernorm_rows_are_loaded_in_one_burst(layernorm):
 
 def test_grouped_weight_gradient_main_loop_is_clean():
     ks = L.kernels(L.compile_isa(os.path.join(CSRC, "gemm_tn8.hip")))
-    # descriptors in the kernel argument | in a device table (round 4)  x  16x16x32 | 32x32x16 matrix instructions (round 6)
-    for inst, mfmas in ((r"gemm_tn8_kernelILb0ELb0E", 128), (r"gemm_tn8_kernelILb1ELb0E", 128), (r"gemm_tn8_kernelILb0ELb1E", 64),
-                        (r"gemm_tn8_kernelILb1ELb1E", 64)):
+    # descriptors in the kernel argument | in a device table (round 4)
+    for inst, mfmas in ((r"gemm_tn8_kernelILb0ELi0E", 128), (r"gemm_tn8_kernelILb1ELi0E", 128)):
         k = L.find(ks, inst)
         lo, hi = L.mfma_region(k["body"])
         inner = L.region_counts(k["body"], lo, hi)
-        assert inner["mfma"] == mfmas and inner["scratch"] == 0     # two K tiles x four phases x 16 (8) MFMAs, no spill traffic in the loop
+        assert inner["mfma"] == mfmas and inner["scratch"] == 0     # two K tiles x four phases x 16 MFMAs, no spill traffic in the loop
         assert inner["vmcnt0"] == 0                                  # the producer never stops (round 6): one form of the counted wait, no drain
         assert k["spill"] == 0 and k["vgpr"] <= 256 and k["scratch"] == 0, inst      # (round 6: a four-way switch over csum[] once put it in scratch)
         # round 6: no `live` flag in front of the load segments -- what is left are the item switch of the producer (taken once per
-        # item) and the four column-sum turns; 37 with the flag
-        assert inner["branches"] <= 28, (inst, inner["branches"])
+        # item) and the four column-sum turns: 12 (arguments) / 16 (table) compiled; 22 / 26 with the uneven cut's item decode in the
+        # switch, 37 with the flag
+        assert inner["branches"] <= 18, (inst, inner["branches"])
 
 
 def test_large_tile_forward_core_has_no_producer_branches():

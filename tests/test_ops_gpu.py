@@ -144,8 +144,8 @@ def test_gemm_epilogues(ops):
 
 # the run-time names of the option table (csrc/options.h) with their defaults
 OPTION_DEFAULTS = {"p8_mode": 1, "p8_keepb": 1, "p8_group": 2, "p8_min_tiles": 160, "p8_wgs": 256, "p8_ablate": 0, "p8_tile192": 1,
-                   "p8_drain": 0, "p8_lastw": 0, "nt_ring": 1, "nt_stagger": 0, "tn8_mode": 1, "tn8_wgs": 256, "tn8_uneven": 0,
-                   "tn8_m32": 0, "tn8_ablate": 0, "ln_fwd_rows": 0, "ln_bwd4": 1}
+                   "p8_drain": 0, "p8_lastw": 0, "nt_ring": 1, "nt_stagger": 0, "tn8_mode": 1, "tn8_wgs": 256, "tn8_ablate": 0,
+                   "ln_fwd_rows": 0, "ln_bwd4": 1}
 
 
 def test_gemm_set_option_names():
@@ -156,6 +156,9 @@ def test_gemm_set_option_names():
             lib.gemm_set_option("no_such_option", 1)
         with pytest.raises(RuntimeError, match="negative value"):
             lib.gemm_set_option("p8_mode", -1)
+        for retired in ("tn8_m32", "tn8_uneven", "tn_waves8", "attn_bwd2"):      # variants that lost their measurements
+            with pytest.raises(RuntimeError, match="unknown option"):
+                lib.gemm_set_option(retired, 0)
     finally:
         for name, value in OPTION_DEFAULTS.items():
             lib.gemm_set_option(name, value)
@@ -529,77 +532,54 @@ def test_wgrad_tn_grouped_layer(ops, R, accumulate):
 
 
 @pytest.mark.parametrize("R", [25856, 12928 + 128, 6528])
-def test_wgrad_tn_grouped_layer_uneven_cut(ops, R):
-    """The grouped launch at the encoder's row counts (batch 256 / 128 / 64): 108 tiles x 2 K slices leave 40 CUs idle, so the host cuts
-    every tile's K range in two long slices + a short remainder dealt to the spare workgroups (gemm_tn8.hip, Tn8Group).  Both cuts
-    against an fp32 torch.mm of the same bf16 operands, and against each other."""
-    from importlib import import_module
-    lib = import_module("vl-bert_amd._lib")
+def test_wgrad_tn_grouped_layer_encoder_rows(ops, R):
+    """The grouped launch at the encoder's row counts (batch 256 / 128 / 64): 108 tiles x 2 equal K slices, against an fp32 torch.mm of
+    the same bf16 operands."""
     H, I = 768, 3072
     shapes = [(H, I), (I, H), (H, H), (3 * H, H)]
     ins = [(to_gpu_bf16(rnd(R, Mo, seed=60 + k, scale=0.5)), to_gpu_bf16(rnd(R, No, seed=70 + k, scale=0.2))) for k, (Mo, No) in enumerate(shapes)]
-    work = torch.empty(3 * sum(a * b for a, b in shapes) + 64, dtype=torch.float32, device=dev())
-    got = {}
-    try:
-        for uneven in (0, 1):
-            lib.gemm_set_option("tn8_uneven", uneven)
-            items = [(dY, X, torch.full((Mo, No), 0.5, dtype=torch.float32, device=dev()), torch.ones(Mo, dtype=torch.float32, device=dev()))
-                     for (dY, X), (Mo, No) in zip(ins, shapes)]
-            ops.wgrad_tn_group(items, workspace=work, accumulate=True)
-            got[uneven] = items
-    finally:
-        lib.gemm_set_option("tn8_uneven", 0)
+    work = torch.empty(2 * sum(a * b for a, b in shapes) + 64, dtype=torch.float32, device=dev())
+    items = [(dY, X, torch.full((Mo, No), 0.5, dtype=torch.float32, device=dev()), torch.ones(Mo, dtype=torch.float32, device=dev()))
+             for (dY, X), (Mo, No) in zip(ins, shapes)]
+    ops.wgrad_tn_group(items, workspace=work, accumulate=True)
     for k, (dY, X) in enumerate(ins):
         ref = 0.5 + dY.float().t() @ X.float()
         refb = 1 + dY.float().sum(0)
-        for uneven in (0, 1):
-            report("grouped wgrad %d (R=%d, uneven=%d)" % (k, R, uneven), got[uneven][k][2], ref.cpu(), 1e-3, 2e-4)
-            report("grouped wgrad %d colsum (uneven=%d)" % (k, uneven), got[uneven][k][3], refb.cpu(), 1e-3, 2e-4)
-        report("grouped wgrad %d uneven vs equal cut" % k, got[1][k][2], got[0][k][2].cpu(), 1e-3, 2e-4)
+        report("grouped wgrad %d (R=%d)" % (k, R), items[k][2], ref.cpu(), 1e-3, 2e-4)
+        report("grouped wgrad %d colsum" % k, items[k][3], refb.cpu(), 1e-3, 2e-4)
 
 
 @pytest.mark.parametrize("R", [25856, 3328])
 def test_wgrad_tn_core_variants(ops, R):
-    """The large-tile weight-gradient core with both matrix instructions (round 6: `tn8_m32` 0 = 16x16x32, the default; 1 = 32x32x16) as the
-    grouped launch of an encoder layer, as a ragged single product (Mo, No not multiples of the tile), and as the TABLE launch of two
-    layers' products over full K (what the engine issues per layer pair): each against an fp32 torch.mm of the same bf16 operands."""
-    from importlib import import_module
-    lib = import_module("vl-bert_amd._lib")
+    """The large-tile weight-gradient core as the grouped launch of an encoder layer, as a ragged single product (Mo, No not multiples
+    of the tile), and as the TABLE launch of two layers' products over full K (what the engine issues per layer pair): each against an
+    fp32 torch.mm of the same bf16 operands."""
     H, I = 768, 3072
     shapes = [(H, I), (I, H), (H, H), (3 * H, H)]
     ins = [(to_gpu_bf16(rnd(R, Mo, seed=160 + k, scale=0.5)), to_gpu_bf16(rnd(R, No, seed=170 + k, scale=0.2))) for k, (Mo, No) in enumerate(shapes * 2)]
     rag = (to_gpu_bf16(rnd(4096, 1000, seed=180, scale=0.5)), to_gpu_bf16(rnd(4096, 520, seed=181, scale=0.2)))
     work = torch.empty(3 * sum(a * b for a, b in shapes) + 64, dtype=torch.float32, device=dev())
-    got = {}
-    try:
-        for m32 in (0, 1):
-            lib.gemm_set_option("tn8_m32", m32)
-            mk = lambda Mo, No, c: (torch.full((Mo, No), c, dtype=torch.float32, device=dev()), torch.ones(Mo, dtype=torch.float32, device=dev()))
-            items = [(dY, X) + mk(Mo, No, 0.5) for (dY, X), (Mo, No) in zip(ins[:4], shapes)]
-            ops.wgrad_tn_group(items, workspace=work, accumulate=True)
-            one = [(rag[0], rag[1], torch.full((1000, 520), -0.25, dtype=torch.float32, device=dev()), torch.zeros(1000, dtype=torch.float32, device=dev()))]
-            ops.wgrad_tn_group(one, workspace=work, accumulate=True)
-            pair = [(dY, X) + mk(Mo, No, 0.5) + (None,) for (dY, X), (Mo, No) in zip(ins, shapes * 2)]
-            tab = ops.WgradTable(pair, dev(), accumulate=True)
-            assert tab.ok and tab.nitems == 216
-            tab.run()
-            torch.cuda.synchronize()
-            got[m32] = (items + one, pair)
-    finally:
-        lib.gemm_set_option("tn8_m32", 0)
+    mk = lambda Mo, No, c: (torch.full((Mo, No), c, dtype=torch.float32, device=dev()), torch.ones(Mo, dtype=torch.float32, device=dev()))
+    items = [(dY, X) + mk(Mo, No, 0.5) for (dY, X), (Mo, No) in zip(ins[:4], shapes)]
+    ops.wgrad_tn_group(items, workspace=work, accumulate=True)
+    one = [(rag[0], rag[1], torch.full((1000, 520), -0.25, dtype=torch.float32, device=dev()), torch.zeros(1000, dtype=torch.float32, device=dev()))]
+    ops.wgrad_tn_group(one, workspace=work, accumulate=True)
+    pair = [(dY, X) + mk(Mo, No, 0.5) + (None,) for (dY, X), (Mo, No) in zip(ins, shapes * 2)]
+    tab = ops.WgradTable(pair, dev(), accumulate=True)
+    assert tab.ok and tab.nitems == 216
+    tab.run()
+    torch.cuda.synchronize()
     for k, (dY, X) in enumerate(ins[:4] + [rag]):
         base, cbase = (0.5, 1.0) if k < 4 else (-0.25, 0.0)
         ref = (base + dY.float().t() @ X.float()).cpu()
         refb = (cbase + dY.float().sum(0)).cpu()
-        for m32 in (0, 1):
-            report("wgrad core m32=%d product %d (R=%d)" % (m32, k, R), got[m32][0][k][2], ref, 1e-3, 2e-4)
-            report("wgrad core m32=%d colsum %d" % (m32, k), got[m32][0][k][3], refb, 1e-3, 2e-4)
+        report("wgrad core product %d (R=%d)" % (k, R), (items + one)[k][2], ref, 1e-3, 2e-4)
+        report("wgrad core colsum %d" % k, (items + one)[k][3], refb, 1e-3, 2e-4)
     for k, (dY, X) in enumerate(ins):
         ref = (0.5 + dY.float().t() @ X.float()).cpu()
         refb = (1.0 + dY.float().sum(0)).cpu()
-        for m32 in (0, 1):
-            report("wgrad pair table m32=%d product %d (R=%d)" % (m32, k, R), got[m32][1][k][2], ref, 1e-3, 2e-4)
-            report("wgrad pair table m32=%d colsum %d" % (m32, k), got[m32][1][k][3], refb, 1e-3, 2e-4)
+        report("wgrad pair table product %d (R=%d)" % (k, R), pair[k][2], ref, 1e-3, 2e-4)
+        report("wgrad pair table colsum %d" % k, pair[k][3], refb, 1e-3, 2e-4)
 
 
 @pytest.mark.parametrize("accumulate", [True, False])

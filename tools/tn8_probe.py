@@ -3,9 +3,8 @@
 
   python tools/tn8_probe.py [batch] [--ablate]
 
-* correctness of both matrix-instruction forms (option "tn8_m32" 0 / 1) against a torch fp32 product on the encoder's four shapes
-  (column sums included) and on an edge shape;
-* the layer group (QKV, attention output, FFN1, FFN2 over R = batch * 101 rows padded to 128) timed INTERLEAVED for both forms, with
+* correctness against a torch fp32 product on the encoder's four shapes (column sums included) and on an edge shape;
+* the layer group (QKV, attention output, FFN1, FFN2 over R = batch * 101 rows padded to 128) timed with
   the per-workgroup clock stamps (vlb_tn8_set_stamps): sustained shader clock, cycles per K tile, spread over the workgroups;
 * --ablate (needs a library built with -DVLB_TN8_PROBE, e.g. VLB_LIB_PATH=vl-bert_amd/csrc/ab/libvlbert_hip.so): the same launch with
   bit 0 no LDS-DMA | bit 1 no fragment reads | bit 2 no MFMAs, in shader CYCLES per K tile (the clock moves with the ablation)."""
@@ -42,39 +41,30 @@ def launch():
     ops.wgrad_tn_group(M, workspace=ws, accumulate=False)
 
 
-VARIANTS = [(0, 0), (1, 0)]      # (tn8_m32, reserved)
-
-
-def select(m32, sched):
-    lib.gemm_set_option("tn8_m32", m32)
-
-
 def check():
     ok = True
-    for m32, sched in VARIANTS:
-        select(m32, sched)
-        for t in M:
-            t[2].zero_(); t[3].zero_()
-        launch()
-        torch.cuda.synchronize()
-        for (name, mo, no), (dy, x, C, cs) in zip(shapes, M):
-            ref = dy.float().t() @ x.float()
-            err = (C - ref).abs().max().item() / ref.abs().max().item()
-            cerr = (cs - dy.float().sum(0)).abs().max().item() / dy.float().sum(0).abs().max().item()
-            good = err < 2e-5 and cerr < 1e-4
-            ok &= good
-            print("check m32=%d sched=%d %-5s rel err %.2e colsum %.2e %s" % (m32, sched, name, err, cerr, "ok" if good else "BAD"))
-        # edge shape: Mo, No not multiples of 256 / 16, accumulate into a non-zero C, through the single-gradient entry
-        dy, x, C, cs = member(1000, 520, 4096)
-        C.fill_(0.5)
-        ops.wgrad_tn_group([(dy, x, C, cs)], workspace=ws, accumulate=True)
-        torch.cuda.synchronize()
-        ref = dy.float().t() @ x.float() + 0.5
+    for t in M:
+        t[2].zero_(); t[3].zero_()
+    launch()
+    torch.cuda.synchronize()
+    for (name, mo, no), (dy, x, C, cs) in zip(shapes, M):
+        ref = dy.float().t() @ x.float()
         err = (C - ref).abs().max().item() / ref.abs().max().item()
-        cerr = (cs - dy.float().sum(0)).abs().max().item()
-        good = err < 2e-5 and cerr < 1e-2
+        cerr = (cs - dy.float().sum(0)).abs().max().item() / dy.float().sum(0).abs().max().item()
+        good = err < 2e-5 and cerr < 1e-4
         ok &= good
-        print("check m32=%d sched=%d edge  rel err %.2e colsum abs %.2e %s" % (m32, sched, err, cerr, "ok" if good else "BAD"))
+        print("check %-5s rel err %.2e colsum %.2e %s" % (name, err, cerr, "ok" if good else "BAD"))
+    # edge shape: Mo, No not multiples of 256 / 16, accumulate into a non-zero C, through the single-gradient entry
+    dy, x, C, cs = member(1000, 520, 4096)
+    C.fill_(0.5)
+    ops.wgrad_tn_group([(dy, x, C, cs)], workspace=ws, accumulate=True)
+    torch.cuda.synchronize()
+    ref = dy.float().t() @ x.float() + 0.5
+    err = (C - ref).abs().max().item() / ref.abs().max().item()
+    cerr = (cs - dy.float().sum(0)).abs().max().item()
+    good = err < 2e-5 and cerr < 1e-2
+    ok &= good
+    print("check edge  rel err %.2e colsum abs %.2e %s" % (err, cerr, "ok" if good else "BAD"))
     return ok
 
 
@@ -111,12 +101,10 @@ for _ in range(10):
     launch()
 kt = R / 64 / 2          # K tiles per work item (two K slices)
 for rnd in range(4):
-    for m32, sched in VARIANTS:
-        select(m32, sched)
-        us = timed()
-        mhz, med, mx, n = stamped()
-        print("round %d m32=%d sched=%d: %7.1f us  %7.1f TFLOP/s | %4.0f MHz, %d workgroups, cycles per K tile median %.0f max %.0f"
-              % (rnd, m32, sched, us, flops / us / 1e6, mhz, n, med / kt, mx / kt))
+    us = timed()
+    mhz, med, mx, n = stamped()
+    print("round %d: %7.1f us  %7.1f TFLOP/s | %4.0f MHz, %d workgroups, cycles per K tile median %.0f max %.0f"
+          % (rnd, us, flops / us / 1e6, mhz, n, med / kt, mx / kt))
 # which workgroups are the slow ones?  (block b runs on XCD b % 8; the item list is XCD-contiguous, see the kernel)
 cyc = stamped.last / kt
 order = torch.argsort(cyc, descending=True)
@@ -137,31 +125,28 @@ for (name, mo, no), (dy, x, C, cs) in zip(shapes + shapes, M + M2):
     ref = dy.float().t() @ x.float()
     err = (C - ref).abs().max().item() / ref.abs().max().item()
     print("pair table %-5s rel err %.2e %s" % (name, err, "ok" if err < 2e-5 else "BAD"))
-for m32, sched in ((0, 0), (1, 0)):
-    select(m32, sched)
-    for rnd in range(2):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        for _ in range(3):
-            tab.run()
-        e0.record()
-        for _ in range(10):
-            tab.run()
-        e1.record()
-        torch.cuda.synchronize()
-        us_tab = e0.elapsed_time(e1) / 10 * 1e3
-        MM = M
-        for _ in range(3):
-            launch()
-        e0.record()
-        for _ in range(10):
-            M = MM; launch(); M = M2; launch()
-        e1.record()
-        torch.cuda.synchronize()
-        M = MM
-        us_two = e0.elapsed_time(e1) / 10 * 1e3
-        print("m32=%d sched=%d two layers: table launch %7.1f us (%6.1f TFLOP/s) | two grouped launches + reduces %7.1f us (%6.1f TFLOP/s)"
-              % (m32, sched, us_tab, 2 * flops / us_tab / 1e6, us_two, 2 * flops / us_two / 1e6))
-select(0, 0)
+for rnd in range(2):
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    for _ in range(3):
+        tab.run()
+    e0.record()
+    for _ in range(10):
+        tab.run()
+    e1.record()
+    torch.cuda.synchronize()
+    us_tab = e0.elapsed_time(e1) / 10 * 1e3
+    MM = M
+    for _ in range(3):
+        launch()
+    e0.record()
+    for _ in range(10):
+        M = MM; launch(); M = M2; launch()
+    e1.record()
+    torch.cuda.synchronize()
+    M = MM
+    us_two = e0.elapsed_time(e1) / 10 * 1e3
+    print("two layers: table launch %7.1f us (%6.1f TFLOP/s) | two grouped launches + reduces %7.1f us (%6.1f TFLOP/s)"
+          % (us_tab, 2 * flops / us_tab / 1e6, us_two, 2 * flops / us_two / 1e6))
 
 # the same launch WITHOUT the bias-gradient column sums: are the n0 = 0 tiles (whose wn = 0 waves take them) the slow workgroups?
 M_cs = M
@@ -177,15 +162,12 @@ M = M_cs
 if ABLATE:
     names = {0: "full", 1: "no DMA", 2: "no reads", 3: "no DMA, no reads (MFMA + barriers)", 4: "no MFMA", 5: "no MFMA, no DMA (reads + barriers)",
              6: "no MFMA, no reads (DMA + barriers)", 8: "all workgroups stream item 0's panels (L2 hits)", 12: "no MFMA, item 0's panels (reads + DMA + barriers, L2 hits)", 14: "DMA + barriers, item 0's panels"}
-    for m32, sched in ((0, 0), (1, 0)):
-        select(m32, sched)
-        for ab in (0, 1, 2, 3, 4, 5, 6, 8, 12, 14):
-            lib.gemm_set_option("tn8_ablate", ab)
-            for _ in range(3):
-                launch()
-            us = timed(10)
-            mhz, med, mx, n = stamped()
-            print("ablate m32=%d sched=%d %-40s: %7.1f us | %4.0f MHz, cycles per K tile median %.0f max %.0f"
-                  % (m32, sched, names[ab], us, mhz, med / kt, mx / kt))
+    for ab in (0, 1, 2, 3, 4, 5, 6, 8, 12, 14):
+        lib.gemm_set_option("tn8_ablate", ab)
+        for _ in range(3):
+            launch()
+        us = timed(10)
+        mhz, med, mx, n = stamped()
+        print("ablate %-40s: %7.1f us | %4.0f MHz, cycles per K tile median %.0f max %.0f"
+              % (names[ab], us, mhz, med / kt, mx / kt))
     lib.gemm_set_option("tn8_ablate", 0)
-select(0, 0)

@@ -27,7 +27,6 @@
 // orientations regenerate identical masks, nothing is stored.
 // Sequences of 257..512 positions do not fit this design (four 64 KB images, a 16x512 score slice per wave): they go to the
 // streaming kernels of attention_long.hip, which share the LDS images and fragments of attention_common.h.
-#include "options.h"
 #include "vlb_common.h"
 #include "attention_common.h"
 
@@ -555,17 +554,14 @@ extern "C" int vlb_attention_bwd(const void* qkv, const float* mask, const void*
   p.drop_thr = vlb_drop_thr(drop_p); p.drop_scale = vlb_drop_scale(p.drop_thr); p.seed = seed; p.tag = tag;
   static bool attr_set = false;
   if (!attr_set) {
-    (void)hipFuncSetAttribute((const void*)attn_bwd_kernel<4, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * (128 * ATT_D * 2) + 3 * 128 * 4);
     (void)hipFuncSetAttribute((const void*)attn_bwd2_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * (128 * ATT_D * 2) + 3 * 128 * 4);
     (void)hipFuncSetAttribute((const void*)attn_bwd_kernel<8, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * (256 * ATT_D * 2) + 3 * 256 * 4);
     attr_set = true;
   }
   if (S > ATT_SP_MAX)            // 257..512: two roles, two launches (attention_long.hip)
     vlb_attention_long_bwd_launch(p, stream);
-  else if (S <= 128 && vlb_opt(VLB_OPT_ATTN_BWD2))
-    hipLaunchKernelGGL(attn_bwd2_kernel, dim3(B * nh), dim3(ATT_THREADS), 4 * (128 * ATT_D * 2) + 3 * 128 * 4, stream, p);
   else if (S <= 128)
-    hipLaunchKernelGGL((attn_bwd_kernel<4, 1>), dim3(B * nh), dim3(ATT_THREADS), 4 * (128 * ATT_D * 2) + 3 * 128 * 4, stream, p);
+    hipLaunchKernelGGL(attn_bwd2_kernel, dim3(B * nh), dim3(ATT_THREADS), 4 * (128 * ATT_D * 2) + 3 * 128 * 4, stream, p);
   else
     hipLaunchKernelGGL((attn_bwd_kernel<8, 2>), dim3(B * nh), dim3(ATT_THREADS), 4 * (256 * ATT_D * 2) + 3 * 256 * 4, stream, p);
   VLB_CHECK_LAUNCH("vlb_attention_bwd");

@@ -1608,13 +1608,8 @@ static int tn128_launch(GemmParams& p, float* C, long ldc, int R, int Mo, int No
   }
   p.ntm = vlb_cdiv(Mo, 128); p.ntn = vlb_cdiv(No, 128);
   const dim3 grid(p.ntm * p.ntn, nsp);
-  if (CONV || vlb_opt(VLB_OPT_TN_WAVES8)) {
-    if (p.out_f32 == 3) tn128_launch_kernel<gemm_tn_bf16_kernel<4, 3, CONV>>(grid, 512, p, colsum, stream);
-    else tn128_launch_kernel<gemm_tn_bf16_kernel<4, 1, CONV>>(grid, 512, p, colsum, stream);
-  } else if constexpr (!CONV) {
-    if (p.out_f32 == 3) tn128_launch_kernel<gemm_tn_bf16_kernel<2, 3>>(grid, 256, p, colsum, stream);
-    else tn128_launch_kernel<gemm_tn_bf16_kernel<2, 1>>(grid, 256, p, colsum, stream);
-  }
+  if (p.out_f32 == 3) tn128_launch_kernel<gemm_tn_bf16_kernel<4, 3, CONV>>(grid, 512, p, colsum, stream);
+  else tn128_launch_kernel<gemm_tn_bf16_kernel<4, 1, CONV>>(grid, 512, p, colsum, stream);
   VLB_CHECK_LAUNCH(name);
   if (slab) return launch_splitk_reduce(workspace, (long)Mo * ldw, nsp, C, ldc, Mo, No, ldw, accumulate, rowscale, stream, name);
   return VLB_OK;

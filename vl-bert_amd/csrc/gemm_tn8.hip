@@ -67,21 +67,13 @@ struct Tn8Desc {
   int ntm, ntn, tile_group;
   int nsplit, kt_per_split;             // K slices and 64-row K tiles per slice (even)
   int item0, nitems;                    // position in the launch's item list
-  int short0;                           // uneven mode: position of this gradient's remainder slices in the short list
   int accumulate;                       // direct output (nsplit == 1): C += instead of C =
   const float* rowscale;                // direct output: row m of the product is multiplied by rowscale[m] first (frozen-BN fold), or null
 };
 constexpr int TN8_MAX_GROUP = 4;
-// Uneven mode (nlong > 0): with T tiles and 2 T <= 256 < 3 T, two equal K slices leave 256 - 2 T CUs idle (216 items for 256 CUs at
-// the encoder's shapes: 16 % of the chip).  Every tile's K range is then cut in THREE: two long slices of kt_per_split K tiles --
-// the first nlong = 2 T items, one per workgroup -- and a short remainder; the T remainders are shared by the other workgroups
-// (k = ceil(T / (grid - nlong)) each).  With L chosen so that L ~ k x remainder the makespan drops from 101 to 87 K-tile pairs at
-// batch 256 (-14 %) for one more slab per tile.  OFF by default: on the GPU the launch is not faster (the 40 idle CUs leave the
-// other 216 more fabric bandwidth and clock; the third slab costs 57 MB of extra traffic per layer) -- see DESIGN.md.
 struct Tn8Group {
   Tn8Desc d[TN8_MAX_GROUP];
   int n, nitems;
-  int nlong;
   unsigned long long* stamps;           // measurement only (tools/tn8_probe.py): workgroup b leaves {cycles, 100 MHz ticks} x {entry, exit}
 };
 
@@ -89,18 +81,9 @@ struct Tn8Group {
 // any number of descriptors in a device table `tab` (grp.n / grp.nitems valid, grp.d unused) -- the deferred weight gradients of a
 // whole ResNet stage (vision.py): ~46 small products that would each be a 100-300-tile launch + a slab reduce become one launch of
 // full-K 256 x 256 items; the descriptor of an item is found by binary search over item0.
-// M32 (round 6): the quadrant's products as 8 x v_mfma_f32_32x32x16 instead of 16 x v_mfma_f32_16x16x32 -- half the matrix
-// instructions and half the operand-register reads per FLOP (the chip is power-limited under these kernels), and the 32x32 form's
-// issue ceiling is 15 % above the 16x16 form's (2382 vs 2075 TFLOP/s micro-benchmarked).  A wave's 64 x 32 share of a quadrant is two
-// 32 x 32 blocks; a fragment of k-step s (16 reduction rows) is rows 16 s + 8 (lane >> 5) + [0, 8) of column lane & 31, i.e. the
-// 16-lane groups of a transpose read take (k half, 16-column half) = (lane >> 5, (lane >> 4) & 1); the 32-B column units are swizzled
-// by f(row) = (row & 3) << 1, which spreads the 4 rows x 2 units of a 32-lane read group over all 64 banks.
-// Measured (tools/tn8_probe.py, profiles/r06_tn8_probe.txt): 11 % fewer shader cycles per K tile (2900 vs 3270) at an 11 % lower clock
-// (1.99 vs 2.23 GHz) -- the chip is power-limited under this kernel and the launch takes the same 355-365 us either way; the whole step
-// was 0.1 ms slower with it.  Default: the 16x16x32 form (VLB_GEMM_TN8_M32=1 / option "tn8_m32" selects this one).
 // ABL (measurement builds only, -DVLB_TN8_PROBE): bit 0 no LDS-DMA, bit 1 no fragment reads, bit 2 no MFMAs, bit 3 every workgroup
 // streams the operand panels of work item 0 (an all-L2-hit operand stream) -- results WRONG.
-template <bool TABLE, bool M32, int ABL = 0>
+template <bool TABLE, int ABL = 0>
 __global__ __launch_bounds__(512, 2) void gemm_tn8_kernel(const Tn8Group grp, const Tn8Desc* __restrict__ tab) {
   auto D = [&](int gi) -> Tn8Desc {
     if constexpr (TABLE) return tab[gi];
@@ -126,37 +109,24 @@ __global__ __launch_bounds__(512, 2) void gemm_tn8_kernel(const Tn8Group grp, co
   // operand rows in L2); inside a slice the tiles are walked in groups of `tile_group` tile rows, column-major inside a group
   // Work item w (block b takes w = b, b + grid, ...) -> position in the item list: every XCD owns a CONTIGUOUS run of the list
   // (tile_order.h), i.e. tiles of the same gradient and K slice that share operand panels in that XCD's L2.
-  const int nlong = grp.nlong;
   auto item_of = [&](int w, int& gi, int& m0, int& n0, int& kt0, int& nk) {
-    int sp, t;
     gi = 0;
-    if (nlong > 0 && w >= nlong) {          // a remainder slice (uneven mode): short list, tile-major per gradient
-      const int vs = vlb_xcd_order(w - nlong, nitems - nlong);
+    w = vlb_xcd_order(w, nitems);
+    if constexpr (TABLE) {
+      int lo = 0, hi = grp.n;
+      while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (w >= tab[mid].item0) lo = mid; else hi = mid;
+      }
+      gi = lo;
+    } else {
 #pragma unroll
       for (int q = 1; q < TN8_MAX_GROUP; ++q)
-        if (q < grp.n && vs >= grp.d[q].short0) gi = q;
-      sp = 2;
-      t = vs - grp.d[gi].short0;
-    } else {
-      w = vlb_xcd_order(w, nlong > 0 ? nlong : nitems);
-      if constexpr (TABLE) {
-        int lo = 0, hi = grp.n;
-        while (hi - lo > 1) {
-          const int mid = (lo + hi) >> 1;
-          if (w >= tab[mid].item0) lo = mid; else hi = mid;
-        }
-        gi = lo;
-      } else {
-#pragma unroll
-        for (int q = 1; q < TN8_MAX_GROUP; ++q)
-          if (q < grp.n && w >= grp.d[q].item0) gi = q;
-      }
-      const Tn8Desc dd = D(gi);
-      const int wl = w - dd.item0, ntile = dd.ntm * dd.ntn;
-      sp = wl / ntile;
-      t = wl - sp * ntile;
+        if (q < grp.n && w >= grp.d[q].item0) gi = q;
     }
     const Tn8Desc d = D(gi);
+    const int wl = w - d.item0, ntile = d.ntm * d.ntn;
+    const int sp = wl / ntile, t = wl - sp * ntile;
     int tile_m, tile_n;
     vlb_tile_of(t, d.ntm, d.ntn, d.tile_group, tile_m, tile_n);
     m0 = tile_m * 256;
@@ -164,15 +134,14 @@ __global__ __launch_bounds__(512, 2) void gemm_tn8_kernel(const Tn8Group grp, co
     kt0 = sp * d.kt_per_split;
     nk = min((d.R >> 6) - kt0, d.kt_per_split);       // even, >= 2 (host guarantees)
   };
-  // this workgroup's walk through the item list: w = b, b + step, ...  (uneven mode: a long item is the only one of its workgroup,
-  // the remainders are dealt round-robin to the workgroups behind the long ones)
-  const int step = (nlong > 0) ? ((int)blockIdx.x < nlong ? (1 << 30) : (int)gridDim.x - nlong) : (int)gridDim.x;
+  // this workgroup's walk through the item list: w = b, b + step, ...
+  const int step = (int)gridDim.x;
 
   // ---------------- producer ----------------
   // chunk P = it*512 + tid of a half-image: row = P >> 4 = it*32 + (tid >> 4), physical 16-B chunk c = P & 15; physical 32-B block
   // c >> 1 holds logical block (c >> 1) ^ f(row), f(row) = (row & 3) | ((row >> 3) & 1) << 2 -- independent of `it`
   const int srow = tid >> 4, sc = tid & 15;
-  const int sf = M32 ? ((srow & 3) << 1) : ((srow & 3) | (((srow >> 3) & 1) << 2));
+  const int sf = (srow & 3) | (((srow >> 3) & 1) << 2);
   const int lc = ((((sc >> 1) ^ sf) << 1) | (sc & 1)) * 8;      // logical column offset inside the 128-wide half-image
   __amdgpu_buffer_rsrc_t rsA, rsB;
   int ldaB = 0, ldbB = 0, clampA = 0, clampB = 0, rowA = 0, rowB = 0;
@@ -213,7 +182,7 @@ __global__ __launch_bounds__(512, 2) void gemm_tn8_kernel(const Tn8Group grp, co
   };
   auto advance = [&]() {
     if (++kt_p == nk_p) {
-      const int w_next = (step >= (1 << 30)) ? nitems : w_p + step;
+      const int w_next = w_p + step;
       if (w_next < nitems) {
         kt_p = 0;
         w_p = w_next;
@@ -231,26 +200,22 @@ __global__ __launch_bounds__(512, 2) void gemm_tn8_kernel(const Tn8Group grp, co
   using W3 = std::integral_constant<int, 2>;
 
   // ---------------- consumer ----------------
-  // fragments: A index i * KS + s (i: 16- / 32-column block of the wave's 64 A columns, s: k-step), B index j * KS + s
-  constexpr int NI = M32 ? 2 : 4, NJ = M32 ? 1 : 2, KS = M32 ? 4 : 2, KROWS = M32 ? 16 : 32;
-  typedef __attribute__((ext_vector_type(16))) float f32x16;
-  typedef typename std::conditional<M32, f32x16, f32x4>::type acc_t;
-  acc_t acc[2 * NI][2 * NJ];
+  // fragments: A index i * KS + s (i: 16-column block of the wave's 64 A columns, s: k-step), B index j * KS + s
+  constexpr int NI = 4, NJ = 2, KS = 2, KROWS = 32;
+  f32x4 acc[2 * NI][2 * NJ];
   s16x4 alo[NI * KS], ahi[NI * KS], blo[NJ * KS], bhi[NJ * KS];
   float csum[2 * NI];
   const int L = lane & 15, g = lane >> 4;
-  const int kh = M32 ? (g >> 1) : g;           // which 8-row group of a k-step this lane's fragment elements come from
-  const int e16 = M32 ? (g & 1) : 0;           // M32: which 16-column half of the 32-column block
-  const int fl = M32 ? ((L >> 2) << 1) : ((L >> 2) | ((g & 1) << 2));
+  const int fl = (L >> 2) | ((g & 1) << 2);    // (g: which 8-row group of a k-step this lane's fragment elements come from)
   const uint32_t lds0 = (uint32_t)(uintptr_t)LDS_PTR(smem);
-  const uint32_t lane_off = lds0 + (uint32_t)((8 * kh + (L >> 2)) * 256 + (L & 3) * 8);   // + KROWS*256*s, + 4*256 for the high half
+  const uint32_t lane_off = lds0 + (uint32_t)((8 * g + (L >> 2)) * 256 + (L & 3) * 8);   // + KROWS*256*s, + 4*256 for the high half
   uint32_t a_fo[NI], b_fo[NJ];
 #pragma unroll
   for (int i = 0; i < NI; ++i)
-    a_fo[i] = lane_off + (uint32_t)(((M32 ? 2 * (wm * 2 + i) + e16 : wm * 4 + i) ^ fl) << 5);
+    a_fo[i] = lane_off + (uint32_t)(((wm * 4 + i) ^ fl) << 5);
 #pragma unroll
   for (int j = 0; j < NJ; ++j)
-    b_fo[j] = lane_off + (uint32_t)(OFF_B0 + (((M32 ? 2 * wn + e16 : wn * 2 + j) ^ fl) << 5));
+    b_fo[j] = lane_off + (uint32_t)(OFF_B0 + (((wn * 2 + j) ^ fl) << 5));
 
   auto read_a = [&](auto buf_c, auto half_c) {
     if constexpr ((ABL & 2) != 0) return;
@@ -262,12 +227,6 @@ __global__ __launch_bounds__(512, 2) void gemm_tn8_kernel(const Tn8Group grp, co
       tn8_tr_read<4 * 256>(ahi[i * KS + 0], v);
       tn8_tr_read<KROWS * 256>(alo[i * KS + 1], v);
       tn8_tr_read<KROWS * 256 + 4 * 256>(ahi[i * KS + 1], v);
-      if constexpr (M32) {
-        tn8_tr_read<2 * KROWS * 256>(alo[i * KS + 2], v);
-        tn8_tr_read<2 * KROWS * 256 + 4 * 256>(ahi[i * KS + 2], v);
-        tn8_tr_read<3 * KROWS * 256>(alo[i * KS + 3], v);
-        tn8_tr_read<3 * KROWS * 256 + 4 * 256>(ahi[i * KS + 3], v);
-      }
     }
   };
   auto read_b = [&](auto buf_c, auto half_c) {
@@ -280,19 +239,13 @@ __global__ __launch_bounds__(512, 2) void gemm_tn8_kernel(const Tn8Group grp, co
       tn8_tr_read<4 * 256>(bhi[j * KS + 0], v);
       tn8_tr_read<KROWS * 256>(blo[j * KS + 1], v);
       tn8_tr_read<KROWS * 256 + 4 * 256>(bhi[j * KS + 1], v);
-      if constexpr (M32) {
-        tn8_tr_read<2 * KROWS * 256>(blo[j * KS + 2], v);
-        tn8_tr_read<2 * KROWS * 256 + 4 * 256>(bhi[j * KS + 2], v);
-        tn8_tr_read<3 * KROWS * 256>(blo[j * KS + 3], v);
-        tn8_tr_read<3 * KROWS * 256 + 4 * 256>(bhi[j * KS + 3], v);
-      }
     }
   };
   bool do_colsum = false;
   auto compute = [&](auto ha_c, auto hb_c, auto cs_c) {
     constexpr int HA = decltype(ha_c)::value, HB_ = decltype(hb_c)::value;
     constexpr bool CS = decltype(cs_c)::value;      // this phase holds freshly read A fragments: column sums are taken here
-    // (both forms hold 8 A and 4 B fragment register pairs x {lo, hi})
+    // (8 A and 4 B fragment register pairs x {lo, hi})
     asm volatile("s_waitcnt lgkmcnt(0)"
                  : "+v"(alo[0]), "+v"(ahi[0]), "+v"(alo[1]), "+v"(ahi[1]), "+v"(alo[2]), "+v"(ahi[2]), "+v"(alo[3]), "+v"(ahi[3]),
                    "+v"(alo[4]), "+v"(ahi[4]), "+v"(alo[5]), "+v"(ahi[5]), "+v"(alo[6]), "+v"(ahi[6]), "+v"(alo[7]), "+v"(ahi[7]),
@@ -305,14 +258,9 @@ __global__ __launch_bounds__(512, 2) void gemm_tn8_kernel(const Tn8Group grp, co
 #pragma unroll
         for (int i = 0; i < NI; ++i)
 #pragma unroll
-          for (int j = 0; j < NJ; ++j) {
-            if constexpr (M32)
-              acc[HA * NI + i][HB_ * NJ + j] = VLB_MFMA_32x32x16(tn8_frag(blo[j * KS + s], bhi[j * KS + s]), tn8_frag(alo[i * KS + s], ahi[i * KS + s]),
-                                                                 acc[HA * NI + i][HB_ * NJ + j], 0, 0, 0);
-            else
-              acc[HA * NI + i][HB_ * NJ + j] = VLB_MFMA_16x16x32(tn8_frag(blo[j * KS + s], bhi[j * KS + s]), tn8_frag(alo[i * KS + s], ahi[i * KS + s]),
-                                                                 acc[HA * NI + i][HB_ * NJ + j], 0, 0, 0);
-          }
+          for (int j = 0; j < NJ; ++j)
+            acc[HA * NI + i][HB_ * NJ + j] = VLB_MFMA_16x16x32(tn8_frag(blo[j * KS + s], bhi[j * KS + s]), tn8_frag(alo[i * KS + s], ahi[i * KS + s]),
+                                                               acc[HA * NI + i][HB_ * NJ + j], 0, 0, 0);
       __builtin_amdgcn_s_setprio(0);
     }
     if constexpr (CS) {
@@ -347,7 +295,7 @@ __global__ __launch_bounds__(512, 2) void gemm_tn8_kernel(const Tn8Group grp, co
   if (wm == 1) tn8_barrier();
 
   int gk = 0;      // K tiles consumed by this workgroup so far
-  for (int w = blockIdx.x; w < nitems; w = (step >= (1 << 30)) ? nitems : w + step) {
+  for (int w = blockIdx.x; w < nitems; w += step) {
     int gi, m0, n0, kt0, nk;
     item_of(w, gi, m0, n0, kt0, nk);
     float* const colsum = D(gi).colsum;
@@ -359,15 +307,9 @@ __global__ __launch_bounds__(512, 2) void gemm_tn8_kernel(const Tn8Group grp, co
     for (int i = 0; i < 2 * NI; ++i) {
       csum[i] = 0.f;
 #pragma unroll
-      for (int j = 0; j < 2 * NJ; ++j) {
-        if constexpr (M32) {
+      for (int j = 0; j < 2 * NJ; ++j)
 #pragma unroll
-          for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-        } else {
-#pragma unroll
-          for (int r = 0; r < 4; ++r) acc[i][j][r] = 0.f;
-        }
-      }
+        for (int r = 0; r < 4; ++r) acc[i][j][r] = 0.f;
     }
     for (int kt = 0; kt < nk; kt += 2, gk += 2) {
       do_colsum = (colsum != nullptr) && (cs_wait == 0);
@@ -427,41 +369,35 @@ __global__ __launch_bounds__(512, 2) void gemm_tn8_kernel(const Tn8Group grp, co
     // (no LDS involved: the operand stream of the next item keeps landing; the wave groups need no re-alignment)
     {
       const Tn8Desc d = D(gi);
-      const int sp = kt0 / d.kt_per_split;      // kt0 = slice x kt_per_split in both item lists
+      const int sp = kt0 / d.kt_per_split;      // kt0 = slice x kt_per_split
       float* const C = d.C + (long)sp * d.c_split_stride;
       const bool accum = d.accumulate != 0;
       const int Mo = d.Mo, No = d.No;
       const long ldc = d.ldc;
       const float* const rowscale = d.rowscale;
-      // output fragment (fi, cj, q): row m (one per lane), 4 consecutive columns from n
-      //   16x16 form: fi < 8 (tile half x 16-row fragment), cj < 4, q = 0:      m = .. + (fi & 3) * 16 + L,       n = .. + (cj & 1) * 16 + 4 g
-      //   32x32 form: fi < 4 (tile half x 32-row block),    cj < 2, q < 4:      m = .. + (fi & 1) * 32 + lane&31, n = .. + 8 q + 4 (lane >> 5)
-      constexpr int NQ = M32 ? 4 : 1;
+      // output fragment (fi, cj): row m (one per lane), 4 consecutive columns from n; fi < 8 (tile half x 16-row fragment), cj < 4
 #pragma unroll
       for (int fi = 0; fi < 2 * NI; ++fi) {
-        const int m = M32 ? m0 + (fi >> 1) * 128 + wm * 64 + (fi & 1) * 32 + (lane & 31) : m0 + (fi >> 2) * 128 + wm * 64 + (fi & 3) * 16 + L;
+        const int m = m0 + (fi >> 2) * 128 + wm * 64 + (fi & 3) * 16 + L;
         if (m >= Mo) continue;
         const float rs = rowscale ? rowscale[m] : 1.0f;
 #pragma unroll
         for (int cj = 0; cj < 2 * NJ; ++cj) {
-#pragma unroll
-          for (int q = 0; q < NQ; ++q) {
-            const int n = M32 ? n0 + cj * 128 + wn * 32 + 8 * q + 4 * (lane >> 5) : n0 + (cj >> 1) * 128 + wn * 32 + (cj & 1) * 16 + 4 * g;
-            if (n >= No) continue;
-            float* c = C + (long)m * ldc + n;
-            f32x4 v = (f32x4){acc[fi][cj][4 * q + 0], acc[fi][cj][4 * q + 1], acc[fi][cj][4 * q + 2], acc[fi][cj][4 * q + 3]};
-            if (rowscale) v = (f32x4){v[0] * rs, v[1] * rs, v[2] * rs, v[3] * rs};
-            if (n + 3 < No) {
-              float4 o4 = make_float4(v[0], v[1], v[2], v[3]);
-              if (accum) {
-                const float4 o = *(const float4*)c;
-                o4 = make_float4(o.x + v[0], o.y + v[1], o.z + v[2], o.w + v[3]);
-              }
-              if (d.c_split_stride == 0) vlb_store_nt((float4*)c, o4);      // the gradient itself (next read by the optimizer): streaming store
-              else *(float4*)c = o4;                                          // a K-slice slab: re-read by the reduce kernel right away
-            } else {
-              for (int r = 0; r < 4 && n + r < No; ++r) c[r] = accum ? c[r] + v[r] : v[r];
+          const int n = n0 + (cj >> 1) * 128 + wn * 32 + (cj & 1) * 16 + 4 * g;
+          if (n >= No) continue;
+          float* c = C + (long)m * ldc + n;
+          f32x4 v = acc[fi][cj];
+          if (rowscale) v = (f32x4){v[0] * rs, v[1] * rs, v[2] * rs, v[3] * rs};
+          if (n + 3 < No) {
+            float4 o4 = make_float4(v[0], v[1], v[2], v[3]);
+            if (accum) {
+              const float4 o = *(const float4*)c;
+              o4 = make_float4(o.x + v[0], o.y + v[1], o.z + v[2], o.w + v[3]);
             }
+            if (d.c_split_stride == 0) vlb_store_nt((float4*)c, o4);      // the gradient itself (next read by the optimizer): streaming store
+            else *(float4*)c = o4;                                          // a K-slice slab: re-read by the reduce kernel right away
+          } else {
+            for (int r = 0; r < 4 && n + r < No; ++r) c[r] = accum ? c[r] + v[r] : v[r];
           }
         }
       }
@@ -469,14 +405,10 @@ __global__ __launch_bounds__(512, 2) void gemm_tn8_kernel(const Tn8Group grp, co
 #pragma unroll
         for (int fi = 0; fi < 2 * NI; ++fi) {
           float v = csum[fi];
-          if constexpr (M32) {
-            v += __shfl_xor(v, 32, 64);
-          } else {
-            v += __shfl_xor(v, 16, 64);
-            v += __shfl_xor(v, 32, 64);
-          }
-          const int m = M32 ? m0 + (fi >> 1) * 128 + wm * 64 + (fi & 1) * 32 + (lane & 31) : m0 + (fi >> 2) * 128 + wm * 64 + (fi & 3) * 16 + L;
-          if (kh == 0 && m < D(gi).Mo) atomicAdd(colsum + m, v);
+          v += __shfl_xor(v, 16, 64);
+          v += __shfl_xor(v, 32, 64);
+          const int m = m0 + (fi >> 2) * 128 + wm * 64 + (fi & 3) * 16 + L;
+          if (g == 0 && m < D(gi).Mo) atomicAdd(colsum + m, v);
         }
       }
     }
@@ -523,40 +455,38 @@ static int tile_group_for(int ntm, int ntn) {
   return group > 0 ? (group < ntm ? group : ntm) : vlb_square_tile_group(ntm, ntn);
 }
 
-template <bool TABLE, bool M32, int ABL>
+template <bool TABLE, int ABL>
 static int tn8_launch_k(Tn8Group& grp, const Tn8Desc* tab, int gx, hipStream_t stream) {
   constexpr int smem = 131072;
   static bool attr_set = false;
   if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute((const void*)gemm_tn8_kernel<TABLE, M32, ABL>, hipFuncAttributeMaxDynamicSharedMemorySize, smem);
+    hipError_t e = hipFuncSetAttribute((const void*)gemm_tn8_kernel<TABLE, ABL>, hipFuncAttributeMaxDynamicSharedMemorySize, smem);
     if (e != hipSuccess) {
       vlb_set_error("gemm_tn8: cannot reserve %d bytes of LDS: %s", smem, hipGetErrorString(e));
       return VLB_ERR_HIP;
     }
     attr_set = true;
   }
-  hipLaunchKernelGGL((gemm_tn8_kernel<TABLE, M32, ABL>), dim3(gx), dim3(512), smem, stream, grp, tab);
+  hipLaunchKernelGGL((gemm_tn8_kernel<TABLE, ABL>), dim3(gx), dim3(512), smem, stream, grp, tab);
   VLB_CHECK_LAUNCH("vlb_wgrad_tn_bf16(tn8)");
   return VLB_OK;
 }
 
 template <bool TABLE>
 static int tn8_launch_t(Tn8Group& grp, const Tn8Desc* tab, hipStream_t stream) {
-  const int wgs = vlb_opt(VLB_OPT_TN8_WGS), m32 = vlb_opt(VLB_OPT_TN8_M32);
+  const int wgs = vlb_opt(VLB_OPT_TN8_WGS);
   const int cap = (wgs >= 8 && wgs <= 256) ? wgs : 256;
   const int gx = grp.nitems > cap ? cap : grp.nitems;
   grp.stamps = g_tn8_stamps;
 #ifdef VLB_TN8_PROBE
   if (const int ablate = vlb_opt(VLB_OPT_TN8_ABLATE); !TABLE && ablate) {
-#define TN8_ABL(M, A) \
-  if ((m32 != 0) == (M != 0) && (ablate & 15) == A) return tn8_launch_k<false, M != 0, A>(grp, tab, gx, stream);
-#define TN8_ABLS(M) TN8_ABL(M, 1) TN8_ABL(M, 2) TN8_ABL(M, 3) TN8_ABL(M, 4) TN8_ABL(M, 5) TN8_ABL(M, 6) TN8_ABL(M, 8) TN8_ABL(M, 12) TN8_ABL(M, 14)
-    TN8_ABLS(0) TN8_ABLS(1)
-#undef TN8_ABLS
+#define TN8_ABL(A) \
+  if ((ablate & 15) == A) return tn8_launch_k<false, A>(grp, tab, gx, stream);
+    TN8_ABL(1) TN8_ABL(2) TN8_ABL(3) TN8_ABL(4) TN8_ABL(5) TN8_ABL(6) TN8_ABL(8) TN8_ABL(12) TN8_ABL(14)
 #undef TN8_ABL
   }
 #endif
-  return m32 ? tn8_launch_k<TABLE, true, 0>(grp, tab, gx, stream) : tn8_launch_k<TABLE, false, 0>(grp, tab, gx, stream);
+  return tn8_launch_k<TABLE, 0>(grp, tab, gx, stream);
 }
 
 static int tn8_launch(Tn8Group& grp, hipStream_t stream) { return tn8_launch_t<false>(grp, nullptr, stream); }
@@ -618,27 +548,11 @@ int vlb_gemm_tn8_group(int n, const void* const* A, const long* lda, const void*
   if (splits < 1) splits = 1;
   if (splits > pairs) splits = pairs;
   if (tiles * splits < 128) return 0;
-  int per = vlb_cdiv(pairs, splits);
+  const int per = vlb_cdiv(pairs, splits);
   splits = vlb_cdiv(pairs, per);
-  // uneven three-way cut (see Tn8Group): two long slices of L pairs per tile, one workgroup each, and a remainder of pairs - 2 L
-  // shared by the 256 - 2 T spare workgroups, k = ceil(T / spare) remainders each; L minimises max(L, k x remainder)
-  int nlong = 0;
-  long slab_floats = 0;
-  for (int i = 0; i < n; ++i) slab_floats += (long)Mo[i] * ((No[i] + 3) / 4 * 4);
-  if (vlb_opt(VLB_OPT_TN8_UNEVEN) && splits == 2 && 2 * tiles < 256 && workspace && 3 * slab_floats <= workspace_floats &&
-      vlb_opt(VLB_OPT_TN8_WGS) == 256) {
-    const int spare = 256 - 2 * (int)tiles, k = vlb_cdiv((int)tiles, spare);
-    const int L = vlb_cdiv(k * pairs, 2 * k + 1), rem = pairs - 2 * L;
-    const int makespan = L > k * rem ? L : k * rem;
-    if (rem >= 1 && L >= 1 && makespan * 100 <= per * 95) {      // worth a third slab per tile only for >= 5 %
-      nlong = 2 * (int)tiles;
-      per = L;
-      splits = 3;
-    }
-  }
   Tn8Group grp = {};
   long off = 0;
-  int item = 0, sitem = 0;
+  int item = 0;
   for (int i = 0; i < n; ++i) {
     Tn8Desc& d = grp.d[i];
     const long ldw = (No[i] + 3) / 4 * 4;
@@ -646,11 +560,8 @@ int vlb_gemm_tn8_group(int n, const void* const* A, const long* lda, const void*
     d.lda = (int)lda[i]; d.ldb = (int)ldb[i]; d.Mo = Mo[i]; d.No = No[i]; d.R = R;
     d.ntm = vlb_cdiv(Mo[i], 256); d.ntn = vlb_cdiv(No[i], 256); d.tile_group = tile_group_for(d.ntm, d.ntn);
     d.nsplit = splits; d.kt_per_split = per * 2;
-    const int ntile = d.ntm * d.ntn;
-    d.item0 = item; d.nitems = ntile * (nlong ? 2 : splits);      // (uneven: the two long slices; the remainders follow all of them)
-    d.short0 = sitem;
+    d.item0 = item; d.nitems = d.ntm * d.ntn * splits;
     item += d.nitems;
-    sitem += ntile;
     if (splits > 1) {
       d.C = workspace + off; d.ldc = (int)ldw; d.c_split_stride = (long)Mo[i] * ldw; d.accumulate = 0;
       ws_off[i] = off;
@@ -661,8 +572,6 @@ int vlb_gemm_tn8_group(int n, const void* const* A, const long* lda, const void*
     }
     slices[i] = splits;
   }
-  if (nlong) item += sitem;
-  grp.nlong = nlong;
   if (splits > 1 && (!workspace || off > workspace_floats)) return 0;
   grp.n = n; grp.nitems = item;
   const int rc = tn8_launch(grp, stream);
@@ -698,7 +607,7 @@ extern "C" int vlb_wgrad_tn_table_pack(int n, const void* const* A, const long* 
     d.lda = (int)lda[i]; d.ldb = (int)ldb[i]; d.ldc = (int)ldc[i]; d.Mo = Mo[i]; d.No = No[i]; d.R = R[i];
     d.ntm = vlb_cdiv(Mo[i], 256); d.ntn = vlb_cdiv(No[i], 256); d.tile_group = tile_group_for(d.ntm, d.ntn);
     d.nsplit = 1; d.kt_per_split = R[i] / 64; d.c_split_stride = 0; d.accumulate = accumulate ? 1 : 0;
-    d.item0 = item; d.nitems = d.ntm * d.ntn; d.short0 = 0;
+    d.item0 = item; d.nitems = d.ntm * d.ntn;
     item += d.nitems;
     out[i] = d;
   }
@@ -708,6 +617,6 @@ extern "C" int vlb_wgrad_tn_table_pack(int n, const void* const* A, const long* 
 extern "C" int vlb_wgrad_tn_table_launch(const void* desc_dev, int n, int nitems, hipStream_t stream) {
   VLB_CHECK_ARG(desc_dev && n >= 1 && nitems >= 1, "vlb_wgrad_tn_table_launch: bad argument");
   Tn8Group grp = {};
-  grp.n = n; grp.nitems = nitems; grp.nlong = 0;
+  grp.n = n; grp.nitems = nitems;
   return tn8_launch_t<true>(grp, (const Tn8Desc*)desc_dev, stream);
 }

@@ -149,181 +149,8 @@ __global__ __launch_bounds__(256) void layernorm_fwd_kernel(const bf16_t* __rest
 // flows into the dense layer *before* its dropout; idx = row*H + col matches the GEMM epilogue),
 // dx_acc fp32 (atomicAdd; used when several rows alias one input row, e.g. the broadcast
 // text_visual_embeddings of pretrain/modules/resnet_vlbert_for_pretraining.py:132-135).
-// Lane layout: 16-B accesses, lane owns columns (lane + 64 i) * 8 .. +7 (H = 768: one full pass + one half-wave
-// pass); two rows per wave iteration with all four row loads issued before the first reduction.
-template <int NP>
-struct Row8 {
-  float v[NP][8];
-};
-
-template <int NP>
-__device__ __forceinline__ void load_row8_bf16(const bf16_t* x, int H, int lane, Row8<NP>& r, bool f16 = false) {
-  uint4 w[NP];
-#pragma unroll
-  for (int i = 0; i < NP; ++i) w[i] = *(const uint4*)(x + min((lane + 64 * i) * 8, H - 8));      // unconditional (see load_row_bf16)
-  if (f16) {
-#pragma unroll
-    for (int i = 0; i < NP; ++i) {
-      const bool in = (lane + 64 * i) * 8 < H;
-      const uint32_t u[4] = {w[i].x, w[i].y, w[i].z, w[i].w};
-#pragma unroll
-      for (int k = 0; k < 4; ++k) { r.v[i][2 * k] = in ? hlo(u[k]) : 0.f; r.v[i][2 * k + 1] = in ? hhi(u[k]) : 0.f; }
-    }
-  } else {
-#pragma unroll
-    for (int i = 0; i < NP; ++i) {
-      const bool in = (lane + 64 * i) * 8 < H;
-      const uint32_t u[4] = {w[i].x, w[i].y, w[i].z, w[i].w};
-#pragma unroll
-      for (int k = 0; k < 4; ++k) { r.v[i][2 * k] = in ? bflo(u[k]) : 0.f; r.v[i][2 * k + 1] = in ? bfhi(u[k]) : 0.f; }
-    }
-  }
-}
-
-template <int NP>
-__global__ __launch_bounds__(256) void layernorm_bwd_kernel(const void* __restrict__ dy_, long lddy, int dy_f32, const bf16_t* __restrict__ x,
-                                                            long ldx, const float* __restrict__ stats, const float* __restrict__ gamma,
-                                                            bf16_t* __restrict__ dx, long lddx, bf16_t* __restrict__ dx_drop, long lddd,
-                                                            uint32_t drop_thr, float drop_scale, const uint32_t* __restrict__ seedp,
-                                                            uint32_t tag, float* __restrict__ dx_acc, long ldacc, float* __restrict__ dgamma,
-                                                            float* __restrict__ dbeta, float* __restrict__ ws, int rows, int H, int x_f16) {
-  extern __shared__ __attribute__((aligned(16))) float red[];  // [4 waves][2][LW] per-wave partial dgamma / dbeta (lane-major)
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const uint32_t seed = (drop_thr && seedp) ? *seedp : 0u;
-  const bool want_gb = (dgamma != nullptr) || (dbeta != nullptr);
-  float gsum[NP][8], bsum[NP][8], gam[NP][8];
-#pragma unroll
-  for (int i = 0; i < NP; ++i) {
-    const int c = (lane + 64 * i) * 8;
-    float4 g0 = make_float4(0.f, 0.f, 0.f, 0.f), g1 = g0;
-    if (c < H) { g0 = *(const float4*)(gamma + c); g1 = *(const float4*)(gamma + c + 4); }
-    gam[i][0] = g0.x; gam[i][1] = g0.y; gam[i][2] = g0.z; gam[i][3] = g0.w;
-    gam[i][4] = g1.x; gam[i][5] = g1.y; gam[i][6] = g1.z; gam[i][7] = g1.w;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) gsum[i][k] = bsum[i][k] = 0.f;
-  }
-
-  const int nw = blockDim.x >> 6, step = gridDim.x * nw;
-  for (int row0 = blockIdx.x * nw + wave; row0 < rows; row0 += 2 * step) {
-    const int row1 = row0 + step;
-    const bool has1 = row1 < rows;
-    Row8<NP> xr[2], dyr[2];
-    float mean[2], rstd[2];
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-      const int row = t ? (has1 ? row1 : row0) : row0;
-      load_row8_bf16(x + (long)row * ldx, H, lane, xr[t], x_f16 != 0);
-      if (dy_f32) {
-        const float* d = (const float*)dy_ + (long)row * lddy;
-#pragma unroll
-        for (int i = 0; i < NP; ++i) {
-          const int c = (lane + 64 * i) * 8;
-          float4 v0 = make_float4(0.f, 0.f, 0.f, 0.f), v1 = v0;
-          if (c < H) { v0 = *(const float4*)(d + c); v1 = *(const float4*)(d + c + 4); }
-          dyr[t].v[i][0] = v0.x; dyr[t].v[i][1] = v0.y; dyr[t].v[i][2] = v0.z; dyr[t].v[i][3] = v0.w;
-          dyr[t].v[i][4] = v1.x; dyr[t].v[i][5] = v1.y; dyr[t].v[i][6] = v1.z; dyr[t].v[i][7] = v1.w;
-        }
-      } else {
-        load_row8_bf16((const bf16_t*)dy_ + (long)row * lddy, H, lane, dyr[t]);
-      }
-      const float2 ms = *(const float2*)(stats + 2 * (long)row);
-      mean[t] = ms.x;
-      rstd[t] = ms.y;
-    }
-    float s1[2] = {0.f, 0.f}, s2[2] = {0.f, 0.f};
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-      const float live = (t == 0 || has1) ? 1.f : 0.f;   // the duplicate of row0 must not count twice
-#pragma unroll
-      for (int i = 0; i < NP; ++i) {
-        const bool in = (lane + 64 * i) * 8 < H;         // out-of-range lanes hold zeros for dy: only xhat needs masking
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-          const float xh = in ? (xr[t].v[i][k] - mean[t]) * rstd[t] : 0.f;
-          const float dyv = dyr[t].v[i][k] * live;
-          gsum[i][k] += dyv * xh;
-          bsum[i][k] += dyv;
-          const float gv = dyv * gam[i][k];
-          s1[t] += gv;
-          s2[t] += gv * xh;
-          xr[t].v[i][k] = xh;   // reuse storage: xhat
-          dyr[t].v[i][k] = gv;  // reuse storage: g
-        }
-      }
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {   // four independent butterflies interleaved
-      s1[0] += __shfl_xor(s1[0], o, 64); s2[0] += __shfl_xor(s2[0], o, 64);
-      s1[1] += __shfl_xor(s1[1], o, 64); s2[1] += __shfl_xor(s2[1], o, 64);
-    }
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-      if (t == 1 && !has1) break;
-      const int row = t ? row1 : row0;
-      const float m1 = s1[t] / (float)H, m2 = s2[t] / (float)H;
-#pragma unroll
-      for (int i = 0; i < NP; ++i) {
-        const int c = (lane + 64 * i) * 8;
-        if (c < H) {
-          float o[8];
-#pragma unroll
-          for (int k = 0; k < 8; ++k) o[k] = rstd[t] * (dyr[t].v[i][k] - m1 - xr[t].v[i][k] * m2);
-          if (dx) *(uint4*)(dx + (long)row * lddx + c) = make_uint4(pack2bf(o[0], o[1]), pack2bf(o[2], o[3]), pack2bf(o[4], o[5]), pack2bf(o[6], o[7]));
-          if (dx_drop) {
-            float d[8];
-            if (drop_thr) {
-              const uint32_t idx = (uint32_t)row * (uint32_t)H + (uint32_t)c;  // H%8==0 -> idx even
-#pragma unroll
-              for (int q = 0; q < 4; ++q) {
-                const uint32_t h = vlb_rng_pair(seed, tag, (idx >> 1) + q);
-                d[2 * q] = ((h & 0xffffu) >= drop_thr) ? o[2 * q] * drop_scale : 0.f;
-                d[2 * q + 1] = ((h >> 16) >= drop_thr) ? o[2 * q + 1] * drop_scale : 0.f;
-              }
-            } else {
-#pragma unroll
-              for (int k = 0; k < 8; ++k) d[k] = o[k];
-            }
-            *(uint4*)(dx_drop + (long)row * lddd + c) = make_uint4(pack2bf(d[0], d[1]), pack2bf(d[2], d[3]), pack2bf(d[4], d[5]), pack2bf(d[6], d[7]));
-          }
-          if (dx_acc) {
-#pragma unroll
-            for (int k = 0; k < 8; ++k) atomicAdd(dx_acc + (long)row * ldacc + c + k, o[k]);
-          }
-        }
-      }
-    }
-  }
-  if (!want_gb) return;
-  // Per-wave partials -> LDS in LANE-MAJOR order (element (i,k) of lane l at (i*8+k)*64 + l: conflict-free plain stores,
-  // no LDS atomics -- the natural column order has lanes 8 floats apart = 16-way bank conflicts), summed over the 4 waves
-  // by the whole workgroup in the same order.  q -> column: ln_col_of().
-  constexpr int LW = NP * 512;
-  float* mine = red + wave * 2 * LW;
-#pragma unroll
-  for (int i = 0; i < NP; ++i)
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      mine[(i * 8 + k) * 64 + lane] = gsum[i][k];
-      mine[LW + (i * 8 + k) * 64 + lane] = bsum[i][k];
-    }
-  __syncthreads();
-  for (int q = threadIdx.x; q < 2 * LW; q += 256) {
-    const float v = (red[q] + red[2 * LW + q]) + (red[4 * LW + q] + red[6 * LW + q]);
-    if (ws) ws[(long)blockIdx.x * 2 * LW + q] = v;   // partial vector of this workgroup; ln_param_finalize_kernel column-sums them
-    else red[q] = v;                                  // (only this thread reads red[q])
-  }
-  if (ws) return;
-  __syncthreads();
-  for (int c = threadIdx.x; c < 2 * H; c += 256) {    // no workspace: coalesced atomics in natural column order
-    const int which = c >= H, col = c - which * H, chunk = col >> 3;
-    const float v = red[which * LW + (((chunk >> 6) * 8 + (col & 7)) << 6) + (chunk & 63)];
-    float* dst = which ? dbeta : dgamma;
-    if (dst) atomicAdd(dst + col, v);
-  }
-}
-
-// The same backward with 4-column (8-B) lane chunks -- the forward's mapping: a lane owns columns (lane + 64 i) * 4 .. +3.
-// H = 768 is then three FULL passes (the 8-column form above runs one full and one half-wave pass and keeps 16 values per
+// Lane layout: 4-column (8-B) lane chunks -- the forward's mapping: a lane owns columns (lane + 64 i) * 4 .. +3.
+// H = 768 is then three FULL passes (an 8-column form, removed, ran one full and one half-wave pass and kept 16 values per
 // array per lane: 192 VGPRs, 2 waves per SIMD -- too few bytes in flight for a kernel that only streams: 2.8 TB/s measured);
 // here the footprint is 12 values per array, two rows in flight, <= 128 VGPRs -> 4 waves per SIMD.
 // Partial dgamma / dbeta vectors are lane-major with LW = NIT * 256: element (i, k) of lane l at (i*4 + k)*64 + l.
@@ -498,7 +325,7 @@ __device__ __forceinline__ float ln_slab_colsum(const float* __restrict__ ws, in
 
 // dgamma/dbeta += column sums of the `nslab` lane-major partial vectors [2][LW]: grid (2 LW / 64, 8)
 __global__ __launch_bounds__(256) void ln_param_finalize_kernel(const float* __restrict__ ws, int nslab, int LW, float* __restrict__ dgamma,
-                                                                float* __restrict__ dbeta, int H, int cpl_log2) {
+                                                                float* __restrict__ dbeta, int H) {
   __shared__ float part[4][64];
   const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
   const int q = blockIdx.x * 64 + tx;
@@ -507,8 +334,8 @@ __global__ __launch_bounds__(256) void ln_param_finalize_kernel(const float* __r
   __syncthreads();
   if (ty == 0) {
     s = (part[0][tx] + part[1][tx]) + (part[2][tx] + part[3][tx]);
-    const int r = q % LW, cpl = 1 << cpl_log2;      // columns per lane chunk: 8 (layernorm_bwd_kernel) or 4 (layernorm_bwd4_kernel)
-    const int col = ((r & 63) + 64 * (r >> (6 + cpl_log2))) * cpl + ((r >> 6) & (cpl - 1));
+    const int r = q % LW;      // element (i, k) of lane l sits at (i*4 + k)*64 + l and is column (l + 64 i) * 4 + k
+    const int col = ((r & 63) + 64 * (r >> 8)) * 4 + ((r >> 6) & 3);
     if (col < H) {
       if (q < LW) { if (dgamma) atomicAdd(dgamma + col, s); }
       else if (dbeta) atomicAdd(dbeta + col, s);
@@ -566,16 +393,10 @@ static int ln_bwd_blocks(int rows) {
   return blocks;
 }
 
-static void ln_lw(int H, int& LW, int& cpl_log2) {
-  if (vlb_opt(VLB_OPT_LN_BWD4)) {
-    const int nit = vlb_cdiv(H, 256);
-    LW = (nit <= 4 ? nit : 8) * 256;
-    cpl_log2 = 2;
-  } else {
-    const int np = vlb_cdiv(H, 512);
-    LW = (np <= 3 ? np : 4) * 512;
-    cpl_log2 = 3;
-  }
+// length of one partial dgamma (or dbeta) vector of layernorm_bwd4_kernel<NIT, .>
+static int ln_lw(int H) {
+  const int nit = vlb_cdiv(H, 256);
+  return (nit <= 4 ? nit : 8) * 256;
 }
 
 static int ln_bwd_impl(const void* dy, long lddy, int dy_f32, const void* x, long ldx, const float* stats,
@@ -588,13 +409,11 @@ static int ln_bwd_impl(const void* dy, long lddy, int dy_f32, const void* x, lon
                 "vlb_layernorm_bwd: row strides must be multiples of 8");
   VLB_CHECK_ARG(!(drop_p > 0.f) || seed, "vlb_layernorm_bwd: dropout needs a device seed pointer");
   VLB_CHECK_ARG((long)rows * H < (1L << 32) || !(drop_p > 0.f), "vlb_layernorm_bwd: dropout index overflow");
-  const int bwd4 = vlb_opt(VLB_OPT_LN_BWD4);
+  const bool rif2 = vlb_opt(VLB_OPT_LN_BWD4) == 2;
   const int blocks = ln_bwd_blocks(rows);
   float* ws = (workspace && (dgamma || dbeta) && blocks > 32) ? workspace : nullptr;
   const uint32_t thr = vlb_drop_thr(drop_p);
-  int LW, cpl_log2;
-  if (bwd4) {
-    const int nit = vlb_cdiv(H, 256);
+  const int nit = vlb_cdiv(H, 256);
 #define LN_BWD4(NIT, RIF)                                                                                                      \
   do {                                                                                                                          \
     constexpr size_t smem = (8 * NIT * 256 + 4 * NIT * 256) * sizeof(float);      /* reduction area + the lanes' gamma */          \
@@ -604,25 +423,16 @@ static int ln_bwd_impl(const void* dy, long lddy, int dy_f32, const void* x, lon
                        (const bf16_t*)x, ldx, stats, gamma, (bf16_t*)dx, lddx, (bf16_t*)dx_drop, lddd, thr, vlb_drop_scale(thr), \
                        seed, tag, dx_acc, ldacc, dgamma, dbeta, ws, rows, H, x_f16);                                             \
   } while (0)
-    // rows in flight per wave: 2 while the kernel stays near 128 VGPRs (4 waves per SIMD); ln_bwd4 == 2 forces 2 for H = 768 / 1024
-    if (nit <= 1) LN_BWD4(1, 2); else if (nit == 2) LN_BWD4(2, 2);
-    else if (nit == 3) { if (bwd4 == 2) LN_BWD4(3, 2); else LN_BWD4(3, 1); }
-    else if (nit == 4) { if (bwd4 == 2) LN_BWD4(4, 2); else LN_BWD4(4, 1); }
-    else LN_BWD4(8, 1);
+  // rows in flight per wave: 2 while the kernel stays near 128 VGPRs (4 waves per SIMD); ln_bwd4 == 2 forces 2 for H = 768 / 1024
+  if (nit <= 1) LN_BWD4(1, 2); else if (nit == 2) LN_BWD4(2, 2);
+  else if (nit == 3) { if (rif2) LN_BWD4(3, 2); else LN_BWD4(3, 1); }
+  else if (nit == 4) { if (rif2) LN_BWD4(4, 2); else LN_BWD4(4, 1); }
+  else LN_BWD4(8, 1);
 #undef LN_BWD4
-  } else {
-#define LN_BWD(NP)                                                                                                             \
-  hipLaunchKernelGGL(layernorm_bwd_kernel<NP>, dim3(blocks), dim3(256), 8 * NP * 512 * sizeof(float), stream, dy, lddy, dy_f32,  \
-                     (const bf16_t*)x, ldx, stats, gamma, (bf16_t*)dx, lddx, (bf16_t*)dx_drop, lddd, thr, vlb_drop_scale(thr),  \
-                     seed, tag, dx_acc, ldacc, dgamma, dbeta, ws, rows, H, x_f16)
-    const int np = vlb_cdiv(H, 512);
-    if (np <= 1) LN_BWD(1); else if (np == 2) LN_BWD(2); else if (np == 3) LN_BWD(3); else LN_BWD(4);
-#undef LN_BWD
-  }
-  ln_lw(H, LW, cpl_log2);
   VLB_CHECK_LAUNCH("vlb_layernorm_bwd");
   if (ws && finalize) {
-    hipLaunchKernelGGL(ln_param_finalize_kernel, dim3(2 * LW / 64, 8), dim3(256), 0, stream, ws, blocks, LW, dgamma, dbeta, H, cpl_log2);
+    const int LW = ln_lw(H);
+    hipLaunchKernelGGL(ln_param_finalize_kernel, dim3(2 * LW / 64, 8), dim3(256), 0, stream, ws, blocks, LW, dgamma, dbeta, H);
     VLB_CHECK_LAUNCH("vlb_layernorm_bwd(finalize)");
   }
   return VLB_OK;
@@ -663,7 +473,7 @@ struct LnFinalizeBatch {
   int nslab[32];
 };
 
-__global__ __launch_bounds__(256) void ln_param_finalize_batch_kernel(const LnFinalizeBatch b, int LW, int H, int cpl_log2) {
+__global__ __launch_bounds__(256) void ln_param_finalize_batch_kernel(const LnFinalizeBatch b, int LW, int H) {
   __shared__ float part[4][64];
   const int e = blockIdx.z;
   const float* ws = b.ws[e];
@@ -675,8 +485,8 @@ __global__ __launch_bounds__(256) void ln_param_finalize_batch_kernel(const LnFi
   __syncthreads();
   if (ty == 0) {
     s = (part[0][tx] + part[1][tx]) + (part[2][tx] + part[3][tx]);
-    const int r = q % LW, cpl = 1 << cpl_log2;
-    const int col = ((r & 63) + 64 * (r >> (6 + cpl_log2))) * cpl + ((r >> 6) & (cpl - 1));
+    const int r = q % LW;
+    const int col = ((r & 63) + 64 * (r >> 8)) * 4 + ((r >> 6) & 3);
     if (col < H) {
       if (q < LW) { if (b.dgamma[e]) atomicAdd(b.dgamma[e] + col, s); }
       else if (b.dbeta[e]) atomicAdd(b.dbeta[e] + col, s);
@@ -694,16 +504,13 @@ extern "C" int vlb_ln_param_finalize_batch(int n, const float* const* ws, const 
     VLB_CHECK_ARG(ws[i] && nslab[i] > 0, "vlb_ln_param_finalize_batch: entry %d has no partial vectors", i);
     b.ws[i] = ws[i]; b.nslab[i] = nslab[i]; b.dgamma[i] = dgamma[i]; b.dbeta[i] = dbeta[i];
   }
-  int LW, cpl_log2;
-  ln_lw(H, LW, cpl_log2);
-  hipLaunchKernelGGL(ln_param_finalize_batch_kernel, dim3(2 * LW / 64, 8, n), dim3(256), 0, stream, b, LW, H, cpl_log2);
+  const int LW = ln_lw(H);
+  hipLaunchKernelGGL(ln_param_finalize_batch_kernel, dim3(2 * LW / 64, 8, n), dim3(256), 0, stream, b, LW, H);
   VLB_CHECK_LAUNCH("vlb_ln_param_finalize_batch");
   return VLB_OK;
 }
 
 extern "C" long vlb_layernorm_bwd_workspace_floats(int H) {
   if (H <= 0) return 0;
-  const int np = vlb_cdiv(H, 512), nit = vlb_cdiv(H, 256);
-  const long lw8 = (np <= 3 ? np : 4) * 512, lw4 = (nit <= 4 ? nit : 8) * 256;      // either backward kernel may run
-  return (long)LN_MAX_BLOCKS * 2 * (lw8 > lw4 ? lw8 : lw4);
+  return (long)LN_MAX_BLOCKS * 2 * ln_lw(H);
 }

@@ -46,30 +46,20 @@
   /* ---- gemm.hip: 128x128 TN (weight-gradient) kernel ---- */                                                                         \
   /* tile-rows per L2 group; <= 0: the near-square rule of tile_order.h */                                                              \
   X(TN_GROUP, "tn_group", "VLB_GEMM_TN_GROUP", -1)                                                                                      \
-  /* 1: 8 waves of 64x32 per workgroup, 0: 4 waves */                                                                                   \
-  X(TN_WAVES8, "tn_waves8", "VLB_GEMM_TN_WAVES8", 1)                                                                                    \
   /* ---- gemm_tn8.hip: large-tile weight-gradient core ---- */                                                                         \
   /* 0: the 128x128 TN kernel only */                                                                                                   \
   X(TN8_MODE, "tn8_mode", "VLB_GEMM_TN8", 1)                                                                                            \
   /* persistent workgroups per launch (8..256, else 256 = one per CU) */                                                                \
   X(TN8_WGS, "tn8_wgs", "VLB_GEMM_TN8_WGS", 256)                                                                                        \
-  /* 1: the uneven three-slice cut of grouped launches, 0 equal slices -- measured: no gain at batch 256 (21.07 vs 21.02 ms / step),    \
-     5-10 % slower launches at batch 64 / 32 */                                                                                         \
-  X(TN8_UNEVEN, "tn8_uneven", "VLB_GEMM_TN8_UNEVEN", 0)                                                                                 \
-  /* 1: v_mfma_f32_32x32x16 form of the quadrant products, 0: 16x16x32 -- same 355-365 us per launch either way (power-limited), the    \
-     whole step 0.1 ms slower with 1 */                                                                                                 \
-  X(TN8_M32, "tn8_m32", "VLB_GEMM_TN8_M32", 0)                                                                                          \
   /* measurement builds (-DVLB_TN8_PROBE) only: see the kernel's ABL parameter */                                                       \
   X(TN8_ABLATE, "tn8_ablate", nullptr, 0)                                                                                               \
   /* tile-rows per L2 group; <= 0: the near-square rule of tile_order.h */                                                              \
   X(TN8_GROUP, "tn8_group", "VLB_GEMM_TN8_GROUP", 0)                                                                                    \
-  /* ---- layernorm.hip, attention.hip (their variants ride on the same table) ---- */                                                  \
+  /* ---- layernorm.hip (its variants ride on the same table) ---- */                                                                   \
   /* rows per wave of the forward: 1 | 2 | 4 (else: 2 where at least two full rounds of single-row waves exist) */                      \
   X(LN_FWD_ROWS, "ln_fwd_rows", "VLB_LN_FWD_ROWS", 0)                                                                                   \
-  /* backward: 1 the 4-column kernel (2: two rows in flight at H = 768 / 1024); 0 the 8-column kernel */                                \
-  X(LN_BWD4, "ln_bwd4", "VLB_LN_BWD4", 1)                                                                                               \
-  /* 1: the single-evaluation attention backward for S <= 128; 0 the two-orientation kernel */                                          \
-  X(ATTN_BWD2, "attn_bwd2", "VLB_ATTN_BWD2", 1)
+  /* backward: 1 one row in flight per wave at H = 768 / 1024 | 2 two rows in flight there; any other value means 1 */                  \
+  X(LN_BWD4, "ln_bwd4", "VLB_LN_BWD4", 1)
 
 enum VlbOpt {
 #define VLB_OPT_ID(id, name, env, dflt) VLB_OPT_##id,

@@ -424,15 +424,11 @@ class PretrainEngine:
         self.side = torch.cuda.Stream(device=d) if (d.type == "cuda" and os.environ.get("VLB_WGRAD_STREAM", "1") != "0") else None
         self.wg_ws_main = zf(max(need_dec, 4)) if self.side is not None else self.wg_ws    # decoder dgrad split-K (main stream)
         self._hazards = SideStreams()
-        # VLB_FRONT_JOIN=1: the front of the backward waits for the whole side stream instead of for the launches that wrote the
-        # gradients it adds into (A/B runs)
-        self._front_join = os.environ.get("VLB_FRONT_JOIN", "0") != "0"
         self.ln_ws = zf(ops.ln_bwd_workspace_floats(H))     # per-workgroup partial dgamma/dbeta sums of the LayerNorm backward
         # The encoder's LayerNorm backwards (2 per layer + the MLM head's) leave their partial sums in a workspace slice of their
         # own; one batched launch (ops.ln_param_finalize_batch) adds them into the gradients when those are next needed -- a
         # bucket's all-reduce, or the end of backward -- instead of a 7-10 us finalize launch behind each of the 25 calls.
-        n_slices = min(2 * L + 1, 32) if os.environ.get("VLB_LN_DEFER", "1") != "0" else 0
-        self._ln_slices = list(zf(n_slices, ops.ln_bwd_workspace_floats(H)).unbind(0)) if n_slices else []
+        self._ln_slices = list(zf(min(2 * L + 1, 32), ops.ln_bwd_workspace_floats(H)).unbind(0))
         self._ln_pending = []
         self.graph = None
         self._weights_dirty = True
@@ -875,9 +871,6 @@ class PretrainEngine:
             self._hazards.join([self.side])
 
     def _ln_bwd(self, dy, x, stats, gamma, dgamma, dbeta, **kw):
-        if not self._ln_slices:             # VLB_LN_DEFER=0: finalize behind every call
-            ops.layernorm_bwd(dy, x, stats, gamma, dgamma=dgamma, dbeta=dbeta, workspace=self.ln_ws, **kw)
-            return
         if len(self._ln_pending) == len(self._ln_slices):
             self._flush_ln()                 # (more deferred calls than slices: the 24-layer model)
         ws = self._ln_slices[len(self._ln_pending)]
@@ -1008,7 +1001,7 @@ class PretrainEngine:
         # embed_bwd adds into the word-embedding gradient the decoder weight-gradient launch wrote: the front waits for the side
         # launches that wrote one of ITS gradient tensors, not for the encoder's last weight-gradient launch, which it runs beside.
         # With a bucket hook the exchange reads whole buckets behind the front: everything on the side stream completes first.
-        if on_layer_done or self._front_join:
+        if on_layer_done:
             self._join_side()
         else:
             self._hazards.before_accumulate(*self._front_grads())
