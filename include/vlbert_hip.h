@@ -586,6 +586,36 @@ int vlb_softmax_f32_fwd(const float* s, const float* mask01, int rows_per_sample
 int vlb_softmax_f32_bwd(const float* p, float* dpd, int rows, int S, int Sp, float drop_p, const uint32_t* seed, uint32_t tag,
                         vlb_stream_t stream);
 
+/* ---- fp32 front and back end of the VQA fine-tuning route (csrc/f32_ends.hip; `fp32_ends` of engine.py / the module mirrors) ----
+ * What stands in front of X[0] and behind X[L] of the fp32 encoder, with every tensor in fp32: the fp32 twins of vlb_obj_prep_fwd
+ * (no mvrc_ops / mask-embedding substitution), vlb_zero_padded_rows_bf16, vlb_embed_fwd / _bwd (per-token text_vis, dense obj_ling;
+ * obj_ling_idx != NULL is an argument error; the tables are the fp32 MASTER parameters; dtv_st != 0), vlb_dropout_bf16, vlb_mul_bf16 and
+ * vlb_bce_logits_fwd_bwd (ld % 4 == 0; logits_copy with ldcopy >= ld).  Same id clamping, LayerNorm eps handling, loss convention and
+ * (seed, tag, element index) dropout convention as those; pointers 16-byte aligned, strides % 4 == 0.  The code does not depend on the
+ * library's 16-bit type. */
+int vlb_obj_prep_f32_fwd(const float* boxes, long ldbox, const float* im_info, long ldinfo, float* out, int B, int R, float drop_p,
+                         const uint32_t* seed, uint32_t tag, vlb_stream_t stream);
+int vlb_zero_padded_rows_f32(float* x, long ld, const float* boxes, long ldbox, int rows, int H, vlb_stream_t stream);
+int vlb_embed_f32_fwd(const int32_t* code, const int32_t* text_len, const int64_t* text_ids, const int64_t* text_type,
+                      const float* word_emb, const float* pos_emb, const float* type_emb, const float* end_emb,
+                      const float* text_vis, long tv_sb, long tv_st, const float* obj_vis, long ov_sb, long ov_sr,
+                      const float* obj_ling, long ol_sb, long ol_sr, const int64_t* obj_ling_idx, const float* gamma,
+                      const float* beta, float* pre, float* stats, float* out, int B, int T, int R, int S, int H, int V, int P,
+                      float eps, float drop_p, const uint32_t* seed, uint32_t tag, vlb_stream_t stream);
+int vlb_embed_f32_bwd(const float* dy, const float* pre, const float* stats, const float* gamma, const int32_t* code,
+                      const int32_t* text_len, const int64_t* text_ids, const int64_t* text_type, const int64_t* obj_ling_idx,
+                      float* d_word, float* d_pos, float* d_type, float* d_end, float* d_gamma, float* d_beta, float* d_text_vis,
+                      long dtv_sb, long dtv_st, float* d_obj_vis, long dov_sb, long dov_sr, float* d_obj_ling, long dol_sb,
+                      long dol_sr, int B, int T, int R, int S, int H, int V, int P, float drop_p, const uint32_t* seed,
+                      uint32_t tag, vlb_stream_t stream);
+int vlb_dropout_f32(const float* x, float* y, long n, float drop_p, const uint32_t* seed, uint32_t tag, vlb_stream_t stream);
+int vlb_mul_f32(const float* a, const float* b, float* out, long n, vlb_stream_t stream);
+/* out = g where y > 0 else 0 (fp32, n % 4 == 0): vlb_relu_bwd_cast without the cast */
+int vlb_relu_bwd_f32(const float* g, const float* y, float* out, long n, vlb_stream_t stream);
+/* row_loss: scratch of `rows` floats; the rows' sums are added up in a fixed order, so the loss is the same bits on every run */
+int vlb_bce_logits_f32_fwd_bwd(float* logits, long ld, int rows, int A, const float* label, long ldl, float gscale, float pos_weight,
+                               float* loss_out, float* row_loss, float* logits_copy, long ldcopy, vlb_stream_t stream);
+
 /* ---- data-parallel gradient exchange for a C / C++ host: RCCL over xGMI (csrc/comm.hip) ---------------------------------------
  * Replaces the gradient all-reduce that torch DistributedDataParallel / apex DDP issue for the reference
  * (pretrain/function/train.py:89-90,353-354; vqa/function/train.py:327; vcr/function/train.py:330): one SUM over the ranks of every

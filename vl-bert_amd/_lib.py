@@ -117,6 +117,15 @@ _SIGS = {
     "vlb_layernorm_f32_bwd": "plplppplplfpuppiis",
     "vlb_softmax_f32_fwd": "ppippiiifpus",
     "vlb_softmax_f32_bwd": "ppiiifpus",
+    # fp32 front / back end of the VQA route (csrc/f32_ends.hip)
+    "vlb_obj_prep_f32_fwd": "plplpiifpus",
+    "vlb_zero_padded_rows_f32": "plpliis",
+    "vlb_embed_f32_fwd": "pppp" "pppp" "pll" "pll" "pll" "p" "pp" "ppp" "iiiiiii" "f" "fpu" "s",
+    "vlb_embed_f32_bwd": "pppp" "ppppp" "pppppp" "pll" "pll" "pll" "iiiiiii" "fpu" "s",
+    "vlb_dropout_f32": "pplfpus",
+    "vlb_mul_f32": "pppls",
+    "vlb_relu_bwd_f32": "pppls",
+    "vlb_bce_logits_f32_fwd_bwd": "pliiplffpppls",
     "vlb_scale_f32": "plfs",
     "vlb_cast_f32_bf16": "ppls",
     "vlb_cast_bf16_f32": "ppls",

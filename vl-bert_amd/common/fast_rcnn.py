@@ -17,6 +17,10 @@ continues through the RoI head, ROIAlign and the trainable trunk stages.  Parame
 load_state_dict convert from / to the reference's [O,I,KH,KW]).  `segms` [B,R,14,14] (VCR's object masks) are multiplied into the
 RoI-head output before the pool (:152-156).  Not supported on this branch: IMAGE_SEMANTIC (`classes` is accepted and unused, as
 in the reference with that option off), `mask_visual_embed`, the bottom-of-CNN cnn_reg_loss, OUTPUT_CONV5.
+
+fp32_ends=True (the fp32 VQA route): the precomputed branch in fp32 -- vlb_obj_prep_f32_fwd -> the fp32 GEMM on the MASTER weight with
+fused bias + ReLU -> vlb_zero_padded_rows_f32; backward: ReLU mask, weight gradient as the fp32 NT product of the transposed operands,
+bias gradient as its column sums.  The image branch and `mask_visual_embed` raise NotImplementedError with it.
 """
 from collections import OrderedDict
 
@@ -76,6 +80,40 @@ class _Fn(torch.autograd.Function):
         return gw, gb, g_embed, None, None, None, None, None, None
 
 
+class _Fn32(torch.autograd.Function):
+    """The precomputed branch with every tensor fp32 (fp32_ends): one autograd node, no 16-bit working copy of the weight."""
+
+    @staticmethod
+    def forward(ctx, weight, bias, module, boxes, im_info, train):
+        B, R = boxes.shape[0], boxes.shape[1]
+        H, n = weight.shape[0], B * R
+        st = module._state32(B, R, boxes.device)
+        p = module.drop_p if train else 0.0
+        ops.obj_prep_f32_fwd(boxes, im_info, st["a"], drop_p=p, seed=module._seed, tag=_TAG)
+        ops.gemm_nt_f32(st["a"], 2 * VIS_DIM, weight.detach(), 2 * VIS_DIM, st["y"], H, n, H, 2 * VIS_DIM, bias=bias.detach(), epi=2)
+        ops.zero_padded_rows_f32(st["y"], boxes)                  # rows of padded boxes -> 0
+        ctx.module, ctx.st, ctx.p = module, st, p
+        return st["y"].view(B, R, H).clone()
+
+    @staticmethod
+    def backward(ctx, g):
+        module, st = ctx.module, ctx.st
+        H = module.final_dim
+        n = st["y"].shape[0]
+        npad = (n + 31) // 32 * 32
+        g = g.contiguous().float().view(n, H)
+        ops.relu_bwd_f32(g, st["y"], st["dy"])                    # (a padded box's row of y is zero: no gradient from it)
+        lin = getattr(module.obj_downsample, "1")
+        gw, gb = torch.zeros_like(lin.weight), torch.zeros_like(lin.bias)
+        # gw [H, 4096] = dy^T . a as the NT product of the two transposed operands (rows zero-padded to 32), gb = column sums of dy
+        ops.transpose_f32(st["dy"], H, st["tG"], npad, n, H, npad, colsum=gb)
+        ops.transpose_f32(st["a"], 2 * VIS_DIM, st["tA"], npad, n, 2 * VIS_DIM, npad)
+        ops.gemm_nt_f32(st["tG"], npad, st["tA"], npad, gw, 2 * VIS_DIM, H, 2 * VIS_DIM, npad, atomic=True)
+        if ctx.p > 0:
+            ops.rng_advance(module._seed)
+        return gw, gb, None, None, None, None
+
+
 class _FnE2E(torch.autograd.Function):
     """images -> VisionStack -> (coord || feature) -> Dropout -> Linear -> ReLU, one autograd node; conv weights are inputs so that
     autograd delivers their gradients (accumulated by VisionStack.backward into the module's flat-layout buffers)."""
@@ -109,10 +147,15 @@ class _FnE2E(torch.autograd.Function):
 
 
 class FastRCNN(nn.Module):
-    def __init__(self, config, average_pool=True, final_dim=768, enable_cnn_reg_loss=False, device=None):
+    def __init__(self, config, average_pool=True, final_dim=768, enable_cnn_reg_loss=False, device=None, fp32_ends=False):
         super().__init__()
         net = _get(config, "NETWORK")
         self.e2e = not _get(net, "IMAGE_FEAT_PRECOMPUTED", False)
+        self.fp32_ends = bool(fp32_ends)
+        if self.fp32_ends and self.e2e:
+            raise NotImplementedError("fp32_ends: the image branch (CNN, ROIAlign) is not built in fp32; use IMAGE_FEAT_PRECOMPUTED")
+        if self.fp32_ends and final_dim % 4:
+            raise NotImplementedError("fp32_ends: final_dim must be a multiple of 4")
         if self.e2e and not (average_pool and _get(net, "IMAGE_FROZEN_BN", True) and _get(net, "IMAGE_STRIDE_IN_1x1", True)
                              and _get(net, "IMAGE_C5_DILATED", True) and not _get(net, "OUTPUT_CONV5", False)):
             raise NotImplementedError("image branch: needs average_pool, IMAGE_FROZEN_BN, IMAGE_STRIDE_IN_1x1, IMAGE_C5_DILATED, no OUTPUT_CONV5")
@@ -226,6 +269,15 @@ class FastRCNN(nn.Module):
         from .visual_linguistic_bert import lru_get       # (R follows each batch's largest box count: keep the recent shapes only)
         return lru_get(self._states, (B, R), make)
 
+    def _state32(self, B, R, dev):
+        def make():
+            n, H = B * R, self.final_dim
+            npad = (n + 31) // 32 * 32
+            zf = lambda *s: torch.zeros(s, dtype=torch.float32, device=dev)
+            return dict(a=zf(n, 2 * VIS_DIM), y=zf(n, H), dy=zf(n, H), tG=zf(H, npad), tA=zf(2 * VIS_DIM, npad))
+        from .visual_linguistic_bert import lru_get
+        return lru_get(self._states, ("f32", B, R), make)
+
     def _forward_e2e(self, images, boxes, box_mask, im_info, classes, segms, mvrc_ops, mask_visual_embed):
         # `classes` only feeds the IMAGE_SEMANTIC object-class embedding and the bottom-of-CNN regulariser (common/fast_rcnn.py:139,
         # 158-163), both rejected by the constructor: accepted and unused here, as in the reference with those options off
@@ -254,6 +306,14 @@ class FastRCNN(nn.Module):
         if boxes.shape[2] != 4 + VIS_DIM:
             raise ValueError("precomputed boxes must be [B, R, 4 + 2048]")
         use_mask = mvrc_ops is not None and mask_visual_embed is not None
+        if self.fp32_ends:
+            if use_mask:
+                raise NotImplementedError("fp32_ends: mask_visual_embed (the MVRC substitution) is not built in fp32")
+            lin = getattr(self.obj_downsample, "1")
+            obj_reps = _Fn32.apply(lin.weight, lin.bias, self, boxes, im_info.float().contiguous(), self.training)
+            raw = boxes[:, :, 4:].clone()
+            raw[~box_mask.bool()] = 0
+            return {"obj_reps_raw": raw, "obj_reps": obj_reps}
         sel = (mvrc_ops.reshape(-1).to(torch.int64) if use_mask else torch.zeros((B * R,), dtype=torch.int64, device=boxes.device))
         ar = torch.arange(B * R, dtype=torch.int32, device=boxes.device)
         idx = torch.where(box_mask.reshape(-1).bool(), ar, torch.full_like(ar, -1))     # index plumbing (the reference: nonzero())

@@ -135,8 +135,9 @@ def parse_args(task, argv=None):
     ap.add_argument("--steps-per-epoch", type=int, default=10000, help="stands in for len(train_loader) in the LR schedule")
     ap.add_argument("--val-steps", type=int, default=0, help="validate over N synthetic batches (fixed seed) after every --steps-per-epoch "
                     "optimizer steps of this loop; 0 = no validation")
-    ap.add_argument("--compute", default="bf16", choices=["bf16", "fp16", "fp32", "cfg"], help="as pretrain/train_end2end: cfg = what the "
-                    "YAML names (TRAIN.FP16 true -> the fp16 build + FP16_LOSS_SCALE, false -> fp32 encoder)")
+    ap.add_argument("--compute", default="bf16", choices=["bf16", "fp16", "fp32", "fp32-full", "cfg"], help="as pretrain/train_end2end: cfg = what "
+                    "the YAML names (TRAIN.FP16 true -> the fp16 build + FP16_LOSS_SCALE, false -> fp32 encoder); fp32 = fp32 encoder between "
+                    "16-bit ends; fp32-full = fp32 encoder + fp32 ends (VQA on precomputed features: no 16-bit tensor on the route)")
     ap.add_argument("--dry-run", action="store_true", help="resolve and print the configuration, touch no GPU")
     return ap.parse_args(argv)
 
@@ -145,6 +146,9 @@ def resolve(task, config, world, args):
     tr = config.TRAIN
     B, accum = int(tr.BATCH_IMAGES), int(tr.GRAD_ACCUMULATE_STEPS)
     compute = (("fp16" if tr.FP16 else "fp32") if args.compute == "cfg" else args.compute)
+    if compute == "fp32-full" and (task != "vqa" or not bool(config.NETWORK.IMAGE_FEAT_PRECOMPUTED)):
+        raise NotImplementedError("--compute fp32-full (fp32 encoder + fp32 ends) is built for VQA on precomputed features only; "
+                                  "%s%s runs --compute fp32" % (task, "" if task != "vqa" else " on the image branch"))
     if tr.OPTIMIZER not in ("AdamW", "SGD"):
         raise NotImplementedError("TRAIN.OPTIMIZER %s (supported: AdamW, SGD)" % tr.OPTIMIZER)
     return dict(task=task, module=config.MODULE, per_gpu_batch=B, accumulate=accum, world=world, lr=float(tr.LR) * world * B * accum,
@@ -205,7 +209,8 @@ def main(task, argv=None):
     pkg = __package__.rsplit(".", 1)[0]
     if r["compute"] != "bf16":
         importlib.import_module(pkg + "._lib").set_precision("f16")
-    os.environ["VLB_ENCODER_FP32"] = "1" if r["compute"] == "fp32" else "0"
+    os.environ["VLB_ENCODER_FP32"] = "1" if r["compute"] in ("fp32", "fp32-full") else "0"
+    os.environ["VLB_FP32_ENDS"] = "1" if r["compute"] == "fp32-full" else "0"
     torch.cuda.set_device(local_rank)
     dev = torch.device("cuda", local_rank)
     dist = None

@@ -10,12 +10,13 @@ from .. import ops
 from . import language_pretrained as _lp
 from .fast_rcnn import FastRCNN
 from .heads import cfg_get
-from .visual_linguistic_bert import VisualLinguisticBert
+from .visual_linguistic_bert import VisualLinguisticBert, check_fp32_ends, fp32_flags
 
 
 class Module(nn.Module):
     SEED = None                      # base of the per-rank dropout seed (ops.rank_seed)
     NUM_OBJECT_WORDS = 1             # rows of object_linguistic_embeddings
+    FP32_ENDS = False                # whether the task's route is built with an fp32 front and back end (`fp32_ends`)
 
     def __init__(self, config, device=None):
         super().__init__()
@@ -23,6 +24,15 @@ class Module(nn.Module):
         net = cfg_get(config, "NETWORK")
         vl = cfg_get(net, "VLBERT")
         self._check_config(net, vl)
+        # `fp32_ends` (config key of the VLBERT node / VLB_FP32_ENDS=1): fp32 region projection, embedding, classifier and loss around
+        # the fp32 encoder -- checked before anything touches the device
+        self.fp32_encoder, self.fp32_ends = fp32_flags(vl)
+        check_fp32_ends(self.fp32_ends, self.fp32_encoder, with_pooler=bool(cfg_get(vl, "with_pooler", False)))
+        if self.fp32_ends and not self.FP32_ENDS:
+            raise NotImplementedError("fp32_ends is built for the VQA fine-tuning route only, not for %s.%s"
+                                      % (type(self).__module__.split(".")[-1], type(self).__name__))
+        if self.fp32_ends and not cfg_get(net, "IMAGE_FEAT_PRECOMPUTED", False):
+            raise NotImplementedError("fp32_ends: the image branch (CNN, ROIAlign) is not built in fp32; use IMAGE_FEAT_PRECOMPUTED")
         if not torch.cuda.is_available():
             raise RuntimeError("ResNetVLBERT (HIP) needs an MI355X: there is no CPU fallback")
         dev = torch.device(device or ("cuda:%d" % torch.cuda.current_device()))
@@ -30,7 +40,7 @@ class Module(nn.Module):
         self.H = H = int(cfg_get(vl, "hidden_size"))
         self.cls_drop = float(cfg_get(net, "CLASSIFIER_DROPOUT", 0.1))
         self.image_feature_extractor = FastRCNN(config, average_pool=True, final_dim=cfg_get(net, "IMAGE_FINAL_DIM", 768),
-                                                enable_cnn_reg_loss=False, device=dev)
+                                                enable_cnn_reg_loss=False, device=dev, **({"fp32_ends": True} if self.fp32_ends else {}))
         self.object_linguistic_embeddings = nn.Embedding(self.NUM_OBJECT_WORDS, H).to(dev)
         self.language_pretrained_model_path = _lp.resolve_path(net)
         if self.language_pretrained_model_path is None:

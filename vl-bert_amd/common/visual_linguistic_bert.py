@@ -62,6 +62,25 @@ def lru_get(cache, key, make):
     return cache[key]
 
 
+def fp32_flags(config):
+    """(fp32_encoder, fp32_ends) of a VLBERT config node and the environment (VLB_ENCODER_FP32=1 / VLB_FP32_ENDS=1)."""
+    return (bool(_get(config, "fp32_encoder", False)) or os.environ.get("VLB_ENCODER_FP32", "0") == "1",
+            bool(_get(config, "fp32_ends", False)) or os.environ.get("VLB_FP32_ENDS", "0") == "1")
+
+
+def check_fp32_ends(fp32_ends, fp32_encoder, with_pooler=False, with_heads=False):
+    """The combinations `fp32_ends` is built for (no device needed): raises for the others, naming them."""
+    if not fp32_ends:
+        return
+    if not fp32_encoder:
+        raise ValueError("fp32_ends requires fp32_encoder (config key `fp32_encoder` / VLB_ENCODER_FP32=1): the fp32 front and back end "
+                         "stand around the fp32 encoder")
+    if with_heads:
+        raise NotImplementedError("fp32_ends: the pre-training heads (MLM / MVRC / relationship) and their losses are not built in fp32")
+    if with_pooler:
+        raise NotImplementedError("fp32_ends: the pooler (with_pooler, VCR) is not built in fp32")
+
+
 class _CoreFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, text_vis, obj_vl, anchor, module, eng):
@@ -77,7 +96,9 @@ class _CoreFn(torch.autograd.Function):
             return mlm.float(), mvrc.float(), third
         if eng.seq_out:      # trimmed to the batch's longest packed sequence like the reference (:202; one host sync)
             n = int((eng.lay["text_len"] + eng.lay["nobj"]).max()) + 1
-            return eng.sequence_output()[:, :n].float(), text_vis.new_zeros(()), third
+            seq = eng.sequence_output()[:, :n]
+            # (fp32_ends: the fp32 rows as they are -- a copy, the engine's buffer is rewritten by the next forward)
+            return (seq.clone() if seq.dtype == torch.float32 else seq.float()), text_vis.new_zeros(()), third
         return text_out.float(), obj_out.float(), third
 
     @staticmethod
@@ -92,6 +113,8 @@ class _CoreFn(torch.autograd.Function):
                 d_tv, d_ovl = eng.backward_core_sequence(g0, g2, train=module.training)
             else:
                 d_tv, d_ovl = eng.backward_core_hidden(g0, g1, g2, train=module.training)
+        if d_tv.dtype == torch.float32:      # fp32_ends: views of engine buffers -- hand autograd tensors of its own
+            d_tv, d_ovl = d_tv.clone(), d_ovl.clone()
         return d_tv.to(ctx.in_dtypes[0]), d_ovl.to(ctx.in_dtypes[1]), None, None, None
 
 
@@ -115,6 +138,10 @@ class VisualLinguisticBert(nn.Module):
         # VLBERT config node, or VLB_ENCODER_FP32=1 -- run it on the fp16 build (VLB_PRECISION=f16) for the 1e-3 class
         import os as _os
         self.fp32_encoder = bool(_get(config, "fp32_encoder", False)) or _os.environ.get("VLB_ENCODER_FP32", "0") == "1"
+        # fp32 front and back end as well (engine.PretrainEngine(fp32_ends=True)): `fp32_ends` in the config node, or VLB_FP32_ENDS=1.
+        # The sequence-output call form only (VQA); it needs the fp32 encoder
+        self.fp32_ends = fp32_flags(config)[1]
+        check_fp32_ends(self.fp32_ends, self.fp32_encoder, with_pooler=self.with_pooler, with_heads=self.WITH_HEADS)
         self.cfg = _engine.ModelConfig(
             hidden_size=_get(config, "hidden_size"), num_hidden_layers=_get(config, "num_hidden_layers"),
             num_attention_heads=_get(config, "num_attention_heads"), intermediate_size=_get(config, "intermediate_size"),
@@ -189,11 +216,15 @@ class VisualLinguisticBert(nn.Module):
                 p.grad = named[_PREFIX + name]
 
     def _engine_for(self, B, T, R, sequence=False):
-        eng = lru_get(self._engines, (B, T, R, sequence),
+        if self.fp32_ends and not sequence:
+            raise NotImplementedError("fp32_ends: only the sequence-output call form (output_text_and_object_separately=False) is built; "
+                                      "text and objects returned separately is not")
+        eng = lru_get(self._engines, (B, T, R, sequence, self.fp32_ends),
                       lambda: _engine.PretrainEngine(self.cfg, B, T, R, device=str(self.device_), flat=self.flat, core=True,
                                                      core_heads=self.WITH_HEADS, core_sequence=sequence,
                                                      seed=ops.rank_seed(1234) // 2,         # per-rank dropout stream
-                                                     encoder_fp32=self.fp32_encoder, max_seq=_MAX_S))
+                                                     encoder_fp32=self.fp32_encoder, max_seq=_MAX_S,
+                                                     fp32_ends=self.fp32_ends and sequence))
         eng._dp_hook = getattr(self, "_dp_hook", None)          # parallel.DistributedDataParallel: gradient buckets leave from backward
         version = self.flat.master._version
         if getattr(eng, "_synced_version", None) != version:
@@ -223,6 +254,10 @@ class VisualLinguisticBert(nn.Module):
 
     def forward(self, text_input_ids, text_token_type_ids, text_visual_embeddings, text_mask, object_vl_embeddings, object_mask,
                 output_all_encoded_layers=True, output_text_and_object_separately=False, output_attention_probs=False):
+        if self.fp32_ends and (output_all_encoded_layers or output_attention_probs or output_text_and_object_separately):
+            raise NotImplementedError("fp32_ends: only forward(..., output_all_encoded_layers=False, output_text_and_object_separately=False) "
+                                      "is built; not output_all_encoded_layers / output_attention_probs / "
+                                      "output_text_and_object_separately")
         if output_all_encoded_layers or output_attention_probs:
             return self._inspect(text_input_ids, text_token_type_ids, text_visual_embeddings, text_mask, object_vl_embeddings, object_mask,
                                  output_all_encoded_layers, output_text_and_object_separately, output_attention_probs)

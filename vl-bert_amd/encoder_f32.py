@@ -11,6 +11,8 @@ Where the precision boundary lies: the embedding side and the heads stay on the 
 VLB_PRECISION=f16: 2^-12 per rounding, a handful of roundings in total); `forward` takes the embedding output X[0] up to fp32,
 `backward` hands the 16-bit d X[0] back.  The 24 (12) layers in between -- where rounding error accumulates with depth, 10 operand
 roundings per layer in a 16-bit build -- see none.  Measured: tests/test_f32_encoder_gpu.py.
+With the engine's `fp32_ends` the boundary is gone on the VQA fine-tuning route: the fused fp32 embedding (csrc/f32_ends.hip) writes
+X[0] here, the caller reads X[L] and hands an fp32 d X[L] in, and `forward` / `backward` skip their casts (tests/test_fp32_ends_gpu.py).
 
 Attention is composed from the batched GEMM: scores = Q.K^T / 8 per (sample, head) -> softmax (+ key mask, + dropout) -> P.V with V
 transposed per head; the backward is the five products of the same shapes.  The probabilities are kept per layer ([B, h, S, Sp] fp32:
@@ -145,7 +147,9 @@ class EncoderF32:
         if p_a > 0 and self.Pd is None:
             self.Pd = [torch.zeros((Bt * nh * S, Sp), dtype=F32, device=e.dev) for _ in range(L)]
         seed, mask = e.seed, e.lay["attn_mask"]
-        ops.cast_bf16_f32(e.X[0], self.X[0])
+        ends = getattr(e, "fp32_ends", False)      # X[0] was written in fp32 by the embedding; X[L] is read in fp32
+        if not ends:
+            ops.cast_bf16_f32(e.X[0], self.X[0])
         bh = (Bt, nh)
         for l in range(L):
             w = self.w[l]
@@ -164,18 +168,21 @@ class EncoderF32:
             self._linear(self.Y1[l], H, w["w1"], I, self.G[l], bias=w["b1"], epi=1, pre=self.dG[l], ldpre=I)
             self._linear(self.G[l], I, w["w2"], H, self.Z2[l], bias=w["b2"], drop_p=p_h, seed=seed, tag=l * 8 + 2, res=self.Y1[l], ldres=H)
             ops.layernorm_f32_fwd(self.Z2[l], w["g2"], w["be2"], self.X[l + 1], self.ST2[l])
-        ops.cast_f32_bf16(self.X[L], e.X[L])
+        if not ends:
+            ops.cast_f32_bf16(self.X[L], e.X[L])
 
     # -- backward -----------------------------------------------------------------------------------------------------
     def backward(self, dx16, p_h, p_a, on_layer_done=None, will_launch=None):
         """dx16: 16-bit d X[L] [M, H] -> weight gradients ACCUMULATED into the engine's flat fp32 gradient; returns the 16-bit d X[0]
-        (written over dx16's buffer)."""
+        (written over dx16's buffer).  With the engine's fp32_ends dx16 is the fp32 d X[L] and the fp32 d X[0] is returned."""
         e = self.eng
         H, I, L, nh, M, S, Sp, Bt = self.H, self.I, self.L, self.nh, self.M, self.S, self.Sp, self.Bt
         seed = e.seed
         bh = (Bt, nh)
-        dx = self.dx[0]
-        ops.cast_bf16_f32(dx16, dx)
+        ends = getattr(e, "fp32_ends", False)
+        dx = dx16 if ends else self.dx[0]
+        if not ends:
+            ops.cast_bf16_f32(dx16, dx)
         for l in reversed(range(L)):
             w, t = self.w[l], self.wT[l]
             dx_next = self.dx[1] if dx is self.dx[0] else self.dx[0]
@@ -221,5 +228,7 @@ class EncoderF32:
             dx = dx_next
             if on_layer_done and (will_launch is None or will_launch(l)):
                 on_layer_done(l)
+        if ends:
+            return dx
         ops.cast_f32_bf16(dx, dx16)
         return dx16

@@ -168,8 +168,14 @@ class PretrainEngine:
     def __init__(self, cfg, B, T, R, device="cuda:0", train=True, lr=1e-4, weight_decay=1e-4, max_grad_norm=10.0,
                  betas=(0.9, 0.999), eps=1e-6, seed=1234, grad_accum=1, process_group=None, keep_logits=False, flat=None,
                  B_aux=0, core=False, core_heads=True, core_sequence=False, lr_schedule=None, warmup_steps=0, t_total=0,
-                 image_size=None, dp_mode="default", dp_wire="default", loss_scale=None, encoder_fp32=False, max_seq=256):
+                 image_size=None, dp_mode="default", dp_wire="default", loss_scale=None, encoder_fp32=False, max_seq=256, fp32_ends=False):
         cfg.validate()
+        # fp32_ends: the module-API front end (visual LayerNorms, fused embedding) and the hand-over of the sequence output run in fp32
+        # too (csrc/f32_ends.hip), so that an encoder_fp32 engine holds no 16-bit tensor between its inputs and X[L].  One route only:
+        # checked here, before anything is allocated
+        self.fp32_ends = bool(fp32_ends)
+        if self.fp32_ends:
+            self._check_fp32_ends(cfg, T, R, core, core_heads, core_sequence, encoder_fp32, image_size, dp_mode, B_aux)
         # max_seq: the longest packed sequence S = T + R + 1 this engine may be built for, 256..512.  Up to 256 positions attention runs
         # the whole-sequence kernels (csrc/attention.hip), 257..512 the streaming ones (csrc/attention_long.hip: seven products per tile
         # pair instead of five).  The default stays 256 so that a caller opts into the long path knowingly.
@@ -408,6 +414,11 @@ class PretrainEngine:
             self.tv_n, self.st_tv = zb(BT, H), zf(BT, 2)                # visual_ln_text per token
             self.d_tv_n, self.d_ol = zf(BT, H), zf(BR, H)               # d(LN(text_visual)), d(object linguistic half)
             self.d_tv_in, self.d_ovl_in = zb(BT, H), zb(BR, 2 * H)      # gradients handed back to autograd
+            if self.fp32_ends:     # the same tensors in fp32: inputs, the two visual LayerNorm outputs, the pre-LayerNorm sum, d X[L]
+                self.tv_in32, self.ovl_in32 = zf(BT, H), zf(BR, 2 * H)
+                self.tv_n32, self.objvis32, self.emb_pre32 = zf(BT, H), zf(BR, H), zf(M, H)
+                self.d_tv_in32, self.d_ovl_in32 = zf(BT, H), zf(BR, 2 * H)
+                self.dX32 = zf(M, H)
         # fp32 slab workspace for split-K weight gradients (largest request over this engine's wgrad shapes)
         need = [ops.wgrad_workspace_floats(n, k, rp) for n, k, rp in
                 ((3 * H, H, self.Mp), (H, H, self.Mp), (I, H, self.Mp), (H, I, self.Mp), (V, H, self.BTp), (H, H, self.BTp),
@@ -453,7 +464,8 @@ class PretrainEngine:
                 # every owner-only update (parallel.GradBuckets.set_replicated_fp32)
                 self.buckets.set_replicated_fp32(self._fp32_read_ranges())
         # fp32 compute mode of the encoder (the reference's TRAIN.FP16: false configurations; encoder_f32.py): the layers run on fp32
-        # tensors and the fp32 MASTER weights, the embedding side and the heads stay on the 16-bit kernels (use the fp16 build)
+        # tensors and the fp32 MASTER weights, the embedding side and the heads stay on the 16-bit kernels (use the fp16 build) unless
+        # fp32_ends moves the module-API front end and the hand-over of the sequence output to fp32 as well
         self.enc32 = None
         if encoder_fp32:
             if self.buckets is not None and self.buckets.sharded:
@@ -461,6 +473,32 @@ class PretrainEngine:
                                  "keeps them authoritative on the owner only)")
             from .encoder_f32 import EncoderF32
             self.enc32 = EncoderF32(self)
+
+    @staticmethod
+    def _check_fp32_ends(cfg, T, R, core, core_heads, core_sequence, encoder_fp32, image_size, dp_mode, B_aux):
+        """fp32_ends covers the sequence-output module API on an fp32 encoder (the VQA fine-tuning route); everything else is named."""
+        bad = []
+        if not core:
+            bad.append("core=False (the pre-training engine's own front end, MLM / MVRC / relationship heads and losses)")
+        elif core_heads:
+            bad.append("core_heads=True (the MLM / MVRC / relationship heads)")
+        elif not core_sequence:
+            bad.append("core_sequence=False (text and objects returned separately)")
+        if not encoder_fp32:
+            bad.append("encoder_fp32=False")
+        if cfg.with_pooler:
+            bad.append("with_pooler (the pooled output of VCR)")
+        if cfg.e2e or image_size is not None:
+            bad.append("the image branch (CNN, ROIAlign)")
+        if B_aux:
+            bad.append("B_aux > 0 (multitask text-only samples)")
+        if dp_mode == "sharded":
+            bad.append("dp_mode='sharded' (the sharded optimizer)")
+        if T + R + 1 > 256:
+            bad.append("a sequence of %d+%d+1 positions (the fp32 encoder handles at most 256)" % (T, R))
+        if bad:
+            raise ValueError("fp32_ends needs core=True, core_heads=False, core_sequence=True, encoder_fp32=True and no pooler; "
+                             "unsupported here: " + "; ".join(bad))
 
     # ------------------------------------------------------------------------------------------
     # parameters
@@ -682,6 +720,18 @@ class PretrainEngine:
         cfg, T, R, S, Bt = self.cfg, self.T, self.R, self.S, self.Bt
         H = cfg.hidden_size
         w16, w32, seed = self.w16, self.w32, self.seed
+        if self.fp32_ends:      # fp32 inputs, fp32 master tables, written straight into the fp32 encoder's X[0]
+            ops.layernorm_f32_fwd(self.tv_in32, w32["vlbert.visual_ln_text.weight"], w32["vlbert.visual_ln_text.bias"], self.tv_n32,
+                                  self.st_tv)
+            ops.layernorm_f32_fwd(self.ovl_in32[:, :H], w32["vlbert.visual_ln_object.weight"], w32["vlbert.visual_ln_object.bias"],
+                                  self.objvis32, self.st_objvis)
+            ops.embed_f32_fwd(self.lay, self.in_text, self.in_text_type, w32["vlbert.word_embeddings.weight"],
+                              w32["vlbert.position_embeddings.weight"], w32["vlbert.token_type_embeddings.weight"],
+                              w32["vlbert.end_embedding.weight"], self.tv_n32, (T * H, H), self.objvis32, (R * H, H),
+                              (self.ovl_in32, H), (R * 2 * H, 2 * H), None, w32["vlbert.embedding_LayerNorm.weight"],
+                              w32["vlbert.embedding_LayerNorm.bias"], self.emb_pre32, self.st_emb, self.enc32.X[0], Bt, T, R, S, H,
+                              drop_p=p_h, seed=seed, tag=TAG_EMBED)
+            return
         ops.layernorm_fwd(self.tv_in, w32["vlbert.visual_ln_text.weight"], w32["vlbert.visual_ln_text.bias"], self.tv_n, self.st_tv)
         ops.layernorm_fwd(self.ovl_in[:, :H], w32["vlbert.visual_ln_object.weight"], w32["vlbert.visual_ln_object.bias"], self.objvis,
                           self.st_objvis)
@@ -732,6 +782,8 @@ class PretrainEngine:
         self._last_p_a, self._seed_moved = p_a, False      # attention_probs() recomputes this forward's dropout masks
         if self.enc32 is not None:
             self.enc32.forward(p_h, p_a)
+            if self.fp32_ends:      # the caller reads enc32.X[L] (sequence_output): no 16-bit copy, no gathers from one
+                return
         for l in range(L if self.enc32 is None else 0):
             r, x = self.layer[l], self.X[l]
             if stale:
@@ -936,7 +988,7 @@ class PretrainEngine:
                 pr = "vlbert.relationsip_head.caption_image_relationship."
                 self._wgrad(self.rel_logits[:, :2], self.pooled, g32[pr + "weight"], g32[pr + "bias"])
                 ops.gemm_nt(self.rel_logits, wT[pr + "weight"], self.d_pooled)      # K = 64: two logits + zero padding
-        dx = self.dXa
+        dx = self.dX32 if self.fp32_ends else self.dXa
         if not self.seq_out:      # (sequence mode: the caller's d(sequence_output) is already in dXa)
             ops.head_grad_combine(self.d_text_out, self.d_obj_out, self.lay["code"], dx, Bt, T, R, S, H)
         if cfg.with_pooler and (cfg.with_rel_loss or not self.with_heads):
@@ -1034,8 +1086,21 @@ class PretrainEngine:
         w32, g32, seed = self.w32, self.g32, self.seed
         self.d_tv_n.zero_()
         self.d_objvis.zero_()
-        self.d_ol.zero_()
         pe = "vlbert.embedding_LayerNorm."
+        if self.fp32_ends:      # dx: the fp32 d X[0]; d(object linguistic half) is written straight into the handed-back gradient
+            self.d_ovl_in32.zero_()
+            ops.embed_f32_bwd(dx, self.emb_pre32, self.st_emb, w32[pe + "weight"], self.lay, self.in_text, self.in_text_type, None,
+                              g32["vlbert.word_embeddings.weight"], g32["vlbert.position_embeddings.weight"],
+                              g32["vlbert.token_type_embeddings.weight"], g32["vlbert.end_embedding.weight"], g32[pe + "weight"],
+                              g32[pe + "bias"], self.d_tv_n, (T * H, H), self.d_objvis, (R * H, H), (self.d_ovl_in32, H),
+                              (R * 2 * H, 2 * H), Bt, T, R, S, H, drop_p=p_h, seed=seed, tag=TAG_EMBED)
+            ops.layernorm_f32_bwd(self.d_tv_n, self.tv_in32, self.st_tv, w32["vlbert.visual_ln_text.weight"], dx=self.d_tv_in32,
+                                  dgamma=g32["vlbert.visual_ln_text.weight"], dbeta=g32["vlbert.visual_ln_text.bias"])
+            ops.layernorm_f32_bwd(self.d_objvis, self.ovl_in32[:, :H], self.st_objvis, w32["vlbert.visual_ln_object.weight"],
+                                  dx=self.d_ovl_in32[:, :H], dgamma=g32["vlbert.visual_ln_object.weight"],
+                                  dbeta=g32["vlbert.visual_ln_object.bias"])
+            return
+        self.d_ol.zero_()
         ops.embed_bwd(dx, self.emb_pre, self.st_emb, w32[pe + "weight"], self.lay, self.in_text, self.in_text_type, None,
                       g32["vlbert.word_embeddings.weight"], g32["vlbert.position_embeddings.weight"],
                       g32["vlbert.token_type_embeddings.weight"], g32["vlbert.end_embedding.weight"], g32[pe + "weight"],
@@ -1109,10 +1174,14 @@ class PretrainEngine:
                              % (Bt, T, Bt, T, H, Bt, R, 2 * H))
         self.in_text.copy_(text_input_ids)
         self.in_text_type.copy_(text_token_type_ids)
-        self.tv_in.view(Bt, T, H).copy_(text_visual_embeddings)            # dtype conversion to bf16 (glue)
-        self.ovl_in.view(Bt, R, 2 * H).copy_(object_vl_embeddings)
         self.text_mask.view(torch.bool).copy_(text_mask)
         self.box_mask.view(torch.bool).copy_(object_mask)
+        if self.fp32_ends:      # the caller's embeddings stay fp32
+            self.tv_in32.view(Bt, T, H).copy_(text_visual_embeddings)
+            self.ovl_in32.view(Bt, R, 2 * H).copy_(object_vl_embeddings)
+            return
+        self.tv_in.view(Bt, T, H).copy_(text_visual_embeddings)            # dtype conversion to bf16 (glue)
+        self.ovl_in.view(Bt, R, 2 * H).copy_(object_vl_embeddings)
 
     def forward_core(self, train=None):
         """-> (mlm_logits [B,T,V], mvrc_logits [B,R,C], text_out [B,T,H], obj_out [B,R,H], pooled [B,H] | None,
@@ -1143,7 +1212,10 @@ class PretrainEngine:
         return self.d_tv_in.view(self.Bt, self.T, H), self.d_ovl_in.view(self.Bt, self.R, 2 * H)
 
     def sequence_output(self):
-        """Last encoder layer as the packed [B, S, H] sequence (text || objects || END || padding), bf16 view."""
+        """Last encoder layer as the packed [B, S, H] sequence (text || objects || END || padding), bf16 view (fp32_ends: the fp32
+        encoder's own X[L], fp32)."""
+        if self.fp32_ends:
+            return self.enc32.X[self.cfg.num_hidden_layers].view(self.Bt, self.S, self.cfg.hidden_size)
         return self.X[self.cfg.num_hidden_layers].view(self.Bt, self.S, self.cfg.hidden_size)
 
     # ------------------------------------------------------------------------------------------
@@ -1188,7 +1260,7 @@ class PretrainEngine:
     def backward_core_sequence(self, d_seq, d_pooled=None, train=None):
         """core_sequence=True: d(sequence_output) [B, <=S, H] (rows beyond the given length are zero) -> input gradients."""
         H = self.cfg.hidden_size
-        dx = self.dXa.view(self.Bt, self.S, H)
+        dx = (self.dX32 if self.fp32_ends else self.dXa).view(self.Bt, self.S, H)
         dx.zero_()
         if d_seq is not None:
             dx[:, :d_seq.shape[1]].copy_(d_seq)
@@ -1198,6 +1270,8 @@ class PretrainEngine:
             else:
                 self.d_pooled.copy_(d_pooled)
         self.backward(train)
+        if self.fp32_ends:
+            return self.d_tv_in32.view(self.Bt, self.T, H), self.d_ovl_in32.view(self.Bt, self.R, 2 * H)
         return self.d_tv_in.view(self.Bt, self.T, H), self.d_ovl_in.view(self.Bt, self.R, 2 * H)
 
     def backward_core(self, d_mlm_logits, d_mvrc_logits, d_rel_logits=None, train=None):

@@ -920,3 +920,73 @@ def softmax_f32_fwd(s, mask01, rows_per_sample, p, pd, rows, S, Sp, drop_p=0.0, 
 
 def softmax_f32_bwd(p, dpd, rows, S, Sp, drop_p=0.0, seed=None, tag=0):
     _lib.call("vlb_softmax_f32_bwd", _pf(p), _pf(dpd), int(rows), int(S), int(Sp), float(drop_p), _p(seed), int(tag), _stream())
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# fp32 front / back end of the VQA fine-tuning route (csrc/f32_ends.hip): every operand fp32
+# ---------------------------------------------------------------------------------------------------------------
+def obj_prep_f32_fwd(boxes, im_info, out, drop_p=0.0, seed=None, tag=0):
+    """out fp32 [B*R, 4096] <- dropout(coordinate embedding || 2048-d feature) of boxes fp32 [B, R, 4 + 2048]; padded boxes -> zero rows."""
+    B, R, ldb = boxes.shape
+    assert boxes.is_contiguous() and out.is_contiguous() and out.shape[-1] == 4096 and out.numel() == B * R * 4096
+    assert im_info.dim() == 2 and im_info.shape[0] == B and im_info.shape[1] >= 2 and im_info.stride(1) == 1, tuple(im_info.shape)
+    _lib.call("vlb_obj_prep_f32_fwd", _pf(boxes), ldb, _pf(im_info), im_info.stride(0), _pf(out), B, R, float(drop_p), _p(seed), int(tag),
+              _stream())
+    return out
+
+
+def zero_padded_rows_f32(x, boxes):
+    """x fp32 [B*R, H]: rows whose box (boxes fp32 [B, R, ld], x1 <= -1.5) is padding become 0."""
+    B, R, ldb = boxes.shape
+    _lib.call("vlb_zero_padded_rows_f32", _pf(x), _ld(x), _pf(boxes), ldb, B * R, x.shape[1], _stream())
+    return x
+
+
+def embed_f32_fwd(lay, text_ids, text_type, word_emb, pos_emb, type_emb, end_emb, text_vis, tv_strides, obj_vis, ov_strides, obj_ling,
+                  ol_strides, obj_ling_idx, gamma, beta, pre, stats, out, B, T, R, S, H, eps=1e-12, drop_p=0.0, seed=None, tag=0):
+    """embed_fwd with every operand fp32 (tables = the fp32 master parameters; dense obj_ling only)."""
+    _lib.call("vlb_embed_f32_fwd", _p(lay["code"]), _p(lay["text_len"]), _p(text_ids, torch.int64), _p(text_type, torch.int64),
+              _pf(word_emb), _pf(pos_emb), _pf(type_emb), _pf(end_emb), _pf(text_vis), tv_strides[0], tv_strides[1], _pf(obj_vis),
+              ov_strides[0], ov_strides[1], _pf(obj_ling), ol_strides[0], ol_strides[1], _p(obj_ling_idx, torch.int64), _pf(gamma),
+              _pf(beta), _pf(pre), _pf(stats), _pf(out), B, T, R, S, H, word_emb.shape[0], pos_emb.shape[0], float(eps), float(drop_p),
+              _p(seed), int(tag), _stream())
+    return out
+
+
+def embed_f32_bwd(dy, pre, stats, gamma, lay, text_ids, text_type, obj_ling_idx, d_word, d_pos, d_type, d_end, d_gamma, d_beta, d_text_vis,
+                  dtv_strides, d_obj_vis, dov_strides, d_obj_ling, dol_strides, B, T, R, S, H, drop_p=0.0, seed=None, tag=0):
+    """embed_bwd on an fp32 dy: table gradients ACCUMULATED into the flat fp32 gradient, visual-part gradients written in fp32."""
+    _lib.call("vlb_embed_f32_bwd", _pf(dy), _pf(pre), _pf(stats), _pf(gamma), _p(lay["code"]), _p(lay["text_len"]),
+              _p(text_ids, torch.int64), _p(text_type, torch.int64), _p(obj_ling_idx, torch.int64), _pf(d_word), _pf(d_pos), _pf(d_type),
+              _pf(d_end), _pf(d_gamma), _pf(d_beta), _pf(d_text_vis), dtv_strides[0], dtv_strides[1], _pf(d_obj_vis), dov_strides[0],
+              dov_strides[1], _pf(d_obj_ling), dol_strides[0], dol_strides[1], B, T, R, S, H, d_word.shape[0], d_pos.shape[0],
+              float(drop_p), _p(seed), int(tag), _stream())
+
+
+def dropout_f32(x, y, drop_p, seed, tag):
+    """y = x * keep(seed, tag, i) / (1 - p) on contiguous fp32 tensors: the mask of dropout_bf16 for the same (seed, tag)."""
+    assert x.is_contiguous() and y.is_contiguous() and x.numel() == y.numel()
+    _lib.call("vlb_dropout_f32", _pf(x), _pf(y), x.numel(), float(drop_p), _p(seed), int(tag), _stream())
+    return y
+
+
+def mul_f32(a, b, out):
+    assert a.is_contiguous() and b.is_contiguous() and out.is_contiguous() and a.numel() == b.numel() == out.numel()
+    _lib.call("vlb_mul_f32", _pf(a), _pf(b), _pf(out), a.numel(), _stream())
+    return out
+
+
+def relu_bwd_f32(g, y, out):
+    assert g.is_contiguous() and y.is_contiguous() and out.is_contiguous() and g.numel() == y.numel() == out.numel()
+    _lib.call("vlb_relu_bwd_f32", _pf(g), _pf(y), _pf(out), g.numel(), _stream())
+    return out
+
+
+def bce_logits_f32_fwd_bwd(logits, A, label, loss_out, gscale=1.0, logits_copy=None, pos_weight=1.0):
+    """logits fp32 [rows, ld >= A, ld % 4 == 0] <- gscale * w * (sigmoid(x) - y) / rows in place (columns >= A: 0); loss_out += BCE-with-
+    logits * A; w = pos_weight on the positive labels.  The rows' sums go through a scratch vector and are added in a fixed order: the
+    loss is the same bits on every run."""
+    rows = logits.shape[0]
+    row_loss = torch.empty((max(rows, 1),), dtype=torch.float32, device=logits.device)
+    _lib.call("vlb_bce_logits_f32_fwd_bwd", _pf(logits), _ld(logits), rows, A, _pf(label), _ld(label), float(gscale), float(pos_weight),
+              _pf(loss_out), _pf(row_loss), _pf(logits_copy), _ld(logits_copy), _stream())

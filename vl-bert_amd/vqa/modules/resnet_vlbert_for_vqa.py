@@ -9,13 +9,17 @@ Composition, as in the reference:  FastRCNN mirror (precomputed features or imag
 with fused bias / ReLU / GELU epilogues, LayerNorm, counter-RNG dropout (vlb_dropout_bf16), vlb_bce_logits_fwd_bwd (loss and its
 gradient in one pass), TN weight-gradient GEMMs.  CLASSIFIER_TYPE "2fc" (config default) and "mlm" (the shipped cfgs/vqa/*.yaml)
 are built; "1fc", BLIND, NO_GROUNDING, CLASSIFIER_SIGMOID, cnn_reg_loss raise NotImplementedError.
+
+`fp32_ends` (VLBERT config key, or VLB_FP32_ENDS=1; needs `fp32_encoder`): the whole route in fp32 -- the FastRCNN mirror's fp32
+precomputed branch, the fp32 embedding and encoder, the classifier built from the fp32 stages of common/heads.py on the master weights,
+vlb_bce_logits_f32_fwd_bwd.  No 16-bit tensor between the inputs and the loss, forward or backward.
 """
 import torch
 import torch.nn as nn
 
 from ... import ops
 from ...common import language_pretrained as _lp
-from ...common.heads import Drop, Head, LayerNorm, Linear, Linear16, cfg_get, run_head
+from ...common.heads import Drop, Drop32, Head, Head32, LayerNorm, LayerNorm32, Linear, Linear16, Linear32, Weight32, cfg_get, run_head
 from ...common.module import Module
 
 CLS, SEP, MASK = 101, 102, 103          # ids of '[CLS]', '[SEP]', '[MASK]' in the BERT vocabularies (tokenizer lookups in the reference)
@@ -24,6 +28,7 @@ _TAG0, _TAG1 = 2001, 2002
 
 class ResNetVLBERT(Module):
     SEED = 30011
+    FP32_ENDS = True
 
     def _check_config(self, net, vl):
         if cfg_get(net, "BLIND", False) or cfg_get(net, "NO_GROUNDING", False) or cfg_get(net, "ENABLE_CNN_REG_LOSS", False):
@@ -42,20 +47,26 @@ class ResNetVLBERT(Module):
         self.hc = int(cfg_get(net, "CLASSIFIER_HIDDEN_SIZE", 1024)) if self.classifier == "2fc" else H
         mlp = nn.Module()
         last = lambda lin: Linear(Linear16(lin, pad_k=True))          # its input rows are padded to a multiple of 64 columns
+        Drop_, LayerNorm_, Head_ = Drop, LayerNorm, Head
+        if self.fp32_ends:                        # the same stages in fp32, on the master weights
+            Linear_ = lambda lin, act=None: Linear32(Weight32(lin), act)
+            last, Drop_, LayerNorm_, Head_ = Linear_, Drop32, LayerNorm32, Head32
+        else:
+            Linear_ = lambda lin, act=None: Linear(Linear16(lin), act)
         if self.classifier == "2fc":              # Dropout -> Linear(H, hc) -> ReLU -> Dropout -> Linear(hc, answers)  (:54-63)
             mlp.add_module("1", self._lin(self.hc, H))
             mlp.add_module("4", self._lin(self.answers, self.hc))
-            stages = [Drop(_TAG0), Linear(Linear16(getattr(mlp, "1")), "relu"), Drop(_TAG1), last(getattr(mlp, "4"))]
+            stages = [Drop_(_TAG0), Linear_(getattr(mlp, "1"), "relu"), Drop_(_TAG1), last(getattr(mlp, "4"))]
         elif self.classifier == "1fc":            # Dropout -> Linear(H, answers)  (:64-68)
             mlp.add_module("1", self._lin(self.answers, H))
-            stages = [Drop(_TAG0), last(getattr(mlp, "1"))]
+            stages = [Drop_(_TAG0), last(getattr(mlp, "1"))]
         else:                                     # BertPredictionHeadTransform (dense + gelu + LayerNorm) -> Dropout -> Linear  (:69-74)
             mlp.add_module("0", self._transform(layer_norm=True))
             mlp.add_module("2", self._lin(self.answers, H))
             tr = getattr(mlp, "0")
-            stages = [Linear(Linear16(tr.dense), "gelu"), LayerNorm(tr.LayerNorm), Drop(_TAG1), last(getattr(mlp, "2"))]
+            stages = [Linear_(tr.dense, "gelu"), LayerNorm_(tr.LayerNorm), Drop_(_TAG1), last(getattr(mlp, "2"))]
         self.final_mlp = mlp
-        self._head = Head(stages, self._seed)
+        self._head = Head_(stages, self._seed)
 
     def init_weight(self):
         """resnet_vlbert_for_vqa.py:84-110: xavier-uniform classifier Linears, zero biases, N(0, 0.02) object word embedding."""
@@ -108,9 +119,11 @@ class ResNetVLBERT(Module):
         A = self.answers
 
         def bce(logits, logits_copy, loss, g, fresh):
-            ops.bce_logits_fwd_bwd(logits, A, label.detach().float().contiguous(), loss, gscale=g, logits_copy=logits_copy if fresh else None)
+            fn = ops.bce_logits_f32_fwd_bwd if self.fp32_ends else ops.bce_logits_fwd_bwd
+            fn(logits, A, label.detach().float().contiguous(), loss, gscale=g, logits_copy=logits_copy if fresh else None)
         logits, loss = run_head(self._head, hm, self.cls_drop if train else 0.0, bce if label is not None else None)
-        return logits[:, :A].float(), loss
+        # (fp32_ends: the head's own fp32 buffer, rewritten by its next pass -- the caller gets a copy)
+        return (logits[:, :A].clone() if logits.dtype == torch.float32 else logits[:, :A].float()), loss
 
     def train_forward(self, image, boxes, im_info, question, label):
         logits, loss = self._classify(image, boxes, im_info, question, label, self.training)
