@@ -616,6 +616,41 @@ int vlb_relu_bwd_f32(const float* g, const float* y, float* out, long n, vlb_str
 int vlb_bce_logits_f32_fwd_bwd(float* logits, long ld, int rows, int A, const float* label, long ldl, float gscale, float pos_weight,
                                float* loss_out, float* row_loss, float* logits_copy, long ldcopy, vlb_stream_t stream);
 
+/* ---- fp32 front end, hand-over and losses of the pre-training step (csrc/f32_pretrain.hip; `fp32_full` of engine.py) ----
+ * With the entry points above these put every tensor between the input buffers and the two loss values, and between the losses and
+ * the fp32 gradient, in fp32.  Pointers 16-byte aligned, widths and leading dimensions % 4 == 0.  Every sum is taken in a fixed order
+ * (no float atomics between workgroups): the same bits on every run and on both builds of the library.
+ *   vlb_mask_feature_f32   : a[row, 2048:4096] <- dropout(mask_emb) for the valid boxes with sel[row] == 1 -- the mvrc_ops substitution
+ *                            of vlb_obj_prep_fwd, applied to the output of vlb_obj_prep_f32_fwd (same dropout element index)
+ *   vlb_masked_colsum_f32  : vlb_masked_colsum on an fp32 source (C % 4 == 0; row_elems / col_off even with dropout)
+ *   vlb_select_rows2_f32   : out[i] = table[sel[i] != 0 ? 1 : 0] (the 2-row linguistic table of the objects as a dense operand)
+ *   vlb_table2_grad_f32    : dst[0] += sum of the rows with sel == 0, dst[1] += those with sel == 1 (dst [2, H])
+ *   vlb_group_rowsum_f32   : dst[g] = sum of rows g * group_rows .. + group_rows - 1 of src [groups * group_rows, H]
+ *   vlb_add_rows_f32       : dst[r] += src[r]
+ *   vlb_gather_rows_f32 / vlb_scatter_rows_f32 / vlb_head_grad_combine_f32 : vlb_gather_rows / vlb_scatter_rows /
+ *                            vlb_head_grad_combine on fp32 rows (idx < 0: a zero row / skipped)
+ *   vlb_ce_f32_fwd_bwd / _compact, vlb_soft_ce_f32_fwd_bwd : the losses of vlb_ce_fwd_bwd / _compact / vlb_soft_ce_fwd_bwd on fp32
+ *                            logits (ld % 4 == 0, pad columns take no part and get a zero gradient, gradient in place, counts written,
+ *                            loss_out +=); row_loss = scratch of `rows` floats, summed in a fixed order */
+int vlb_mask_feature_f32(float* a, const float* boxes, long ldbox, const int64_t* sel, const float* mask_emb, int rows, float drop_p,
+                         const uint32_t* seed, uint32_t tag, vlb_stream_t stream);
+int vlb_masked_colsum_f32(const float* src, long lds, const int64_t* sel, int rows, int C, float* dst, float drop_p, const uint32_t* seed,
+                          uint32_t tag, uint32_t row_elems, uint32_t col_off, vlb_stream_t stream);
+int vlb_select_rows2_f32(const float* table, const int64_t* sel, float* out, int n, int H, vlb_stream_t stream);
+int vlb_table2_grad_f32(const float* src, const int64_t* sel, float* dst, int rows, int H, vlb_stream_t stream);
+int vlb_group_rowsum_f32(const float* src, int groups, int group_rows, int H, float* dst, long ldd, vlb_stream_t stream);
+int vlb_add_rows_f32(float* dst, long ldd, const float* src, long lds, int rows, int H, vlb_stream_t stream);
+int vlb_gather_rows_f32(const float* src, const int32_t* idx, float* out, int n, int H, vlb_stream_t stream);
+int vlb_scatter_rows_f32(const float* src, const int32_t* idx, float* out, int n, int H, vlb_stream_t stream);
+int vlb_head_grad_combine_f32(const float* d_text, const float* d_obj, const int32_t* code, float* dx, int B, int T, int R, int S, int H,
+                              vlb_stream_t stream);
+int vlb_ce_f32_fwd_bwd(float* logits, long ld, int rows, int V, const int64_t* labels, float* counts, float gscale, float* loss_out,
+                       float* row_loss, float* logits_copy, long ldcopy, vlb_stream_t stream);
+int vlb_ce_f32_fwd_bwd_compact(float* logits, long ld, int rows, int V, const int64_t* labels_c, const float* count0, const float* count1,
+                               float gscale, float* loss_out0, float* loss_out1, float* row_loss, vlb_stream_t stream);
+int vlb_soft_ce_f32_fwd_bwd(float* logits, long ld, int rows, int C, const float* target, long ldt, float* tsum, float* counts, float gscale,
+                            float* loss_out, float* row_loss, float* logits_copy, long ldcopy, vlb_stream_t stream);
+
 /* ---- data-parallel gradient exchange for a C / C++ host: RCCL over xGMI (csrc/comm.hip) ---------------------------------------
  * Replaces the gradient all-reduce that torch DistributedDataParallel / apex DDP issue for the reference
  * (pretrain/function/train.py:89-90,353-354; vqa/function/train.py:327; vcr/function/train.py:330): one SUM over the ranks of every

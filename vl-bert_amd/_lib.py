@@ -126,6 +126,19 @@ _SIGS = {
     "vlb_mul_f32": "pppls",
     "vlb_relu_bwd_f32": "pppls",
     "vlb_bce_logits_f32_fwd_bwd": "pliiplffpppls",
+    # fp32 front end, hand-over and losses of the pre-training step (csrc/f32_pretrain.hip)
+    "vlb_mask_feature_f32": "pplppifpus",
+    "vlb_masked_colsum_f32": "plpiipfpuuus",
+    "vlb_select_rows2_f32": "pppiis",
+    "vlb_table2_grad_f32": "pppiis",
+    "vlb_group_rowsum_f32": "piiipls",
+    "vlb_add_rows_f32": "plpliis",
+    "vlb_gather_rows_f32": "pppiis",
+    "vlb_scatter_rows_f32": "pppiis",
+    "vlb_head_grad_combine_f32": "ppppiiiiis",
+    "vlb_ce_f32_fwd_bwd": "pliippfpppls",
+    "vlb_ce_f32_fwd_bwd_compact": "pliipppfppps",
+    "vlb_soft_ce_f32_fwd_bwd": "pliiplppfpppls",
     "vlb_scale_f32": "plfs",
     "vlb_cast_f32_bf16": "ppls",
     "vlb_cast_bf16_f32": "ppls",

@@ -6,7 +6,7 @@ HERE="$(cd "$(dirname "${BASH_SOURCE[0]}")" && pwd)"
 OUT="${1:-$HERE/..}"
 HIPCC="${HIPCC:-/opt/rocm/bin/hipcc}"
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wall -Wno-unused-function -ffp-contract=fast"
-SRCS="api options gemm gemm_p8 gemm_tn8 layernorm embed loss metrics finetune_metrics attention attention_long attention_probs optim roi_align vision f32_path f32_ends comm grounding"
+SRCS="api options gemm gemm_p8 gemm_tn8 layernorm embed loss metrics finetune_metrics attention attention_long attention_probs optim roi_align vision f32_path f32_ends f32_pretrain comm grounding"
 JOBS="${VLB_BUILD_JOBS:-$(nproc)}"
 mkdir -p "$HERE/obj" "$HERE/obj_f16"
 todo=()

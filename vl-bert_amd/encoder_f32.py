@@ -13,6 +13,7 @@ VLB_PRECISION=f16: 2^-12 per rounding, a handful of roundings in total); `forwar
 roundings per layer in a 16-bit build -- see none.  Measured: tests/test_f32_encoder_gpu.py.
 With the engine's `fp32_ends` the boundary is gone on the VQA fine-tuning route: the fused fp32 embedding (csrc/f32_ends.hip) writes
 X[0] here, the caller reads X[L] and hands an fp32 d X[L] in, and `forward` / `backward` skip their casts (tests/test_fp32_ends_gpu.py).
+The engine's `fp32_full` does the same for the pre-training step (pretrain_f32.py writes X[0], its heads read X[L]).
 
 Attention is composed from the batched GEMM: scores = Q.K^T / 8 per (sample, head) -> softmax (+ key mask, + dropout) -> P.V with V
 transposed per head; the backward is the five products of the same shapes.  The probabilities are kept per layer ([B, h, S, Sp] fp32:
@@ -147,7 +148,7 @@ class EncoderF32:
         if p_a > 0 and self.Pd is None:
             self.Pd = [torch.zeros((Bt * nh * S, Sp), dtype=F32, device=e.dev) for _ in range(L)]
         seed, mask = e.seed, e.lay["attn_mask"]
-        ends = getattr(e, "fp32_ends", False)      # X[0] was written in fp32 by the embedding; X[L] is read in fp32
+        ends = getattr(e, "fp32_ends", False) or getattr(e, "fp32_full", False)      # X[0] was written in fp32 by the embedding; X[L] is read in fp32
         if not ends:
             ops.cast_bf16_f32(e.X[0], self.X[0])
         bh = (Bt, nh)
@@ -179,7 +180,7 @@ class EncoderF32:
         H, I, L, nh, M, S, Sp, Bt = self.H, self.I, self.L, self.nh, self.M, self.S, self.Sp, self.Bt
         seed = e.seed
         bh = (Bt, nh)
-        ends = getattr(e, "fp32_ends", False)
+        ends = getattr(e, "fp32_ends", False) or getattr(e, "fp32_full", False)
         dx = dx16 if ends else self.dx[0]
         if not ends:
             ops.cast_bf16_f32(dx16, dx)

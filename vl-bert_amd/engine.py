@@ -168,7 +168,7 @@ class PretrainEngine:
     def __init__(self, cfg, B, T, R, device="cuda:0", train=True, lr=1e-4, weight_decay=1e-4, max_grad_norm=10.0,
                  betas=(0.9, 0.999), eps=1e-6, seed=1234, grad_accum=1, process_group=None, keep_logits=False, flat=None,
                  B_aux=0, core=False, core_heads=True, core_sequence=False, lr_schedule=None, warmup_steps=0, t_total=0,
-                 image_size=None, dp_mode="default", dp_wire="default", loss_scale=None, encoder_fp32=False, max_seq=256, fp32_ends=False):
+                 image_size=None, dp_mode="default", dp_wire="default", loss_scale=None, encoder_fp32=False, max_seq=256, fp32_ends=False, fp32_full=False):
         cfg.validate()
         # fp32_ends: the module-API front end (visual LayerNorms, fused embedding) and the hand-over of the sequence output run in fp32
         # too (csrc/f32_ends.hip), so that an encoder_fp32 engine holds no 16-bit tensor between its inputs and X[L].  One route only:
@@ -176,6 +176,13 @@ class PretrainEngine:
         self.fp32_ends = bool(fp32_ends)
         if self.fp32_ends:
             self._check_fp32_ends(cfg, T, R, core, core_heads, core_sequence, encoder_fp32, image_size, dp_mode, B_aux)
+        # fp32_full: the pre-training step itself in fp32 -- this engine's own front end, the MLM / MVRC heads and both losses
+        # (pretrain_f32.py, csrc/f32_pretrain.hip) around the fp32 encoder.  One configuration (precomputed features, no pooler, no
+        # relationship loss, no text-only samples, no loss scale): checked here, before anything is allocated
+        self.fp32_full = bool(fp32_full)
+        if self.fp32_full:
+            self._check_fp32_full(cfg, T, R, core, encoder_fp32, image_size, dp_mode, B_aux, loss_scale)
+            loss_scale = 1.0
         # max_seq: the longest packed sequence S = T + R + 1 this engine may be built for, 256..512.  Up to 256 positions attention runs
         # the whole-sequence kernels (csrc/attention.hip), 257..512 the streaming ones (csrc/attention_long.hip: seven products per tile
         # pair instead of five).  The default stays 256 so that a caller opts into the long path knowingly.
@@ -473,6 +480,16 @@ class PretrainEngine:
                                  "keeps them authoritative on the owner only)")
             from .encoder_f32 import EncoderF32
             self.enc32 = EncoderF32(self)
+        self.pre32 = None
+        if self.fp32_full:
+            # the buffers callers read are the fp32 ones: X is the fp32 encoder's, the logits (and their kept copies) are fp32 twins
+            # of the 16-bit tensors allocated above, which are released
+            from .pretrain_f32 import PretrainF32
+            self.X = self.enc32.X
+            self.mlm_logits, self.mvrc_logits = zf(BT, self.Vp), zf(BR, self.Cp)
+            self.mlm_logits_copy = zf(BT, self.Vp) if keep_logits else None
+            self.mvrc_logits_copy = zf(BR, self.Cp) if keep_logits else None
+            self.pre32 = PretrainF32(self)
 
     @staticmethod
     def _check_fp32_ends(cfg, T, R, core, core_heads, core_sequence, encoder_fp32, image_size, dp_mode, B_aux):
@@ -498,6 +515,31 @@ class PretrainEngine:
             bad.append("a sequence of %d+%d+1 positions (the fp32 encoder handles at most 256)" % (T, R))
         if bad:
             raise ValueError("fp32_ends needs core=True, core_heads=False, core_sequence=True, encoder_fp32=True and no pooler; "
+                             "unsupported here: " + "; ".join(bad))
+
+    @staticmethod
+    def _check_fp32_full(cfg, T, R, core, encoder_fp32, image_size, dp_mode, B_aux, loss_scale):
+        """fp32_full covers the pre-training step of the precomputed-feature configuration on an fp32 encoder; everything else is named."""
+        from . import loss_scale as LS
+        bad = []
+        if core:
+            bad.append("core=True (the module-API engine; its sequence-output route is fp32_ends)")
+        if not encoder_fp32:
+            bad.append("encoder_fp32=False")
+        if cfg.e2e or image_size is not None:
+            bad.append("the image branch (CNN, ROIAlign)")
+        if B_aux:
+            bad.append("B_aux > 0 (multitask text-only samples)")
+        if cfg.with_pooler or cfg.with_rel_loss:
+            bad.append("with_pooler / with_rel_loss (the pooler and the relationship head and loss)")
+        if dp_mode == "sharded":
+            bad.append("dp_mode='sharded' (the sharded optimizer)")
+        if loss_scale is not None and (LS.resolve(loss_scale) is not None or float(loss_scale) != 1.0):
+            bad.append("loss_scale=%r (a loss scaler: fp32 gradients need none)" % (loss_scale,))
+        if T + R + 1 > 256:
+            bad.append("a sequence of %d+%d+1 positions (the fp32 encoder handles at most 256)" % (T, R))
+        if bad:
+            raise ValueError("fp32_full needs core=False, encoder_fp32=True, precomputed features, MLM + MVRC only and no loss scale; "
                              "unsupported here: " + "; ".join(bad))
 
     # ------------------------------------------------------------------------------------------
@@ -582,6 +624,8 @@ class PretrainEngine:
         self._tbatch.run()
         if self.enc32 is not None:
             self.enc32.refresh()
+        if self.pre32 is not None:
+            self.pre32.refresh()
 
     # ------------------------------------------------------------------------------------------
     # batch
@@ -693,6 +737,9 @@ class PretrainEngine:
         touched.  No host synchronisation (read with metric_counts() / loss_values(), whose MLM-overflow contract applies)."""
         if self.core:
             raise ValueError("eval_step: the module-API engine has no loss heads (metrics belong to the wrapper that owns the labels)")
+        if self.fp32_full:
+            raise ValueError("eval_step: not built for an fp32_full engine (the validation kernels of csrc/metrics.hip read 16-bit logits); "
+                             "validate on an engine without fp32_full")
         self._forward_to_logits(False)
         B, T, Ba, V, C = self.B, self.T, self.Ba, self.cfg.vocab_size, self.cfg.visual_region_classes
         losses, acc, nw = self.losses, self.metric_acc, B * T
@@ -746,6 +793,9 @@ class PretrainEngine:
         cfg, B, T, R, S, Bt, Ba = self.cfg, self.B, self.T, self.R, self.S, self.Bt, self.Ba
         H = cfg.hidden_size
         w16, w32, seed = self.w16, self.w32, self.seed
+        if self.fp32_full:      # every tensor fp32, written straight into the fp32 encoder's X[0] (pretrain_f32.py)
+            self.pre32.front_fwd(p_h, p_ds)
+            return
         # --- e2e: ResNet trunk -> ROIAlign -> layer4 head -> avg-pool, written into the feature slots of in_boxes; the raw
         #     pixels are masked by the dataset, so no mask embedding is substituted (mask_visual_embed=None, :120-127) ----
         e2e = self.vision is not None
@@ -783,6 +833,9 @@ class PretrainEngine:
         if self.enc32 is not None:
             self.enc32.forward(p_h, p_a)
             if self.fp32_ends:      # the caller reads enc32.X[L] (sequence_output): no 16-bit copy, no gathers from one
+                return
+            if self.fp32_full:      # the fp32 heads gather from enc32.X[L]
+                self.pre32.heads_fwd()
                 return
         for l in range(L if self.enc32 is None else 0):
             r, x = self.layer[l], self.X[l]
@@ -841,6 +894,9 @@ class PretrainEngine:
         """Loss values + d(logits) written in place over the logits.  Called again by the nn.Module mirror (keep=False:
         logits restored from the kept copies, loss slots untouched) when autograd hands down an upstream scale != 1."""
         B, T, Ba, V, C = self.B, self.T, self.Ba, self.cfg.vocab_size, self.cfg.visual_region_classes
+        if self.fp32_full:
+            self.pre32.losses(gscale, keep)
+            return
         if keep:
             losses, mcopy, vcopy = self.losses, self.mlm_logits_copy, self.mvrc_logits_copy
         else:
@@ -958,7 +1014,9 @@ class PretrainEngine:
             self._wT_stale = False
         if self.buckets is not None and on_layer_done is None:
             self.buckets.invalidate()      # (a micro-step without the exchange: the reduced images are stale until a hooked backward)
-        if self.with_heads:
+        if self.fp32_full:      # heads and hand-over in fp32: the fp32 d X[L] goes into the fp32 encoder's backward
+            dx32 = self.pre32.heads_bwd()
+        elif self.with_heads:
             # --- MLM head ------------------------------------------------------------------------------------
             pm = "vlbert.mlm_head.predictions."
             compact = self._mlm_compact_now and not self.core
@@ -988,8 +1046,8 @@ class PretrainEngine:
                 pr = "vlbert.relationsip_head.caption_image_relationship."
                 self._wgrad(self.rel_logits[:, :2], self.pooled, g32[pr + "weight"], g32[pr + "bias"])
                 ops.gemm_nt(self.rel_logits, wT[pr + "weight"], self.d_pooled)      # K = 64: two logits + zero padding
-        dx = self.dX32 if self.fp32_ends else self.dXa
-        if not self.seq_out:      # (sequence mode: the caller's d(sequence_output) is already in dXa)
+        dx = self.dX32 if self.fp32_ends else (dx32 if self.fp32_full else self.dXa)
+        if not self.seq_out and not self.fp32_full:      # (sequence mode: the caller's d(sequence_output) is already in dXa)
             ops.head_grad_combine(self.d_text_out, self.d_obj_out, self.lay["code"], dx, Bt, T, R, S, H)
         if cfg.with_pooler and (cfg.with_rel_loss or not self.with_heads):
             # d(pooled) came from the relationship head (or from the caller in hidden-state mode): through tanh and the
@@ -1059,6 +1117,8 @@ class PretrainEngine:
             self._hazards.before_accumulate(*self._front_grads())
         if self.core:
             self._front_core_bwd(dx, p_h)
+        elif self.fp32_full:
+            self.pre32.front_bwd(dx, p_h, p_ds, on_layer_done)
         else:
             self._front_pretrain_bwd(dx, p_h, p_ds, on_layer_done)
         self._join_side()

@@ -990,3 +990,99 @@ def bce_logits_f32_fwd_bwd(logits, A, label, loss_out, gscale=1.0, logits_copy=N
     row_loss = torch.empty((max(rows, 1),), dtype=torch.float32, device=logits.device)
     _lib.call("vlb_bce_logits_f32_fwd_bwd", _pf(logits), _ld(logits), rows, A, _pf(label), _ld(label), float(gscale), float(pos_weight),
               _pf(loss_out), _pf(row_loss), _pf(logits_copy), _ld(logits_copy), _stream())
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# fp32 front end, hand-over and losses of the pre-training step (csrc/f32_pretrain.hip; `fp32_full`): every operand fp32
+# ---------------------------------------------------------------------------------------------------------------
+def mask_feature_f32(a, boxes, sel, mask_emb, drop_p=0.0, seed=None, tag=0):
+    """a fp32 [B*R, 4096] (obj_prep_f32_fwd's output): the feature half of the valid boxes with sel == 1 <- dropout(mask_emb [2048])."""
+    B, R, ldb = boxes.shape
+    assert a.is_contiguous() and a.shape[-1] == 4096 and a.numel() == B * R * 4096 and boxes.is_contiguous() and mask_emb.numel() == 2048
+    _lib.call("vlb_mask_feature_f32", _pf(a), _pf(boxes), ldb, _p(sel, torch.int64), _pf(mask_emb), B * R, float(drop_p), _p(seed), int(tag),
+              _stream())
+    return a
+
+
+def masked_colsum_f32(src, sel, dst, drop_p=0.0, seed=None, tag=0, row_elems=0, col_off=0):
+    """dst[c] += sum over the rows with sel == 1 of src[r][c] * dropmask(r * row_elems + col_off + c), in a fixed order."""
+    rows, C = src.shape
+    _lib.call("vlb_masked_colsum_f32", _pf(src), _ld(src), _p(sel, torch.int64), rows, C, _pf(dst), float(drop_p), _p(seed), int(tag),
+              int(row_elems), int(col_off), _stream())
+
+
+def select_rows2_f32(table, sel, out):
+    """out [n, H] <- table[sel != 0] of a contiguous fp32 [2, H] table."""
+    n, H = out.shape
+    assert table.is_contiguous() and out.is_contiguous() and table.numel() == 2 * H
+    _lib.call("vlb_select_rows2_f32", _pf(table), _p(sel, torch.int64), _pf(out), n, H, _stream())
+    return out
+
+
+def table2_grad_f32(src, sel, dst):
+    """dst [2, H] += the sums of the rows of src [n, H] with sel == 0 / sel == 1, in a fixed order."""
+    n, H = src.shape
+    assert src.is_contiguous() and dst.is_contiguous() and dst.numel() == 2 * H
+    _lib.call("vlb_table2_grad_f32", _pf(src), _p(sel, torch.int64), _pf(dst), n, H, _stream())
+
+
+def group_rowsum_f32(src, group_rows, dst):
+    """dst [groups, H] <- sums of the consecutive groups of `group_rows` rows of src [groups * group_rows, H]."""
+    groups, H = dst.shape
+    assert src.is_contiguous() and src.shape == (groups * group_rows, H)
+    _lib.call("vlb_group_rowsum_f32", _pf(src), groups, int(group_rows), H, _pf(dst), _ld(dst), _stream())
+    return dst
+
+
+def add_rows_f32(dst, src):
+    """dst [rows, H] += src [rows, H] (2-D views with their own row strides)."""
+    rows, H = dst.shape
+    assert src.shape == dst.shape
+    _lib.call("vlb_add_rows_f32", _pf(dst), _ld(dst), _pf(src), _ld(src), rows, H, _stream())
+    return dst
+
+
+def gather_rows_f32(src, idx, out):
+    n, H = out.shape
+    assert src.is_contiguous() and out.is_contiguous() and src.shape[1] == H
+    _lib.call("vlb_gather_rows_f32", _pf(src), _p(idx, torch.int32), _pf(out), n, H, _stream())
+    return out
+
+
+def scatter_rows_f32(src, idx, out):
+    assert src.is_contiguous() and out.is_contiguous() and src.shape[1] == out.shape[1] and idx.numel() <= src.shape[0]
+    _lib.call("vlb_scatter_rows_f32", _pf(src), _p(idx, torch.int32), _pf(out), idx.numel(), src.shape[1], _stream())
+    return out
+
+
+def head_grad_combine_f32(d_text, d_obj, code, dx, B, T, R, S, H):
+    _lib.call("vlb_head_grad_combine_f32", _pf(d_text), _pf(d_obj), _p(code, torch.int32), _pf(dx), B, T, R, S, H, _stream())
+    return dx
+
+
+def _row_loss(logits, row_loss):
+    rows = logits.shape[0]
+    if row_loss is None:
+        return torch.empty((max(rows, 1),), dtype=torch.float32, device=logits.device)
+    assert row_loss.numel() >= rows
+    return row_loss
+
+
+def ce_f32_fwd_bwd(logits, V, labels, counts, loss_out, gscale=1.0, logits_copy=None, row_loss=None):
+    """ce_fwd_bwd on fp32 logits [rows, ld % 4 == 0]; the rows' losses go through `row_loss` (scratch, allocated when not given) and
+    are added in a fixed order: the same bits on every run."""
+    row_loss = _row_loss(logits, row_loss)
+    _lib.call("vlb_ce_f32_fwd_bwd", _pf(logits), _ld(logits), logits.shape[0], V, _p(labels, torch.int64), _pf(counts), float(gscale),
+              _pf(loss_out), _pf(row_loss), _pf(logits_copy), _ld(logits_copy), _stream())
+
+
+def ce_f32_fwd_bwd_compact(logits, V, labels_c, count0, count1, loss_out0, loss_out1, gscale=1.0, row_loss=None):
+    row_loss = _row_loss(logits, row_loss)
+    _lib.call("vlb_ce_f32_fwd_bwd_compact", _pf(logits), _ld(logits), logits.shape[0], V, _p(labels_c, torch.int64), _pf(count0),
+              _pf(count1), float(gscale), _pf(loss_out0), _pf(loss_out1), _pf(row_loss), _stream())
+
+
+def soft_ce_f32_fwd_bwd(logits, C, target, tsum, counts, loss_out, gscale=1.0, logits_copy=None, row_loss=None):
+    row_loss = _row_loss(logits, row_loss)
+    _lib.call("vlb_soft_ce_f32_fwd_bwd", _pf(logits), _ld(logits), logits.shape[0], C, _pf(target), _ld(target), _pf(tsum), _pf(counts),
+              float(gscale), _pf(loss_out), _pf(row_loss), _pf(logits_copy), _ld(logits_copy), _stream())

@@ -18,10 +18,14 @@ IMAGE_FEAT_PRECOMPUTED: false (cfgs/pretrain/base_e2e_16x16G_fp16.yaml) runs the
 vision.py in front: `forward(image, boxes[B,R,4], ...)`.  The trainable convolution weights are Parameters that view the
 flat buffer in the engine's [O,KH,KW,I] layout (state_dict / load_state_dict convert from / to the reference's [O,I,KH,KW]);
 BatchNorm tensors and the frozen stages are buffers under the reference's names.  One image size per module (static shapes).
+`fp32_encoder` + `fp32_full` (VLBERT config keys, or VLB_ENCODER_FP32=1 + VLB_FP32_FULL=1): the engines are built with
+encoder_fp32=True, fp32_full=True -- front end, encoder, heads and losses in fp32 (../../pretrain_f32.py) -- and the returned logits are
+the engine's fp32 copies.  Precomputed features, no pooler, no relationship loss, not the multitask wrapper.
 Anything else raises NotImplementedError (nothing silently falls back to PyTorch eager).
 """
 from collections import OrderedDict
 
+import os
 import sys
 
 import torch
@@ -91,6 +95,20 @@ class ResNetVLBERTForPretraining(nn.Module):
             image_num_layers=int(_get(net, "IMAGE_NUM_LAYERS", 101)),
             image_frozen_stages=tuple(_get(net, "IMAGE_FROZEN_BACKBONE_STAGES", (1, 2))))
         self.cfg.validate()
+        self.fp32_full = bool(_get(vl, "fp32_full", False)) or os.environ.get("VLB_FP32_FULL", "0") == "1"
+        if self.fp32_full:
+            bad = []
+            if not (bool(_get(vl, "fp32_encoder", False)) or os.environ.get("VLB_ENCODER_FP32", "0") == "1"):
+                bad.append("without fp32_encoder (config key `fp32_encoder` / VLB_ENCODER_FP32=1)")
+            if self.e2e:
+                bad.append("the image branch (IMAGE_FEAT_PRECOMPUTED: false)")
+            if self.MULTITASK:
+                bad.append("the multitask wrapper (text-only samples)")
+            if self.cfg.with_pooler or self.with_rel:
+                bad.append("with_pooler / WITH_REL_LOSS")
+            if bad:
+                raise NotImplementedError("fp32_full is built for the precomputed-feature MLM + MVRC configuration on the fp32 encoder; "
+                                          "unsupported here: " + "; ".join(bad))
         if not torch.cuda.is_available():
             raise RuntimeError("ResNetVLBERTForPretraining (HIP) needs an MI355X: there is no CPU fallback")
         self.device_ = torch.device(device or ("cuda:%d" % torch.cuda.current_device()))
@@ -213,7 +231,8 @@ class ResNetVLBERTForPretraining(nn.Module):
         eng = lru_get(self._engines, (B, T, R, B_aux, image_size),
                       lambda: _engine.PretrainEngine(self.cfg, B, T, R, device=str(self.device_), keep_logits=True, flat=self.flat,
                                                      B_aux=B_aux, image_size=image_size, seed=ops.rank_seed(1234) // 2,   # per-rank dropout stream
-                                                     max_seq=_engine.MAX_SEQ))
+                                                     max_seq=_engine.MAX_SEQ,
+                                                     **(dict(encoder_fp32=True, fp32_full=True) if self.fp32_full else {})))
         if self.e2e and getattr(eng, "_buffers_version", None) != self._buffers_version:
             eng.vision.load_state_dict(self._vision_buffers, strict=False)      # BatchNorm tensors + frozen stages (trainables live in flat)
             eng._buffers_version = self._buffers_version
@@ -228,10 +247,14 @@ class ResNetVLBERTForPretraining(nn.Module):
     def _padded_logits(self, eng, Bt):
         """fp32 logits re-padded like the reference (:165-167, :195-200) -- needs max_len (host sync)."""
         V, C = self.cfg.vocab_size, self.cfg.visual_region_classes
-        mlm_logits = torch.empty((Bt, eng.T, V), dtype=torch.float32, device=self.device_)
-        ops.cast_bf16_f32(eng.mlm_logits_copy[:, :V].contiguous(), mlm_logits)
-        mvrc = torch.empty((eng.B, eng.R, C), dtype=torch.float32, device=self.device_)
-        ops.cast_bf16_f32(eng.mvrc_logits_copy[:, :C].contiguous(), mvrc)
+        if self.fp32_full:      # the engine's kept copies are fp32: no cast
+            mlm_logits = eng.mlm_logits_copy[:, :V].reshape(Bt, eng.T, V).clone()
+            mvrc = eng.mvrc_logits_copy[:, :C].reshape(eng.B, eng.R, C).clone()
+        else:
+            mlm_logits = torch.empty((Bt, eng.T, V), dtype=torch.float32, device=self.device_)
+            ops.cast_bf16_f32(eng.mlm_logits_copy[:, :V].contiguous(), mlm_logits)
+            mvrc = torch.empty((eng.B, eng.R, C), dtype=torch.float32, device=self.device_)
+            ops.cast_bf16_f32(eng.mvrc_logits_copy[:, :C].contiguous(), mvrc)
         mvrc[:, int(eng.lay["nobj"][:eng.B].max()):] = -10000.0
         # the reference's encoder runs on the batch trimmed to max(text_len + n_obj) + 1 packed positions
         # (common/visual_linguistic_bert.py:202,152-153), so its text logits stop there and the wrapper pads the rest with -10000

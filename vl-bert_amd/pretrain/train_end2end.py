@@ -170,11 +170,12 @@ def parse_args(argv=None):
     ap.add_argument("--batch-images", type=int, default=0, help="override TRAIN.BATCH_IMAGES (per GPU)")
     ap.add_argument("--text-len", type=int, default=0, help="text capacity of the step's static buffers (default 64; DATASET.SEQ_LEN with --data)")
     ap.add_argument("--regions", type=int, default=0, help="box capacity (default 36; DATASET.SEQ_LEN with --data)")
-    ap.add_argument("--compute", default="bf16", choices=["bf16", "fp16", "fp32", "cfg"],
+    ap.add_argument("--compute", default="bf16", choices=["bf16", "fp16", "fp32", "fp32-full", "cfg"],
                     help="arithmetic of the step.  bf16 (default): bf16 operands, fp32 accumulation / master weights, no loss scaling.  "
                          "fp16: the fp16 build of the library + static loss scale TRAIN.FP16_LOSS_SCALE (the reference's Apex mode, "
                          "pretrain/function/train.py:345-352; 'dynamic' -> 4096).  fp32: every encoder tensor in fp32 (encoder_f32.py), fp16 "
-                         "embedding / head kernels around it.  cfg: what the YAML names -- TRAIN.FP16 true -> fp16, false -> fp32")
+                         "embedding / head kernels around it.  fp32-full: the front end, the MLM / MVRC heads and both losses in fp32 as well "
+                         "(engine fp32_full: precomputed features, no pooler / relationship loss / text-only samples, no validation).  cfg: what the YAML names -- TRAIN.FP16 true -> fp16, false -> fp32")
     ap.add_argument("--data", action="store_true",
                     help="read the data sets the YAML names (DATASET.*: annotation jsonl, detector records with base64 boxes / class scores / "
                          "features, images, text corpora -- vl-bert_amd/pretrain/data) instead of synthetic batches; steps per epoch = "
@@ -228,6 +229,9 @@ def main(argv=None):
         args.text_len, args.regions = args.text_len or seq_len, args.regions or seq_len
     args.text_len, args.regions = args.text_len or 64, args.regions or 36
     r = resolve(config, world, args)
+    if r["compute"] == "fp32-full" and (args.val_steps > 0 or val_loader is not None):
+        raise ValueError("--compute fp32-full: validation (--val-steps, or a validation set named by the YAML) is not built in fp32 -- the "
+                         "validation kernels read 16-bit logits; validate with --compute fp32")
     if args.dry_run:
         if rank == 0:
             print(json.dumps({"resolved": r, "NETWORK.VLBERT": dict(config.NETWORK.VLBERT)}, indent=1, default=str))
@@ -238,6 +242,7 @@ def main(argv=None):
         raise RuntimeError("train_end2end: no GPU visible.  The MI355X engine has no CPU execution path (use --dry-run to check a "
                            "configuration without a GPU)")
     pkg = __package__.rsplit(".", 1)[0]
+    fp32_full = r["compute"] == "fp32-full"
     if r["compute"] != "bf16":      # fp16 and fp32 modes run on the fp16 build of the library (vl-bert_amd/_lib.py: one build per process)
         importlib.import_module(pkg + "._lib").set_precision("f16")
     engine = importlib.import_module(pkg + ".engine")
@@ -266,7 +271,8 @@ def main(argv=None):
                                 max_grad_norm=r["clip_grad_norm"], seed=r["seed"] + rank, B_aux=B_aux,
                                 lr_schedule=r["lr_schedule"], warmup_steps=r["warmup_steps"], t_total=max(r["t_total"], r["warmup_steps"] + 1),
                                 image_size=r["image_size"] if r["e2e"] else None, grad_accum=r["accumulate"],
-                                encoder_fp32=r["compute"] == "fp32", dp_mode="allreduce" if r["compute"] == "fp32" else "default",
+                                encoder_fp32=r["compute"] in ("fp32", "fp32-full"), fp32_full=fp32_full,
+                                dp_mode="allreduce" if r["compute"] in ("fp32", "fp32-full") else "default",
                                 loss_scale=r["loss_scale"] if r["compute"] == "fp16" else None, max_seq=engine.MAX_SEQ)
     eng.init_random(seed=r["seed"], visual_ln_init=float(g("visual_scale_object_init", 0.0)))
     # NETWORK.PARTIAL_PRETRAIN (+ _PREFIX_CHANGES): start from a pre-trained checkpoint's matching tensors (pretrain/function/train.py:297-313,
@@ -290,7 +296,8 @@ def main(argv=None):
         print("train_end2end: %s | %d GPU(s) x batch %d | lr %.3e wd %.1e clip %.1f | schedule %s warmup %d t_total %d%s" %
               (config.MODULE, world, B + B_aux, r["lr"], r["weight_decay"], r["clip_grad_norm"], r["lr_schedule"], r["warmup_steps"], r["t_total"],
                " | compute %s%s" % (r["compute"], (" (loss scale dynamic (%s))" % eng.scaler.spec.describe()) if eng.scaler is not None
-                                    else (" (loss scale %g)" % eng.loss_scale if eng.loss_scale != 1.0 else ""))), flush=True)
+                                    else (" (loss scale %g)" % eng.loss_scale if eng.loss_scale != 1.0 else "")) +
+               (" (fp32_full: front end, encoder, heads and losses in fp32, no loss scale)" if fp32_full else "")), flush=True)
     # checkpoints in the reference's format + resume (common/callbacks/epoch_end_callbacks/checkpoint.py, common/utils/load.py:20-54)
     ckpt = importlib.import_module(pkg + ".common.checkpoint")
     spe = max(1, int(r["steps_per_epoch"] // r["accumulate"]))           # optimizer steps per epoch
