@@ -261,6 +261,30 @@ int vlb_ce_eval(const void* logits, long ld, int rows, int V, const int64_t* lab
 int vlb_soft_ce_eval(const void* logits, long ld, int rows, int C, const float* target, long ldt, float* loss_out, int64_t* acc,
                      vlb_stream_t stream);
 
+/* ---- training-time metrics: the fused forward + backward losses that also count top-1 hits -------------------------
+ * vlb_ce_fwd_bwd / vlb_ce_fwd_bwd_compact / vlb_soft_ce_fwd_bwd (and the fp32 forms below) with two additions.  dscale (nullable): the
+ * gradient scale is gscale * *dscale as in the *_ds forms, NULL = the static scale.  acc = int64 [2], ACCUMULATED: acc[0] += counted rows
+ * whose argmax is the label (soft labels: argmax(logits) == argmax(target) over [0, C)), acc[1] += counted rows, with the rules of
+ * vlb_ce_eval / vlb_soft_ce_eval (label in [0, V); |sum(target) - 1| < 0.1; a tie goes to the lowest column; pad columns take no
+ * part).  The argmax rides in the pass that already reads the row; loss, gradient, zeroed pad columns and logits_copy are those of
+ * the plain entry points.  Integer atomics only: the same inputs give the same counters on every run.  The two-group form counts
+ * group 0 into acc0 and group 1 into acc1. */
+int vlb_ce_fwd_bwd_acc(void* logits, long ld, int rows, int V, const int64_t* labels, float* counts, float gscale, const float* dscale,
+                       float* loss_out, void* logits_copy, long ldcopy, int64_t* acc, vlb_stream_t stream);
+int vlb_ce_fwd_bwd_compact_acc(void* logits, long ld, int rows, int V, const int64_t* labels_c, const float* count0, const float* count1,
+                               float gscale, const float* dscale, float* loss_out0, float* loss_out1, int64_t* acc0, int64_t* acc1,
+                               vlb_stream_t stream);
+int vlb_soft_ce_fwd_bwd_acc(void* logits, long ld, int rows, int C, const float* target, long ldt, float* tsum, float* counts, float gscale,
+                            const float* dscale, float* loss_out, void* logits_copy, long ldcopy, int64_t* acc, vlb_stream_t stream);
+int vlb_ce_f32_fwd_bwd_acc(float* logits, long ld, int rows, int V, const int64_t* labels, float* counts, float gscale, const float* dscale,
+                           float* loss_out, float* row_loss, float* logits_copy, long ldcopy, int64_t* acc, vlb_stream_t stream);
+int vlb_ce_f32_fwd_bwd_compact_acc(float* logits, long ld, int rows, int V, const int64_t* labels_c, const float* count0, const float* count1,
+                                   float gscale, const float* dscale, float* loss_out0, float* loss_out1, float* row_loss, int64_t* acc0,
+                                   int64_t* acc1, vlb_stream_t stream);
+int vlb_soft_ce_f32_fwd_bwd_acc(float* logits, long ld, int rows, int C, const float* target, long ldt, float* tsum, float* counts,
+                                float gscale, const float* dscale, float* loss_out, float* row_loss, float* logits_copy, long ldcopy,
+                                int64_t* acc, vlb_stream_t stream);
+
 /* ---- fine-tuning evaluation (csrc/finetune_metrics.hip): the metrics of common/metrics/{vqa,vcr,refcoco}_metrics.py and the
  * predictions of the test-set writers on the device.  All three read fp32 data only, synchronise nothing, allocate nothing and
  * ACCUMULATE (+=) into their outputs.

@@ -68,6 +68,13 @@ _SIGS = {
     "vlb_soft_ce_fwd_bwd": "pliiplppfppls",
     "vlb_ce_eval": "plii" + "p" * 8 + "s",
     "vlb_soft_ce_eval": "pliiplpps",
+    # training-time metrics: the fused losses + [hits, counted rows] (nullable dscale, int64 [2] counters)
+    "vlb_ce_fwd_bwd_acc": "pliippfppplps",
+    "vlb_ce_fwd_bwd_compact_acc": "pliipppfppppps",
+    "vlb_soft_ce_fwd_bwd_acc": "pliiplppfppplps",
+    "vlb_ce_f32_fwd_bwd_acc": "pliippfpppplps",
+    "vlb_ce_f32_fwd_bwd_compact_acc": "pliipppfpppppps",
+    "vlb_soft_ce_f32_fwd_bwd_acc": "pliiplppfpppplps",
     "vlb_argmax_eval": "pliiiplppplpps",
     "vlb_binary_cls_eval": "plpliips",
     "vlb_joint_hits": "ppppips",

@@ -12,7 +12,7 @@
 // taken in a fixed order (no float atomics between workgroups), so losses and these gradients are the same bits on every run.
 #include <math.h>
 
-#include "vlb_common.h"
+#include "arg_reduce.h"
 
 namespace {
 
@@ -231,12 +231,55 @@ __global__ __launch_bounds__(256) void count_labels_f32_kernel(const int64_t* __
   if (threadIdx.x == 0) counts[0] = (float)(sh[0] + sh[1] + sh[2] + sh[3]);
 }
 
-__global__ __launch_bounds__(256) void ce_f32_kernel(float* __restrict__ logits, long ld, int V, const int64_t* __restrict__ labels,
-                                                     const float* __restrict__ n_valid, const float* __restrict__ n_valid2, float gscale,
-                                                     float* __restrict__ row_loss, float* __restrict__ logits_copy, long ldcopy) {
-  __shared__ float sh[4];
+// the ACC form's count: counts[0] as above, and the rows the accuracy counts (label in [0, V), vlb_ce_eval's rule) added to acc[1]
+__global__ __launch_bounds__(256) void count_labels_f32_acc_kernel(const int64_t* __restrict__ labels, int n, int V, float* __restrict__ counts,
+                                                                   vlb_u64* __restrict__ acc) {
+  __shared__ int sh[8];
+  int c = 0, k = 0;
+  for (int i = threadIdx.x; i < n; i += 256) {
+    const int64_t l = labels[i];
+    c += (l >= 0);
+    k += (l >= 0 && l < V);
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    c += __shfl_xor(c, o, 64);
+    k += __shfl_xor(k, o, 64);
+  }
+  if ((threadIdx.x & 63) == 0) {
+    sh[threadIdx.x >> 6] = c;
+    sh[4 + (threadIdx.x >> 6)] = k;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    counts[0] = (float)(sh[0] + sh[1] + sh[2] + sh[3]);
+    const int kk = sh[4] + sh[5] + sh[6] + sh[7];
+    if (kk) atomicAdd(acc + 1, (vlb_u64)kk);
+  }
+}
+
+// ACC (training-time metrics; the *_acc kernels below): the maximum pass also keeps the column of the maximum (lowest among equals,
+// arg_reduce.h); a counted row whose argmax is its label adds 1 to acc[0] (acc2[0] in group 1), an integer atomic.  The counted rows are
+// known before the launch: thread 0 of block 0 adds *n_valid / *n_valid2 to acc[1] / acc2[1] in the two-group form, before any early
+// return; in the one-group form count_labels_f32_acc_kernel has added them.  m, s and everything after them are computed as without ACC:
+// the same bits.  dscale (nullable, ACC only): gscale * *dscale, rounded once.
+template <bool ACC>
+__device__ __forceinline__ void ce_f32_body(float* __restrict__ logits, long ld, int V, const int64_t* __restrict__ labels,
+                                            const float* __restrict__ n_valid, const float* __restrict__ n_valid2, float gscale,
+                                            float* __restrict__ row_loss, float* __restrict__ logits_copy, long ldcopy,
+                                            const float* __restrict__ dscale, vlb_u64* __restrict__ acc, vlb_u64* __restrict__ acc2) {
+  __shared__ float sh[ACC ? 12 : 4];
   const int row = blockIdx.x, ldv = (int)ld;
-  if (n_valid2 && (float)row >= *n_valid) n_valid = n_valid2;      // two groups of compacted rows, each with its own mean
+  if (ACC && dscale) gscale = __fmul_rn(gscale, *dscale);
+  if (ACC && n_valid2 && row == 0 && threadIdx.x == 0) {
+    const vlb_u64 n0 = (vlb_u64)*n_valid, n1 = (vlb_u64)*n_valid2;
+    if (n0) atomicAdd(acc + 1, n0);
+    if (n1) atomicAdd(acc2 + 1, n1);
+  }
+  if (n_valid2 && (float)row >= *n_valid) {      // two groups of compacted rows, each with its own mean
+    n_valid = n_valid2;
+    if (ACC) acc = acc2;
+  }
   float* x = logits + (long)row * ld;
   const long label = labels[row];
   const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -258,12 +301,25 @@ __global__ __launch_bounds__(256) void ce_f32_kernel(float* __restrict__ logits,
   }
   const float xl = x[label];      // (every thread reads it here: the barriers of the reductions stand before the pass that overwrites it)
   float m = -INFINITY;
+  int idx = INT_MAX;      // (ACC) column of m; a thread's columns ascend, so `>` alone keeps its lowest column among equals
   for (int c = threadIdx.x * 4; c < V; c += 1024) {
     const float4 v = *(const float4*)(x + c);
+    if (ACC) {
+      float a = m;
+      if (v.x > a) { a = v.x; idx = c; }
+      if (c + 1 < V && v.y > a) { a = v.y; idx = c + 1; }
+      if (c + 2 < V && v.z > a) { a = v.z; idx = c + 2; }
+      if (c + 3 < V && v.w > a) { a = v.w; idx = c + 3; }
+    }
     m = fmaxf(m, v.x);
     if (c + 1 < V) m = fmaxf(m, v.y);
     if (c + 2 < V) m = fmaxf(m, v.z);
     if (c + 3 < V) m = fmaxf(m, v.w);
+  }
+  if (ACC) {
+    float a = m;
+    block_argmax(a, idx, sh + 4);
+    if (threadIdx.x == 0 && idx == (int)label) atomicAdd(acc, (vlb_u64)1);
   }
   m = block_max4(m, sh);
   float s = 0.f;
@@ -289,6 +345,19 @@ __global__ __launch_bounds__(256) void ce_f32_kernel(float* __restrict__ logits,
     g.w = (c + 3 < V) ? (expf(v.w - m) * inv_s - (c + 3 == lab ? 1.f : 0.f)) * sc : 0.f;
     *(float4*)(x + c) = g;
   }
+}
+
+__global__ __launch_bounds__(256) void ce_f32_kernel(float* __restrict__ logits, long ld, int V, const int64_t* __restrict__ labels,
+                                                     const float* __restrict__ n_valid, const float* __restrict__ n_valid2, float gscale,
+                                                     float* __restrict__ row_loss, float* __restrict__ logits_copy, long ldcopy) {
+  ce_f32_body<false>(logits, ld, V, labels, n_valid, n_valid2, gscale, row_loss, logits_copy, ldcopy, nullptr, nullptr, nullptr);
+}
+
+__global__ __launch_bounds__(256) void ce_f32_acc_kernel(float* __restrict__ logits, long ld, int V, const int64_t* __restrict__ labels,
+                                                         const float* __restrict__ n_valid, const float* __restrict__ n_valid2, float gscale,
+                                                         float* __restrict__ row_loss, float* __restrict__ logits_copy, long ldcopy,
+                                                         const float* __restrict__ dscale, vlb_u64* __restrict__ acc, vlb_u64* __restrict__ acc2) {
+  ce_f32_body<true>(logits, ld, V, labels, n_valid, n_valid2, gscale, row_loss, logits_copy, ldcopy, dscale, acc, acc2);
 }
 
 // loss_out0 += (sum of row_loss[0 .. split)) / max(n_valid, 1), loss_out1 += (sum of the rows behind) / max(n_valid2, 1); split = the
@@ -344,11 +413,20 @@ __global__ __launch_bounds__(256) void soft_count_f32_kernel(const float* __rest
 }
 
 // loss_row = log(s) * sum(t) - sum(t * (x - max)), s = sum exp(x - max);  dlogit_c = (softmax_c * sum(t) - t_c) * gscale / n_valid
-__global__ __launch_bounds__(256) void soft_ce_f32_kernel(float* __restrict__ logits, long ld, int C, const float* __restrict__ target, long ldt,
-                                                          const float* __restrict__ tsum, const float* __restrict__ n_valid, float gscale,
-                                                          float* __restrict__ row_loss, float* __restrict__ logits_copy, long ldcopy) {
-  __shared__ float sh[4];
+// ACC: the maximum pass also takes argmax(x) and, reading the target row there, argmax(t) over [0, C); a valid row where they agree adds 1
+// to acc[0]; thread 0 of block 0 adds the valid rows (*n_valid) to acc[1] before its early return.
+template <bool ACC>
+__device__ __forceinline__ void soft_ce_f32_body(float* __restrict__ logits, long ld, int C, const float* __restrict__ target, long ldt,
+                                                 const float* __restrict__ tsum, const float* __restrict__ n_valid, float gscale,
+                                                 float* __restrict__ row_loss, float* __restrict__ logits_copy, long ldcopy,
+                                                 const float* __restrict__ dscale, vlb_u64* __restrict__ acc) {
+  __shared__ float sh[ACC ? 20 : 4];
   const int row = blockIdx.x, ldv = (int)ld;
+  if (ACC && dscale) gscale = __fmul_rn(gscale, *dscale);
+  if (ACC && row == 0 && threadIdx.x == 0) {
+    const vlb_u64 n = (vlb_u64)*n_valid;
+    if (n) atomicAdd(acc + 1, n);
+  }
   float* x = logits + (long)row * ld;
   const float* t = target + (long)row * ldt;
   const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -370,12 +448,30 @@ __global__ __launch_bounds__(256) void soft_ce_f32_kernel(float* __restrict__ lo
     return;
   }
   float m = -INFINITY;
+  float a = -INFINITY, tm = -INFINITY;
+  int xi = INT_MAX, ti = INT_MAX;      // (ACC) ascending columns per thread: `>` keeps the lowest among equals
   for (int c = threadIdx.x * 4; c < C; c += 1024) {
     const float4 v = *(const float4*)(x + c);
+    if (ACC) {
+      const float vv[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        if (c + k < C) {
+          const float tv = t[c + k];
+          if (vv[k] > a) { a = vv[k]; xi = c + k; }
+          if (tv > tm) { tm = tv; ti = c + k; }
+        }
+      }
+    }
     m = fmaxf(m, v.x);
     if (c + 1 < C) m = fmaxf(m, v.y);
     if (c + 2 < C) m = fmaxf(m, v.z);
     if (c + 3 < C) m = fmaxf(m, v.w);
+  }
+  if (ACC) {
+    block_argmax(a, xi, sh + 4);
+    block_argmax(tm, ti, sh + 12);
+    if (threadIdx.x == 0 && xi == ti) atomicAdd(acc, (vlb_u64)1);
   }
   m = block_max4(m, sh);
   float s = 0.f, dot = 0.f;
@@ -403,6 +499,19 @@ __global__ __launch_bounds__(256) void soft_ce_f32_kernel(float* __restrict__ lo
     for (int k = 0; k < 4; ++k) g[k] = (c + k < C) ? (expf(vv[k] - m) * inv_s * ts - t[c + k]) * sc : 0.f;
     *(float4*)(x + c) = make_float4(g[0], g[1], g[2], g[3]);
   }
+}
+
+__global__ __launch_bounds__(256) void soft_ce_f32_kernel(float* __restrict__ logits, long ld, int C, const float* __restrict__ target, long ldt,
+                                                          const float* __restrict__ tsum, const float* __restrict__ n_valid, float gscale,
+                                                          float* __restrict__ row_loss, float* __restrict__ logits_copy, long ldcopy) {
+  soft_ce_f32_body<false>(logits, ld, C, target, ldt, tsum, n_valid, gscale, row_loss, logits_copy, ldcopy, nullptr, nullptr);
+}
+
+__global__ __launch_bounds__(256) void soft_ce_f32_acc_kernel(float* __restrict__ logits, long ld, int C, const float* __restrict__ target,
+                                                              long ldt, const float* __restrict__ tsum, const float* __restrict__ n_valid,
+                                                              float gscale, float* __restrict__ row_loss, float* __restrict__ logits_copy,
+                                                              long ldcopy, const float* __restrict__ dscale, vlb_u64* __restrict__ acc) {
+  soft_ce_f32_body<true>(logits, ld, C, target, ldt, tsum, n_valid, gscale, row_loss, logits_copy, ldcopy, dscale, acc);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -541,5 +650,51 @@ extern "C" int vlb_soft_ce_f32_fwd_bwd(float* logits, long ld, int rows, int C, 
   hipLaunchKernelGGL(loss_sum_f32_kernel, dim3(1), dim3(64), 0, stream, (const float*)row_loss, rows, (const float*)counts, (const float*)nullptr,
                      loss_out, (float*)nullptr);
   VLB_CHECK_LAUNCH("vlb_soft_ce_f32_fwd_bwd");
+  return VLB_OK;
+}
+
+// the *_acc forms: the same launches with the ACC kernels -- [hits, counted rows] added to an int64[2] per group; dscale nullable
+extern "C" int vlb_ce_f32_fwd_bwd_acc(float* logits, long ld, int rows, int V, const int64_t* labels, float* counts, float gscale,
+                                      const float* dscale, float* loss_out, float* row_loss, float* logits_copy, long ldcopy, int64_t* acc,
+                                      hipStream_t stream) {
+  if (rows <= 0) return VLB_OK;
+  VLB_CHECK_ARG(logits && labels && counts && loss_out && row_loss && acc, "vlb_ce_f32_fwd_bwd_acc: null argument");
+  if (ce_f32_check("vlb_ce_f32_fwd_bwd_acc", logits, ld, V, logits_copy, ldcopy) != VLB_OK) return VLB_ERR_ARG;
+  hipLaunchKernelGGL(count_labels_f32_acc_kernel, dim3(1), dim3(256), 0, stream, labels, rows, V, counts, (vlb_u64*)acc);
+  hipLaunchKernelGGL(ce_f32_acc_kernel, dim3(rows), dim3(256), 0, stream, logits, ld, V, labels, (const float*)counts, (const float*)nullptr, gscale,
+                     row_loss, logits_copy, ldcopy, dscale, (vlb_u64*)acc, (vlb_u64*)nullptr);
+  hipLaunchKernelGGL(loss_sum_f32_kernel, dim3(1), dim3(64), 0, stream, (const float*)row_loss, rows, (const float*)counts, (const float*)nullptr,
+                     loss_out, (float*)nullptr);
+  VLB_CHECK_LAUNCH("vlb_ce_f32_fwd_bwd_acc");
+  return VLB_OK;
+}
+
+extern "C" int vlb_ce_f32_fwd_bwd_compact_acc(float* logits, long ld, int rows, int V, const int64_t* labels_c, const float* count0,
+                                              const float* count1, float gscale, const float* dscale, float* loss_out0, float* loss_out1,
+                                              float* row_loss, int64_t* acc0, int64_t* acc1, hipStream_t stream) {
+  if (rows <= 0) return VLB_OK;
+  VLB_CHECK_ARG(logits && labels_c && count0 && count1 && loss_out0 && loss_out1 && row_loss && acc0 && acc1,
+                "vlb_ce_f32_fwd_bwd_compact_acc: null argument");
+  if (ce_f32_check("vlb_ce_f32_fwd_bwd_compact_acc", logits, ld, V, nullptr, 0) != VLB_OK) return VLB_ERR_ARG;
+  hipLaunchKernelGGL(ce_f32_acc_kernel, dim3(rows), dim3(256), 0, stream, logits, ld, V, labels_c, count0, count1, gscale, row_loss, (float*)nullptr,
+                     0L, dscale, (vlb_u64*)acc0, (vlb_u64*)acc1);
+  hipLaunchKernelGGL(loss_sum_f32_kernel, dim3(1), dim3(64), 0, stream, (const float*)row_loss, rows, count0, count1, loss_out0, loss_out1);
+  VLB_CHECK_LAUNCH("vlb_ce_f32_fwd_bwd_compact_acc");
+  return VLB_OK;
+}
+
+extern "C" int vlb_soft_ce_f32_fwd_bwd_acc(float* logits, long ld, int rows, int C, const float* target, long ldt, float* tsum, float* counts,
+                                           float gscale, const float* dscale, float* loss_out, float* row_loss, float* logits_copy, long ldcopy,
+                                           int64_t* acc, hipStream_t stream) {
+  if (rows <= 0) return VLB_OK;
+  VLB_CHECK_ARG(logits && target && tsum && counts && loss_out && row_loss && acc && ldt >= C, "vlb_soft_ce_f32_fwd_bwd_acc: null argument or ldt < C");
+  if (ce_f32_check("vlb_soft_ce_f32_fwd_bwd_acc", logits, ld, C, logits_copy, ldcopy) != VLB_OK) return VLB_ERR_ARG;
+  hipLaunchKernelGGL(soft_valid_f32_kernel, dim3(vlb_cdiv(rows, 4)), dim3(256), 0, stream, target, ldt, C, rows, tsum);
+  hipLaunchKernelGGL(soft_count_f32_kernel, dim3(1), dim3(256), 0, stream, (const float*)tsum, rows, counts);
+  hipLaunchKernelGGL(soft_ce_f32_acc_kernel, dim3(rows), dim3(256), 0, stream, logits, ld, C, target, ldt, (const float*)tsum, (const float*)counts,
+                     gscale, row_loss, logits_copy, ldcopy, dscale, (vlb_u64*)acc);
+  hipLaunchKernelGGL(loss_sum_f32_kernel, dim3(1), dim3(64), 0, stream, (const float*)row_loss, rows, (const float*)counts, (const float*)nullptr,
+                     loss_out, (float*)nullptr);
+  VLB_CHECK_LAUNCH("vlb_soft_ce_f32_fwd_bwd_acc");
   return VLB_OK;
 }

@@ -8,7 +8,7 @@
 // A copy of the logits is only kept when the caller asks for one (API parity / metrics).
 // n_valid is produced on the device by the count kernels -> no host synchronisation
 // (the reference does `.item()` at misc.py:140).
-#include "vlb_common.h"
+#include "arg_reduce.h"
 
 __device__ __forceinline__ void online_merge(float& m, float& s, float m2, float s2) {
   const float mn = fmaxf(m, m2);
@@ -37,6 +37,45 @@ __device__ __forceinline__ void block_online_reduce(float& m, float& s, float* s
   for (int w = 1; w < 4; ++w) online_merge(m, s, sh[w * 2], sh[w * 2 + 1]);
 }
 
+// block_online_reduce for the ACC kernels, with the roundings written out.  online_merge's s * e + s2 * e2 holds two products and the
+// build contracts one of them into the add (-ffp-contract=fast); WHICH one is the compiler's choice per inlined copy, and it chose
+// differently inside an ACC kernel than inside the plain one (the ACC forms' last butterfly step but one), which moved the last bit of
+// a row's sum-exp and with it single 16-bit gradients.  The plain kernels -- hard and soft labels, static and dynamic scale, both
+// builds -- round the thread's own product s * e in every step except the last butterfly step (o == 1), where they round the
+// partner's: this function states exactly that with __fmul_rn / fmaf, so that an ACC kernel computes the bits of its plain twin
+// whatever surrounds the reduction.  tests/test_train_metrics_gpu.py compares the two bit for bit on logits off the 1/8 grid.
+template <bool OWN>
+__device__ __forceinline__ void online_merge_as_plain(float& m, float& s, float m2, float s2) {
+  const float mn = fmaxf(m, m2);
+  if (mn == -INFINITY) return;  // both empty
+  const float e = __expf(m - mn), e2 = __expf(m2 - mn);
+  s = OWN ? fmaf(s2, e2, __fmul_rn(s, e)) : fmaf(s, e, __fmul_rn(s2, e2));
+  m = mn;
+}
+
+__device__ __forceinline__ void block_online_reduce_as_plain(float& m, float& s, float* sh) {
+#pragma unroll
+  for (int o = 32; o > 1; o >>= 1) {
+    const float m2 = __shfl_xor(m, o, 64), s2 = __shfl_xor(s, o, 64);
+    online_merge_as_plain<true>(m, s, m2, s2);
+  }
+  {
+    const float m2 = __shfl_xor(m, 1, 64), s2 = __shfl_xor(s, 1, 64);
+    online_merge_as_plain<false>(m, s, m2, s2);
+  }
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  __syncthreads();
+  if (lane == 0) {
+    sh[wave * 2] = m;
+    sh[wave * 2 + 1] = s;
+  }
+  __syncthreads();
+  m = sh[0];
+  s = sh[1];
+#pragma unroll
+  for (int w = 1; w < 4; ++w) online_merge_as_plain<true>(m, s, sh[w * 2], sh[w * 2 + 1]);
+}
+
 __device__ __forceinline__ float block_sum(float v, float* sh) {
   v = wave_sum(v);
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -54,6 +93,24 @@ __global__ void count_labels_kernel(const int64_t* __restrict__ labels, int n, f
   if ((threadIdx.x & 63) == 0 && f != 0.f) atomicAdd(counts, f);
 }
 
+// the same count for the ACC form of the one-group loss, which also adds the rows the accuracy counts -- label in [0, V), the rows
+// vlb_ce_eval counts -- to acc[1].  (counts[0] keeps every label >= 0: it is the divisor of the mean, as above.)
+__global__ void count_labels_acc_kernel(const int64_t* __restrict__ labels, int n, int V, float* __restrict__ counts, vlb_u64* __restrict__ acc) {
+  int c = 0, k = 0;
+  for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
+    const int64_t l = labels[i];
+    c += (l >= 0);
+    k += (l >= 0 && l < V);
+  }
+  float f = wave_sum((float)c);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) k += __shfl_xor(k, o, 64);
+  if ((threadIdx.x & 63) == 0) {
+    if (f != 0.f) atomicAdd(counts, f);
+    if (k) atomicAdd(acc + 1, (vlb_u64)k);
+  }
+}
+
 // One block per row.  logits: bf16 [rows, ld] (columns >= V are padding and are zeroed).
 // out: loss_sum += row_loss / n_valid ;  logits <- dlogits * (gscale / n_valid).
 // Two-group form (compacted MLM rows of the multitask wrapper): rows [0, *n_valid) belong to group 0 (mean over n_valid ->
@@ -61,18 +118,31 @@ __global__ void count_labels_kernel(const int64_t* __restrict__ labels, int n, f
 // DS (dynamic loss scale): the gradient scale is gscale * *dscale, a device value formed once per block and used exactly where gscale
 // is -- the same bits as a launch given the product from the host, and no second pass over the logits.  The static instantiation
 // never reads the trailing argument.
-template <bool DS = false>
+// ACC (training-time metrics): the per-thread online (m, s) pair also carries the column of m, merged with the tie rule of arg_reduce.h,
+// and a row whose argmax is its label adds 1 to acc[0] (acc2[0] for a row of group 1) -- an integer atomic, so the counters do not
+// depend on arrival order.  The columns meet in block_argmax (arg_reduce.h); (m, s) go through block_online_reduce_as_plain, the
+// reduction of the plain form with its roundings written out, so loss and gradient are the plain form's bits.
+// The counted rows are known before the launch: in the two-group form thread 0 of block 0 adds *n_valid / *n_valid2 to acc[1] /
+// acc2[1], before any early return (its own row may be unlabelled); in the one-group form count_labels_acc_kernel has added them.
+template <bool DS = false, bool ACC = false>
 __global__ __launch_bounds__(256) void ce_fwd_bwd_kernel(bf16_t* __restrict__ logits, long ld, int V, const int64_t* __restrict__ labels,
                                                          const float* __restrict__ n_valid, float gscale, float* __restrict__ loss_out,
                                                          bf16_t* __restrict__ logits_copy, long ldcopy,
                                                          const float* __restrict__ n_valid2 = nullptr, float* __restrict__ loss_out2 = nullptr,
-                                                         const float* __restrict__ dscale = nullptr) {
+                                                         const float* __restrict__ dscale = nullptr, vlb_u64* __restrict__ acc = nullptr,
+                                                         vlb_u64* __restrict__ acc2 = nullptr) {
   if (DS) gscale = __fmul_rn(gscale, *dscale);
   __shared__ float sh[16];
   const int row = blockIdx.x;
+  if (ACC && n_valid2 && row == 0 && threadIdx.x == 0) {
+    const vlb_u64 n0 = (vlb_u64)*n_valid, n1 = (vlb_u64)*n_valid2;
+    if (n0) atomicAdd(acc + 1, n0);
+    if (n1) atomicAdd(acc2 + 1, n1);
+  }
   if (n_valid2 && (float)row >= *n_valid) {
     n_valid = n_valid2;
     loss_out = loss_out2;
+    if (ACC) acc = acc2;
   }
   bf16_t* x = logits + (long)row * ld;
   const long label = labels[row];
@@ -89,20 +159,34 @@ __global__ __launch_bounds__(256) void ce_fwd_bwd_kernel(bf16_t* __restrict__ lo
     return;
   }
   float m = -INFINITY, s = 0.f;
+  int idx = INT_MAX;      // (ACC) column of m; a thread's columns ascend, so `>` alone keeps its lowest column among equals
   for (int c = threadIdx.x * 8; c < V; c += 2048) {
     const uint4 w = *(const uint4*)(x + c);
     const uint32_t ww[4] = {w.x, w.y, w.z, w.w};
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
       const float a = bflo(ww[k]), b = bfhi(ww[k]);
-      if (c + 2 * k < V) online_merge(m, s, a, 1.f);
-      if (c + 2 * k + 1 < V) online_merge(m, s, b, 1.f);
+      if (c + 2 * k < V) {
+        if (ACC && a > m) idx = c + 2 * k;
+        online_merge(m, s, a, 1.f);
+      }
+      if (c + 2 * k + 1 < V) {
+        if (ACC && b > m) idx = c + 2 * k + 1;
+        online_merge(m, s, b, 1.f);
+      }
     }
   }
-  block_online_reduce(m, s, sh);
+  if (ACC) {      // the thread's (maximum, its column) -> the row's, before (m, s) become the row's
+    float mv = m;
+    block_argmax(mv, idx, sh + 8);
+    block_online_reduce_as_plain(m, s, sh);
+  } else {
+    block_online_reduce(m, s, sh);
+  }
   const float lse = m + __logf(s);
   const float nv = fmaxf(*n_valid, 1.f);
   if (threadIdx.x == 0) atomicAdd(loss_out, (lse - bf2f(x[label])) / nv);
+  if (ACC && threadIdx.x == 0 && idx == (int)label) atomicAdd(acc, (vlb_u64)1);
   const float sc = gscale / nv;
   __syncthreads();  // x[label] read above before anyone overwrites it
   for (int c = threadIdx.x * 8; c < ldv; c += 2048) {
@@ -218,10 +302,22 @@ extern "C" int vlb_mlm_compact(const int64_t* labels, const int32_t* src_rows, i
 
 // CE forward + backward on COMPACTED rows: counts are given (vlb_mlm_compact wrote them), two groups with their own means.
 static int ce_fwd_bwd_compact(void* logits, long ld, int rows, int V, const int64_t* labels_c, const float* count0, const float* count1,
-                              float gscale, const float* dscale, float* loss_out0, float* loss_out1, hipStream_t stream) {
+                              float gscale, const float* dscale, float* loss_out0, float* loss_out1, hipStream_t stream,
+                              int64_t* acc0 = nullptr, int64_t* acc1 = nullptr) {
   if (rows <= 0) return VLB_OK;
   VLB_CHECK_ARG(logits && labels_c && count0 && count1 && loss_out0 && loss_out1, "vlb_ce_fwd_bwd_compact: null argument");
   VLB_CHECK_ARG(ld >= V && (ld % 8) == 0, "vlb_ce_fwd_bwd_compact: ld=%ld must be >= V=%d and a multiple of 8", ld, V);
+  if (acc0) {      // the ACC form: its own instantiations, the launches below are the ones they were
+    VLB_CHECK_ARG(acc1, "vlb_ce_fwd_bwd_compact_acc: acc1 is null");
+    if (dscale)
+      hipLaunchKernelGGL((ce_fwd_bwd_kernel<true, true>), dim3(rows), dim3(256), 0, stream, (bf16_t*)logits, ld, V, labels_c, count0, gscale,
+                         loss_out0, (bf16_t*)nullptr, 0L, count1, loss_out1, dscale, (vlb_u64*)acc0, (vlb_u64*)acc1);
+    else
+      hipLaunchKernelGGL((ce_fwd_bwd_kernel<false, true>), dim3(rows), dim3(256), 0, stream, (bf16_t*)logits, ld, V, labels_c, count0, gscale,
+                         loss_out0, (bf16_t*)nullptr, 0L, count1, loss_out1, (const float*)nullptr, (vlb_u64*)acc0, (vlb_u64*)acc1);
+    VLB_CHECK_LAUNCH("vlb_ce_fwd_bwd_compact_acc");
+    return VLB_OK;
+  }
   if (dscale)
     hipLaunchKernelGGL(ce_fwd_bwd_kernel<true>, dim3(rows), dim3(256), 0, stream, (bf16_t*)logits, ld, V, labels_c, count0, gscale, loss_out0,
                        (bf16_t*)nullptr, 0L, count1, loss_out1, dscale);
@@ -242,6 +338,13 @@ extern "C" int vlb_ce_fwd_bwd_compact_ds(void* logits, long ld, int rows, int V,
                                          const float* count1, float gscale, const float* dscale, float* loss_out0, float* loss_out1,
                                          hipStream_t stream) {
   return ce_fwd_bwd_compact(logits, ld, rows, V, labels_c, count0, count1, gscale, dscale, loss_out0, loss_out1, stream);
+}
+
+extern "C" int vlb_ce_fwd_bwd_compact_acc(void* logits, long ld, int rows, int V, const int64_t* labels_c, const float* count0,
+                                          const float* count1, float gscale, const float* dscale, float* loss_out0, float* loss_out1,
+                                          int64_t* acc0, int64_t* acc1, hipStream_t stream) {
+  VLB_CHECK_ARG(acc0 && acc1, "vlb_ce_fwd_bwd_compact_acc: null counters");
+  return ce_fwd_bwd_compact(logits, ld, rows, V, labels_c, count0, count1, gscale, dscale, loss_out0, loss_out1, stream, acc0, acc1);
 }
 
 // row validity for the soft-label loss: valid[r] = |sum_c t[r,c] - 1| < 0.1 ; counts[0] += #valid
@@ -270,14 +373,21 @@ __global__ __launch_bounds__(256) void soft_valid_kernel(const float* __restrict
 
 // One block per row.  logits bf16 [rows, ld] -> in place d(logits); target fp32 [rows, ldt].
 //   loss_row = lse * sum(t) - sum(t * x);  dlogit_c = (softmax_c * sum(t) - t_c) / n_valid
-template <bool DS = false>
+// ACC: the pass that reads x and t also takes argmax(x) and argmax(t) over [0, C) (lowest column among equals); a valid row where they
+// agree adds 1 to acc[0]; thread 0 of block 0 adds the valid rows (*n_valid, from soft_valid_kernel) to acc[1] before its early return.
+template <bool DS = false, bool ACC = false>
 __global__ __launch_bounds__(256) void soft_ce_fwd_bwd_kernel(bf16_t* __restrict__ logits, long ld, int C, const float* __restrict__ target,
                                                               long ldt, const float* __restrict__ tsum, const float* __restrict__ n_valid,
                                                               float gscale, float* __restrict__ loss_out, bf16_t* __restrict__ logits_copy,
-                                                              long ldcopy, const float* __restrict__ dscale = nullptr) {
-  __shared__ float sh[16];
+                                                              long ldcopy, const float* __restrict__ dscale = nullptr,
+                                                              vlb_u64* __restrict__ acc = nullptr) {
+  __shared__ float sh[ACC ? 28 : 16];
   if (DS) gscale = __fmul_rn(gscale, *dscale);
   const int row = blockIdx.x;
+  if (ACC && row == 0 && threadIdx.x == 0) {
+    const vlb_u64 n = (vlb_u64)*n_valid;
+    if (n) atomicAdd(acc + 1, n);
+  }
   bf16_t* x = logits + (long)row * ld;
   const float* t = target + (long)row * ldt;
   const int ldv = (int)ld;
@@ -290,13 +400,26 @@ __global__ __launch_bounds__(256) void soft_ce_fwd_bwd_kernel(bf16_t* __restrict
     for (int c = threadIdx.x; c < ldv; c += 256) x[c] = 0;
     return;
   }
-  float m = -INFINITY, s = 0.f, dot = 0.f;
+  float m = -INFINITY, s = 0.f, dot = 0.f, tm = -INFINITY;
+  int xi = INT_MAX, ti = INT_MAX;      // (ACC) ascending columns per thread: `>` keeps the lowest among equals
   for (int c = threadIdx.x; c < C; c += 256) {
-    const float v = bf2f(x[c]);
+    const float v = bf2f(x[c]), tv = t[c];
+    if (ACC) {
+      if (v > m) xi = c;
+      if (tv > tm) { tm = tv; ti = c; }
+    }
     online_merge(m, s, v, 1.f);
-    dot += t[c] * v;
+    dot += tv * v;
   }
-  block_online_reduce(m, s, sh);
+  if (ACC) {      // the threads' (maximum, its column) pairs -> the row's two argmaxes; (m, s) and dot reduce to the plain form's bits
+    float mv = m;
+    block_argmax(mv, xi, sh + 12);
+    block_argmax(tm, ti, sh + 20);
+    if (threadIdx.x == 0 && xi == ti) atomicAdd(acc, (vlb_u64)1);
+    block_online_reduce_as_plain(m, s, sh);
+  } else {
+    block_online_reduce(m, s, sh);
+  }
   dot = block_sum(dot, sh + 8);
   const float lse = m + __logf(s);
   const float nv = fmaxf(*n_valid, 1.f);
@@ -310,11 +433,24 @@ __global__ __launch_bounds__(256) void soft_ce_fwd_bwd_kernel(bf16_t* __restrict
 }
 
 static int ce_fwd_bwd(void* logits, long ld, int rows, int V, const int64_t* labels, float* counts, float gscale, const float* dscale,
-                      float* loss_out, void* logits_copy, long ldcopy, hipStream_t stream) {
+                      float* loss_out, void* logits_copy, long ldcopy, hipStream_t stream, int64_t* acc = nullptr) {
   if (rows <= 0) return VLB_OK;
   VLB_CHECK_ARG(logits && labels && counts && loss_out, "vlb_ce_fwd_bwd: null argument");
   VLB_CHECK_ARG(ld >= V && (ld % 8) == 0, "vlb_ce_fwd_bwd: ld=%ld must be >= V=%d and a multiple of 8", ld, V);
   (void)hipMemsetAsync(counts, 0, sizeof(float), stream);
+  if (acc) {      // the ACC form: its own count kernel and instantiations, the launches below are the ones they were
+    hipLaunchKernelGGL(count_labels_acc_kernel, dim3(vlb_cdiv(rows, 256) > 64 ? 64 : vlb_cdiv(rows, 256)), dim3(256), 0, stream, labels, rows, V,
+                       counts, (vlb_u64*)acc);
+    if (dscale)
+      hipLaunchKernelGGL((ce_fwd_bwd_kernel<true, true>), dim3(rows), dim3(256), 0, stream, (bf16_t*)logits, ld, V, labels, counts, gscale, loss_out,
+                         (bf16_t*)logits_copy, ldcopy, (const float*)nullptr, (float*)nullptr, dscale, (vlb_u64*)acc, (vlb_u64*)nullptr);
+    else
+      hipLaunchKernelGGL((ce_fwd_bwd_kernel<false, true>), dim3(rows), dim3(256), 0, stream, (bf16_t*)logits, ld, V, labels, counts, gscale,
+                         loss_out, (bf16_t*)logits_copy, ldcopy, (const float*)nullptr, (float*)nullptr, (const float*)nullptr, (vlb_u64*)acc,
+                         (vlb_u64*)nullptr);
+    VLB_CHECK_LAUNCH("vlb_ce_fwd_bwd_acc");
+    return VLB_OK;
+  }
   hipLaunchKernelGGL(count_labels_kernel, dim3(vlb_cdiv(rows, 256) > 64 ? 64 : vlb_cdiv(rows, 256)), dim3(256), 0, stream, labels, rows,
                      counts);
   if (dscale)
@@ -337,13 +473,30 @@ extern "C" int vlb_ce_fwd_bwd_ds(void* logits, long ld, int rows, int V, const i
   return ce_fwd_bwd(logits, ld, rows, V, labels, counts, gscale, dscale, loss_out, logits_copy, ldcopy, stream);
 }
 
+// (the *_acc forms: the fused loss + [hits, counted rows] added to an int64[2]; dscale nullable = the static scale)
+extern "C" int vlb_ce_fwd_bwd_acc(void* logits, long ld, int rows, int V, const int64_t* labels, float* counts, float gscale,
+                                  const float* dscale, float* loss_out, void* logits_copy, long ldcopy, int64_t* acc, hipStream_t stream) {
+  VLB_CHECK_ARG(acc, "vlb_ce_fwd_bwd_acc: null counters");
+  return ce_fwd_bwd(logits, ld, rows, V, labels, counts, gscale, dscale, loss_out, logits_copy, ldcopy, stream, acc);
+}
+
 static int soft_ce_fwd_bwd(void* logits, long ld, int rows, int C, const float* target, long ldt, float* tsum, float* counts, float gscale,
-                           const float* dscale, float* loss_out, void* logits_copy, long ldcopy, hipStream_t stream) {
+                           const float* dscale, float* loss_out, void* logits_copy, long ldcopy, hipStream_t stream, int64_t* acc = nullptr) {
   if (rows <= 0) return VLB_OK;
   VLB_CHECK_ARG(logits && target && tsum && counts && loss_out, "vlb_soft_ce_fwd_bwd: null argument");
   VLB_CHECK_ARG(ld >= C && ldt >= C, "vlb_soft_ce_fwd_bwd: bad leading dimensions");
   (void)hipMemsetAsync(counts, 0, sizeof(float), stream);
   hipLaunchKernelGGL(soft_valid_kernel, dim3(vlb_cdiv(rows, 4)), dim3(256), 0, stream, target, ldt, C, rows, tsum, counts);
+  if (acc) {
+    if (dscale)
+      hipLaunchKernelGGL((soft_ce_fwd_bwd_kernel<true, true>), dim3(rows), dim3(256), 0, stream, (bf16_t*)logits, ld, C, target, ldt, tsum, counts,
+                         gscale, loss_out, (bf16_t*)logits_copy, ldcopy, dscale, (vlb_u64*)acc);
+    else
+      hipLaunchKernelGGL((soft_ce_fwd_bwd_kernel<false, true>), dim3(rows), dim3(256), 0, stream, (bf16_t*)logits, ld, C, target, ldt, tsum, counts,
+                         gscale, loss_out, (bf16_t*)logits_copy, ldcopy, (const float*)nullptr, (vlb_u64*)acc);
+    VLB_CHECK_LAUNCH("vlb_soft_ce_fwd_bwd_acc");
+    return VLB_OK;
+  }
   if (dscale)
     hipLaunchKernelGGL(soft_ce_fwd_bwd_kernel<true>, dim3(rows), dim3(256), 0, stream, (bf16_t*)logits, ld, C, target, ldt, tsum, counts,
                        gscale, loss_out, (bf16_t*)logits_copy, ldcopy, dscale);
@@ -364,6 +517,13 @@ extern "C" int vlb_soft_ce_fwd_bwd_ds(void* logits, long ld, int rows, int C, co
                                       float gscale, const float* dscale, float* loss_out, void* logits_copy, long ldcopy,
                                       hipStream_t stream) {
   return soft_ce_fwd_bwd(logits, ld, rows, C, target, ldt, tsum, counts, gscale, dscale, loss_out, logits_copy, ldcopy, stream);
+}
+
+extern "C" int vlb_soft_ce_fwd_bwd_acc(void* logits, long ld, int rows, int C, const float* target, long ldt, float* tsum, float* counts,
+                                       float gscale, const float* dscale, float* loss_out, void* logits_copy, long ldcopy, int64_t* acc,
+                                       hipStream_t stream) {
+  VLB_CHECK_ARG(acc, "vlb_soft_ce_fwd_bwd_acc: null counters");
+  return soft_ce_fwd_bwd(logits, ld, rows, C, target, ldt, tsum, counts, gscale, dscale, loss_out, logits_copy, ldcopy, stream, acc);
 }
 
 // ------------------------------------------------------------------------------------------------------------------

@@ -168,8 +168,16 @@ class PretrainEngine:
     def __init__(self, cfg, B, T, R, device="cuda:0", train=True, lr=1e-4, weight_decay=1e-4, max_grad_norm=10.0,
                  betas=(0.9, 0.999), eps=1e-6, seed=1234, grad_accum=1, process_group=None, keep_logits=False, flat=None,
                  B_aux=0, core=False, core_heads=True, core_sequence=False, lr_schedule=None, warmup_steps=0, t_total=0,
-                 image_size=None, dp_mode="default", dp_wire="default", loss_scale=None, encoder_fp32=False, max_seq=256, fp32_ends=False, fp32_full=False):
+                 image_size=None, dp_mode="default", dp_wire="default", loss_scale=None, encoder_fp32=False, max_seq=256, fp32_ends=False, fp32_full=False,
+                 train_metrics=False):
         cfg.validate()
+        # train_metrics: every forward() also adds [top-1 hits, counted rows] per head to `train_metric_acc`, from the fused loss kernels
+        # themselves (the ACC forms of csrc/loss.hip / csrc/f32_pretrain.hip) -- the reference's train_metrics (common/trainer.py:84,157-158).
+        # Without it no launch changes.  Checked here, before anything is allocated
+        self.train_metrics = bool(train_metrics)
+        if self.train_metrics and core:
+            raise ValueError("train_metrics=True needs an engine that owns the loss heads: core=True (the module-API engine) computes no "
+                             "loss, so it has no training-time metrics (they belong to the wrapper that owns the labels)")
         # fp32_ends: the module-API front end (visual LayerNorms, fused embedding) and the hand-over of the sequence output run in fp32
         # too (csrc/f32_ends.hip), so that an encoder_fp32 engine holds no 16-bit tensor between its inputs and X[L].  One route only:
         # checked here, before anything is allocated
@@ -312,6 +320,9 @@ class PretrainEngine:
         self.counts = zf(4)       # n_valid mlm, n_valid mvrc, n_valid mlm aux
         # validation counters of eval_step(): [hits, counted rows] per row of METRIC_ROWS
         self.metric_acc = torch.zeros((4, 2), dtype=torch.int64, device=d)
+        # training counters of forward() (train_metrics=True), same rows; a table of their own, allocated here so that a captured step
+        # graph holds its address and validation in between (eval_step, the ValidationMonitor) keeps its own counts
+        self.train_metric_acc = torch.zeros((4, 2), dtype=torch.int64, device=d) if self.train_metrics else None
 
         # static batch buffers (graph-capturable: the host copies new batches into them)
         self.in_boxes = zf(B, R, 4 + VIS_DIM)
@@ -762,6 +773,35 @@ class PretrainEngine:
         a = self.metric_acc.cpu()
         return {k: (int(a[i, 0]), int(a[i, 1])) for i, k in enumerate(self.METRIC_ROWS)}
 
+    # ------------------------------------------------------------------------------------------
+    # training-time metrics (train_metrics=True): counters of forward(), rows as METRIC_ROWS
+    # ------------------------------------------------------------------------------------------
+    def _need_train_metrics(self, what):
+        if not self.train_metrics:
+            raise ValueError("%s: the engine was built without train_metrics=True" % what)
+
+    def reset_train_metrics(self):
+        self._need_train_metrics("reset_train_metrics")
+        self.train_metric_acc.zero_()
+
+    def train_metric_counts(self):
+        """{head: (hits, counted rows)} added by forward() since reset_train_metrics() (one host synchronisation)."""
+        self._need_train_metrics("train_metric_counts")
+        a = self.train_metric_acc.cpu()
+        return {k: (int(a[i, 0]), int(a[i, 1])) for i, k in enumerate(self.METRIC_ROWS)}
+
+    class _TrainMetricsSource(object):
+        """What common/metrics.py's classes update() from, over the TRAINING counters: metric_acc = train_metric_acc, losses = the
+        mean losses of the last forward (the reference's LossLogger reads them per batch), reset_metrics() zeroes the counters."""
+
+        def __init__(self, eng):
+            self.metric_acc, self.losses, self.reset_metrics = eng.train_metric_acc, eng.losses, eng.reset_train_metrics
+
+    @property
+    def train_metrics_source(self):
+        self._need_train_metrics("train_metrics_source")
+        return self._TrainMetricsSource(self)
+
     def _front_core_fwd(self, p_h):
         """VisualLinguisticBert.embedding (common/visual_linguistic_bert.py:173-241) on caller-provided embeddings."""
         cfg, T, R, S, Bt = self.cfg, self.T, self.R, self.S, self.Bt
@@ -905,22 +945,26 @@ class PretrainEngine:
             losses, mcopy, vcopy = torch.zeros_like(self.losses), None, None
         nw = B * T     # rows of the image-caption samples; the aux rows follow and get their own mean (multitask.py:224-246)
         ds = self.scaler.scale if self.scaler is not None else None      # dynamic loss scale: multiplied into gscale on the device
+        # train_metrics: the launches below become their ACC forms and add [hits, counted rows] to a row of train_metric_acc
+        # (METRIC_ROWS) -- on the keep=True pass only, so that the mirror's re-run counts nothing twice
+        tm = self.train_metric_acc if keep else None
+        acc = (lambda *rows: dict(zip(("acc", "acc1"), (tm[r] for r in rows)))) if tm is not None else (lambda *rows: {})
         if self._mlm_compact_now:      # labelled rows only: caption rows first, then the aux rows, each group with its own mean
             ops.ce_fwd_bwd_compact(self.mlm_logits[:self.mlm_cap], V, self.labels_c, self.counts[0:1], self.counts[2:3], losses[0:1],
-                                   losses[2:3], gscale=gscale, dscale=ds)
+                                   losses[2:3], gscale=gscale, dscale=ds, **acc(0, 1))
         else:
             ops.ce_fwd_bwd(self.mlm_logits[:nw], V, self.in_mlm_labels.view(-1)[:nw], self.counts[0:1], losses[0:1], gscale=gscale,
-                           logits_copy=mcopy[:nw] if mcopy is not None else None, dscale=ds)
+                           logits_copy=mcopy[:nw] if mcopy is not None else None, dscale=ds, **acc(0))
             if Ba:
                 ops.ce_fwd_bwd(self.mlm_logits[nw:], V, self.in_mlm_labels.view(-1)[nw:], self.counts[2:3], losses[2:3],
-                               gscale=gscale, logits_copy=mcopy[nw:] if mcopy is not None else None, dscale=ds)
+                               gscale=gscale, logits_copy=mcopy[nw:] if mcopy is not None else None, dscale=ds, **acc(1))
         ops.soft_ce_fwd_bwd(self.mvrc_logits, C, self.in_mvrc_labels.view(self.BR, C), self.mvrc_tsum, self.counts[1:2],
-                            losses[1:2], gscale=gscale, logits_copy=vcopy, dscale=ds)
+                            losses[1:2], gscale=gscale, logits_copy=vcopy, dscale=ds, **acc(2))
         if self.cfg.with_rel_loss:     # F.cross_entropy(relationship_logits, relationship_label) (resnet_vlbert_for_pretraining.py:160-161)
             if not keep:
                 self.rel_logits.copy_(self.rel_logits_copy)
             ops.ce_fwd_bwd(self.rel_logits, 2, self.in_rel_label, self.counts[3:4], losses[3:4], gscale=gscale,
-                           logits_copy=self.rel_logits_copy if keep else None, dscale=ds)
+                           logits_copy=self.rel_logits_copy if keep else None, dscale=ds, **acc(3))
 
     # ------------------------------------------------------------------------------------------
     # backward (explicit; weight gradients are ACCUMULATED into the flat fp32 grad buffer)

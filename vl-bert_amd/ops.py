@@ -397,9 +397,15 @@ def mul_bf16(a, b, out):
     return out
 
 
-def ce_fwd_bwd(logits, V, labels, counts, loss_out, gscale=1.0, logits_copy=None, dscale=None):
-    """dscale (fp32 device scalar, e.g. the scale slot of a loss scaler): the gradient scale is gscale * dscale, formed on the device."""
+def ce_fwd_bwd(logits, V, labels, counts, loss_out, gscale=1.0, logits_copy=None, dscale=None, acc=None):
+    """dscale (fp32 device scalar, e.g. the scale slot of a loss scaler): the gradient scale is gscale * dscale, formed on the device.
+    acc (int64 [2], training-time metrics): += [rows whose argmax is the label, rows with a label in [0, V)] (vlb_ce_fwd_bwd_acc)."""
     rows = logits.shape[0]
+    if acc is not None:
+        _lib.call("vlb_ce_fwd_bwd_acc", _p(logits, BF16), _ld(logits), rows, V, _p(labels, torch.int64), _p(counts, torch.float32),
+                  float(gscale), _p(dscale, torch.float32), _p(loss_out, torch.float32), _p(logits_copy, BF16), _ld(logits_copy),
+                  _p(acc, torch.int64), _stream())
+        return
     if dscale is not None:
         _lib.call("vlb_ce_fwd_bwd_ds", _p(logits, BF16), _ld(logits), rows, V, _p(labels, torch.int64), _p(counts, torch.float32),
                   float(gscale), _p(dscale, torch.float32), _p(loss_out, torch.float32), _p(logits_copy, BF16), _ld(logits_copy), _stream())
@@ -415,7 +421,15 @@ def mlm_compact(labels, src_rows, n_split, V, sel_pos, sel_src, labels_c, count0
               _p(count1, torch.float32), _p(overflow, torch.int32), _stream())
 
 
-def ce_fwd_bwd_compact(logits, V, labels_c, count0, count1, loss_out0, loss_out1, gscale=1.0, dscale=None):
+def ce_fwd_bwd_compact(logits, V, labels_c, count0, count1, loss_out0, loss_out1, gscale=1.0, dscale=None, acc=None, acc1=None):
+    """acc / acc1 (int64 [2] each, both or neither): += [hits, counted rows] of group 0 / group 1 (vlb_ce_fwd_bwd_compact_acc)."""
+    if acc is not None or acc1 is not None:
+        if acc is None or acc1 is None:
+            raise ValueError("ce_fwd_bwd_compact: acc and acc1 go together (one counter pair per group)")
+        _lib.call("vlb_ce_fwd_bwd_compact_acc", _p(logits, BF16), _ld(logits), logits.shape[0], V, _p(labels_c, torch.int64),
+                  _p(count0, torch.float32), _p(count1, torch.float32), float(gscale), _p(dscale, torch.float32),
+                  _p(loss_out0, torch.float32), _p(loss_out1, torch.float32), _p(acc, torch.int64), _p(acc1, torch.int64), _stream())
+        return
     if dscale is not None:
         _lib.call("vlb_ce_fwd_bwd_compact_ds", _p(logits, BF16), _ld(logits), logits.shape[0], V, _p(labels_c, torch.int64),
                   _p(count0, torch.float32), _p(count1, torch.float32), float(gscale), _p(dscale, torch.float32),
@@ -431,8 +445,14 @@ def scatter_rows(src, idx, out):
     return out
 
 
-def soft_ce_fwd_bwd(logits, C, target, tsum, counts, loss_out, gscale=1.0, logits_copy=None, dscale=None):
+def soft_ce_fwd_bwd(logits, C, target, tsum, counts, loss_out, gscale=1.0, logits_copy=None, dscale=None, acc=None):
+    """acc (int64 [2]): += [valid rows with argmax(logits) == argmax(target), valid rows] (vlb_soft_ce_fwd_bwd_acc)."""
     rows = logits.shape[0]
+    if acc is not None:
+        _lib.call("vlb_soft_ce_fwd_bwd_acc", _p(logits, BF16), _ld(logits), rows, C, _p(target, torch.float32), _ld(target),
+                  _p(tsum, torch.float32), _p(counts, torch.float32), float(gscale), _p(dscale, torch.float32),
+                  _p(loss_out, torch.float32), _p(logits_copy, BF16), _ld(logits_copy), _p(acc, torch.int64), _stream())
+        return
     if dscale is not None:
         _lib.call("vlb_soft_ce_fwd_bwd_ds", _p(logits, BF16), _ld(logits), rows, C, _p(target, torch.float32), _ld(target),
                   _p(tsum, torch.float32), _p(counts, torch.float32), float(gscale), _p(dscale, torch.float32),
@@ -1068,21 +1088,41 @@ def _row_loss(logits, row_loss):
     return row_loss
 
 
-def ce_f32_fwd_bwd(logits, V, labels, counts, loss_out, gscale=1.0, logits_copy=None, row_loss=None):
+def ce_f32_fwd_bwd(logits, V, labels, counts, loss_out, gscale=1.0, logits_copy=None, row_loss=None, acc=None, dscale=None):
     """ce_fwd_bwd on fp32 logits [rows, ld % 4 == 0]; the rows' losses go through `row_loss` (scratch, allocated when not given) and
-    are added in a fixed order: the same bits on every run."""
+    are added in a fixed order: the same bits on every run.  acc (int64 [2]): += [hits, counted rows] (the *_acc entry points, which
+    also take a device scale `dscale`)."""
     row_loss = _row_loss(logits, row_loss)
+    if acc is not None:
+        _lib.call("vlb_ce_f32_fwd_bwd_acc", _pf(logits), _ld(logits), logits.shape[0], V, _p(labels, torch.int64), _pf(counts), float(gscale),
+                  _pf(dscale), _pf(loss_out), _pf(row_loss), _pf(logits_copy), _ld(logits_copy), _p(acc, torch.int64), _stream())
+        return
+    assert dscale is None, "ce_f32_fwd_bwd: dscale comes with acc (vlb_ce_f32_fwd_bwd_acc)"
     _lib.call("vlb_ce_f32_fwd_bwd", _pf(logits), _ld(logits), logits.shape[0], V, _p(labels, torch.int64), _pf(counts), float(gscale),
               _pf(loss_out), _pf(row_loss), _pf(logits_copy), _ld(logits_copy), _stream())
 
 
-def ce_f32_fwd_bwd_compact(logits, V, labels_c, count0, count1, loss_out0, loss_out1, gscale=1.0, row_loss=None):
+def ce_f32_fwd_bwd_compact(logits, V, labels_c, count0, count1, loss_out0, loss_out1, gscale=1.0, row_loss=None, acc=None, acc1=None,
+                           dscale=None):
     row_loss = _row_loss(logits, row_loss)
+    if acc is not None or acc1 is not None:
+        if acc is None or acc1 is None:
+            raise ValueError("ce_f32_fwd_bwd_compact: acc and acc1 go together (one counter pair per group)")
+        _lib.call("vlb_ce_f32_fwd_bwd_compact_acc", _pf(logits), _ld(logits), logits.shape[0], V, _p(labels_c, torch.int64), _pf(count0),
+                  _pf(count1), float(gscale), _pf(dscale), _pf(loss_out0), _pf(loss_out1), _pf(row_loss), _p(acc, torch.int64),
+                  _p(acc1, torch.int64), _stream())
+        return
+    assert dscale is None, "ce_f32_fwd_bwd_compact: dscale comes with acc / acc1"
     _lib.call("vlb_ce_f32_fwd_bwd_compact", _pf(logits), _ld(logits), logits.shape[0], V, _p(labels_c, torch.int64), _pf(count0),
               _pf(count1), float(gscale), _pf(loss_out0), _pf(loss_out1), _pf(row_loss), _stream())
 
 
-def soft_ce_f32_fwd_bwd(logits, C, target, tsum, counts, loss_out, gscale=1.0, logits_copy=None, row_loss=None):
+def soft_ce_f32_fwd_bwd(logits, C, target, tsum, counts, loss_out, gscale=1.0, logits_copy=None, row_loss=None, acc=None, dscale=None):
     row_loss = _row_loss(logits, row_loss)
+    if acc is not None:
+        _lib.call("vlb_soft_ce_f32_fwd_bwd_acc", _pf(logits), _ld(logits), logits.shape[0], C, _pf(target), _ld(target), _pf(tsum), _pf(counts),
+                  float(gscale), _pf(dscale), _pf(loss_out), _pf(row_loss), _pf(logits_copy), _ld(logits_copy), _p(acc, torch.int64), _stream())
+        return
+    assert dscale is None, "soft_ce_f32_fwd_bwd: dscale comes with acc"
     _lib.call("vlb_soft_ce_f32_fwd_bwd", _pf(logits), _ld(logits), logits.shape[0], C, _pf(target), _ld(target), _pf(tsum), _pf(counts),
               float(gscale), _pf(loss_out), _pf(row_loss), _pf(logits_copy), _ld(logits_copy), _stream())

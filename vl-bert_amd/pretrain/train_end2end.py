@@ -1,7 +1,7 @@
 """Entry point with the reference's command line (pretrain/train_end2end.py:11-48) over the HIP engine:
 
     python -m vl-bert_amd.pretrain.train_end2end --cfg cfgs/pretrain/base_prec_withouttextonly_4x16G_fp32.yaml [--dist]
-           [--steps N] [--steps-per-epoch M] [--batch-images B] [--data] [--val-steps N] [--dry-run]
+           [--steps N] [--steps-per-epoch M] [--batch-images B] [--data] [--val-steps N] [--train-metrics] [--dry-run]
 
 It reads the reference's YAML files as they are (the keys of pretrain/function/config.py that the hot path consumes: NETWORK.*,
 TRAIN.{BATCH_IMAGES, LR, WD, CLIP_GRAD_NORM, LR_SCHEDULE, WARMUP, WARMUP_STEPS, END_EPOCH, BEGIN_EPOCH, GRAD_ACCUMULATE_STEPS},
@@ -17,7 +17,9 @@ with --data they come from the data sets the YAML names, read by vl-bert_amd/pre
 corpus formats, its sampling and collation).  Validation: at every epoch end the reference's ValidationMonitor
 (pretrain/function/train.py:244-281) runs PretrainEngine.eval_step() over the validation set(s) the YAML names (--data; DATASET.VAL_IMAGE_SET /
 VAL_ANNOTATION_FILE) or over --val-steps synthetic batches with fixed seeds, prints `Epoch[k] \tVal-MLMAcc=...` and tracks the best epoch
-(vl-bert_amd/common/metrics.py).  There is no CPU execution path: without a GPU
+(vl-bert_amd/common/metrics.py).  Training metrics: with --train-metrics the fused loss kernels also count top-1 hits on every training
+batch (PretrainEngine(train_metrics=True)) and the reference's Speedometer line `Epoch[e] Batch [n]\tSpeed: ...\tTrain-MLMAcc=...` follows
+every `step N ...` line.  There is no CPU execution path: without a GPU
 the program stops with an error unless --dry-run is given, which only resolves and prints the configuration (the "plumbing"
 check of the reference's scripts/nondist_run.sh case).
 """
@@ -182,6 +184,14 @@ def parse_args(argv=None):
                          "len(loader) unless --steps-per-epoch is given; the engine's text / box capacities default to DATASET.SEQ_LEN")
     ap.add_argument("--val-steps", type=int, default=0, help="without --data: validate at every epoch end on this many synthetic batches with "
                     "fixed seeds (0 = no validation)")
+    ap.add_argument("--train-metrics", action="store_true",
+                    help="the reference's train_metrics (common/trainer.py:84,157-158; pretrain/function/train.py:247-266): top-1 hits of "
+                         "every training batch, counted by the fused loss kernels themselves, and the per-batch mean losses.  Every "
+                         "LOG_FREQUENT steps, after the `step N ...` line, rank 0 prints the Speedometer's `Epoch[e] Batch [n]\\tSpeed: x "
+                         "samples/s\\tTrain-<name>=<value>,\\t...` with the reference's names in its order (a LossLogger of a loss that is "
+                         "switched off -- RelLoss without NETWORK.WITH_REL_LOSS -- is left out); the metrics reset at every epoch start.  The "
+                         "Speedometer's ETA field and its per-phase times (Data / Tran / F / B / O / M) are left out: one captured step "
+                         "has no host-visible phases")
     ap.add_argument("--dry-run", action="store_true", help="resolve and print the configuration, touch no GPU")
     return ap.parse_args(argv)
 
@@ -232,6 +242,8 @@ def main(argv=None):
     if r["compute"] == "fp32-full" and (args.val_steps > 0 or val_loader is not None):
         raise ValueError("--compute fp32-full: validation (--val-steps, or a validation set named by the YAML) is not built in fp32 -- the "
                          "validation kernels read 16-bit logits; validate with --compute fp32")
+    if args.train_metrics:      # (reported only when asked for: without the flag the resolved dict is what it was)
+        r["train_metrics"] = True
     if args.dry_run:
         if rank == 0:
             print(json.dumps({"resolved": r, "NETWORK.VLBERT": dict(config.NETWORK.VLBERT)}, indent=1, default=str))
@@ -273,7 +285,8 @@ def main(argv=None):
                                 image_size=r["image_size"] if r["e2e"] else None, grad_accum=r["accumulate"],
                                 encoder_fp32=r["compute"] in ("fp32", "fp32-full"), fp32_full=fp32_full,
                                 dp_mode="allreduce" if r["compute"] in ("fp32", "fp32-full") else "default",
-                                loss_scale=r["loss_scale"] if r["compute"] == "fp16" else None, max_seq=engine.MAX_SEQ)
+                                loss_scale=r["loss_scale"] if r["compute"] == "fp16" else None, max_seq=engine.MAX_SEQ,
+                                **(dict(train_metrics=True) if args.train_metrics else {}))
     eng.init_random(seed=r["seed"], visual_ln_init=float(g("visual_scale_object_init", 0.0)))
     # NETWORK.PARTIAL_PRETRAIN (+ _PREFIX_CHANGES): start from a pre-trained checkpoint's matching tensors (pretrain/function/train.py:297-313,
     # common/utils/load.py:57-81).  Empty in every shipped pre-training YAML; a configured file that does not exist is reported and skipped
@@ -387,16 +400,38 @@ def main(argv=None):
         monitor = met.ValidationMonitor(met.do_validation, val_items, metrics, host_metric_name=met.host_metric_name(r["multitask"]),
                                         load_batch=put, verbose=rank == 0)
     eng.validation_monitor = monitor
+    # training metrics (pretrain/function/train.py:247-266 + the Speedometer): the list of the validation branch over the engine's
+    # TRAINING counters; a LossLogger of a head that is switched off is left out of the line
+    train_metrics = None
+    if args.train_metrics:
+        met = importlib.import_module(pkg + ".common.metrics")
+        loggers = met.parse_loss_loggers(config.TRAIN.get("LOSS_LOGGERS", None)) or met.DEFAULT_LOSS_LOGGERS
+        off = {"relationship_loss": not config.NETWORK.WITH_REL_LOSS, "mlm_loss": not config.NETWORK.WITH_MLM_LOSS,
+               "mlm_loss_wvc": not config.NETWORK.WITH_MLM_LOSS, "mlm_loss_aux": not config.NETWORK.WITH_MLM_LOSS,
+               "mvrc_loss": not config.NETWORK.WITH_MVRC_LOSS}
+        train_metrics = met.pretrain_metrics(with_rel_loss=bool(config.NETWORK.WITH_REL_LOSS), with_mlm_loss=bool(config.NETWORK.WITH_MLM_LOSS),
+                                             with_mvrc_loss=bool(config.NETWORK.WITH_MVRC_LOSS), multitask=r["multitask"],
+                                             loss_loggers=[l for l in loggers if not off.get(l[0], False)],
+                                             allreduce=world > 1, num_replicas=world)
+        eng.reset_train_metrics()
+    eng.train_metrics_monitor = train_metrics
+    tic, tic_seen = time.time(), 0
     accum = r["accumulate"]
     for step in range(first_step, first_step + args.steps):
+        if train_metrics is not None and step % spe == 0:      # common/trainer.py:84: reset at every epoch start
+            train_metrics.reset()
         if accum == 1:
             load_batch(step)
             eng.train_step()
+            if train_metrics is not None:
+                train_metrics.update(eng.train_metrics_source)
         else:      # common/trainer.py:117-153: loss / accumulate per micro-batch, exchange + optimizer on the boundary micro-step
             eng.zero_grad()
             for micro in range(accum):
                 load_batch(step * accum + micro)
                 eng.forward(True, gscale=1.0 / accum)
+                if train_metrics is not None:      # once per micro-batch (common/trainer.py:157-158)
+                    train_metrics.update(eng.train_metrics_source)
                 last = micro == accum - 1
                 eng.backward(True, on_layer_done=eng.buckets.on_done if (last and eng.buckets is not None) else None)
                 if not last:
@@ -418,6 +453,14 @@ def main(argv=None):
                 print("step %d  lr %.3e  loss %.4f (mlm %.4f mvrc %.4f)  %.1f samples/s%s" %
                       (step + 1, float(eng.adam[0]), lv["loss"], lv["mlm_loss"], lv["mvrc_loss"], seen / (time.time() - t0),
                        "  loss scale %g (%d skipped)" % (ss["scale"], ss["skipped_total"]) if ss is not None else ""), flush=True)
+            if train_metrics is not None:
+                names, values = train_metrics.get()      # (every rank: an all-reduce under --dist)
+                now = time.time()
+                if rank == 0:
+                    print("Epoch[%d] Batch [%d]\tSpeed: %.2f samples/s\t" % (step // spe, (step % spe + 1) * accum,
+                                                                            (seen - tic_seen) / max(now - tic, 1e-9)) +
+                          "".join("Train-%s=%f,\t" % (n, v) for n, v in zip(names, values)), flush=True)
+                tic, tic_seen = now, seen
         if monitor is not None and (step + 1) % spe == 0:      # after the step's log line: validation overwrites the loss slots
             monitor((step + 1) // spe - 1, eng)
             eng.loss_values()               # (raises if a validation batch overflowed the MLM compaction capacity)

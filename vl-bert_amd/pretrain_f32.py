@@ -142,14 +142,18 @@ class PretrainF32:
             e.mvrc_logits.copy_(e.mvrc_logits_copy)
             losses, mcopy, vcopy = torch.zeros_like(e.losses), None, None
         compact, nr = self._mlm_rows()
+        # train_metrics: the ACC forms add [hits, counted rows] to rows 0 (MLM; row 1 takes the empty second group) and 2 (MVRC) of
+        # train_metric_acc, on the keep=True pass only (engine._losses_fwd_bwd)
+        tm = e.train_metric_acc if keep else None
+        acc = (lambda *rows: dict(zip(("acc", "acc1"), (tm[r] for r in rows)))) if tm is not None else (lambda *rows: {})
         if compact:
             ops.ce_f32_fwd_bwd_compact(e.mlm_logits[:nr], V, e.labels_c, e.counts[0:1], e.counts[2:3], losses[0:1], losses[2:3], gscale=gscale,
-                                       row_loss=self.row_loss)
+                                       row_loss=self.row_loss, **acc(0, 1))
         else:
             ops.ce_f32_fwd_bwd(e.mlm_logits, V, e.in_mlm_labels.view(-1), e.counts[0:1], losses[0:1], gscale=gscale, logits_copy=mcopy,
-                               row_loss=self.row_loss)
+                               row_loss=self.row_loss, **acc(0))
         ops.soft_ce_f32_fwd_bwd(e.mvrc_logits, C, e.in_mvrc_labels.view(e.BR, C), e.mvrc_tsum, e.counts[1:2], losses[1:2], gscale=gscale,
-                                logits_copy=vcopy, row_loss=self.row_loss)
+                                logits_copy=vcopy, row_loss=self.row_loss, **acc(2))
 
     # -- backward -----------------------------------------------------------------------------------------------------
     def heads_bwd(self):
