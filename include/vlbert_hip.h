@@ -33,6 +33,8 @@ extern "C" {
 typedef struct ihipStream_t* vlb_stream_t; /* == hipStream_t */
 
 const char* vlb_last_error(void);
+/* 200 = 0.2.0: the fused losses and optimizer steps take their optional features (dscale, acc, scaler, g_is_bf16) as arguments of one
+ * entry point each; arguments were inserted under names that 0.1.0 already had, so a caller checks the version it was built for */
 int vlb_version(void);
 /* 16-bit storage type of this build: 0 = bfloat16 (libvlbert_hip.so, the default), 1 = IEEE fp16 (libvlbert_hip_f16.so: every
  * "bf16" in the names below then means fp16 -- the reference's own mixed precision, Apex O2 with a static loss scale,
@@ -213,12 +215,14 @@ int vlb_scatter_rows(const void* src, const int32_t* idx, void* out, int n, int 
  * d(logits) rows, so the head runs on the labelled rows only.  vlb_mlm_compact lists them (stable order): sel_pos[k] = position in
  * [0, n), sel_src[k] = src_rows[position], labels_c[k] = label (all -1 beyond the count), count0 / count1 = labelled rows among
  * positions < n_split / >= n_split; *overflow is set when more than `cap` rows carry a label (the excess is dropped: an error for
- * the caller).  vlb_ce_fwd_bwd_compact = vlb_ce_fwd_bwd on such rows with the two group means (loss_out0 over count0 rows, then
- * loss_out1 over count1 rows). */
+ * the caller).  vlb_ce_fwd_bwd_compact = vlb_ce_fwd_bwd (below, with its nullable dscale / acc) on such rows with the two group
+ * means (loss_out0 over count0 rows, then loss_out1 over count1 rows); group 0 counts into acc0 and group 1 into acc1, which are
+ * both given or both NULL. */
 int vlb_mlm_compact(const int64_t* labels, const int32_t* src_rows, int n, int n_split, int V, int cap, int32_t* sel_pos,
                     int32_t* sel_src, int64_t* labels_c, float* count0, float* count1, int32_t* overflow, vlb_stream_t stream);
 int vlb_ce_fwd_bwd_compact(void* logits, long ld, int rows, int V, const int64_t* labels_c, const float* count0, const float* count1,
-                           float gscale, float* loss_out0, float* loss_out1, vlb_stream_t stream);
+                           float gscale, const float* dscale, float* loss_out0, float* loss_out1, int64_t* acc0, int64_t* acc1,
+                           vlb_stream_t stream);
 /* inverse of the split: dX[b,s] = (s<T ? d_text[b,s] : 0) + (row is object j ? d_obj[b,j] : 0) */
 int vlb_head_grad_combine(const void* d_text, const void* d_obj, const int32_t* code, void* dx, int B, int T, int R,
                           int S, int H, vlb_stream_t stream);
@@ -236,12 +240,19 @@ int vlb_tanh_bwd(const void* dy, const void* y, void* out, long n, vlb_stream_t 
  * MLM: F.cross_entropy(ignore_index=-1) (resnet_vlbert_for_pretraining.py:176-178).
  * MVRC: soft_cross_entropy (common/utils/misc.py:124-151).  `counts` = 1 device float (n_valid),
  * `loss_out` is accumulated (+=).  gscale multiplies the gradient (1/grad-accumulation steps).
- * logits_copy (optional) receives the untouched logits for API parity / metrics. */
-int vlb_ce_fwd_bwd(void* logits, long ld, int rows, int V, const int64_t* labels, float* counts, float gscale,
-                   float* loss_out, void* logits_copy, long ldcopy, vlb_stream_t stream);
-int vlb_soft_ce_fwd_bwd(void* logits, long ld, int rows, int C, const float* target, long ldt, float* tsum,
-                        float* counts, float gscale, float* loss_out, void* logits_copy, long ldcopy,
-                        vlb_stream_t stream);
+ * logits_copy (optional) receives the untouched logits for API parity / metrics.
+ * dscale (nullable; DEVICE float, e.g. &scaler[0] of the dynamic loss scale below): the gradient scale is gscale * *dscale, the product
+ *   formed once per block and used where gscale is, so a launch at *dscale = S gives the bits of a launch given gscale * S and NULL.
+ * acc (nullable; training-time metrics) = int64 [2], ACCUMULATED: acc[0] += counted rows whose argmax is the label (soft labels:
+ *   argmax(logits) == argmax(target) over [0, C)), acc[1] += counted rows, with the rules of vlb_ce_eval / vlb_soft_ce_eval (label in
+ *   [0, V); |sum(target) - 1| < 0.1; a tie goes to the lowest column; pad columns take no part).  The argmax rides in the pass that
+ *   already reads the row; loss, gradient, zeroed pad columns and logits_copy are those of the call with acc == NULL.  Integer
+ *   atomics only: the same inputs give the same counters on every run.
+ * The fp32 forms (vlb_ce_f32_fwd_bwd ..., below) take the same two arguments. */
+int vlb_ce_fwd_bwd(void* logits, long ld, int rows, int V, const int64_t* labels, float* counts, float gscale, const float* dscale,
+                   float* loss_out, void* logits_copy, long ldcopy, int64_t* acc, vlb_stream_t stream);
+int vlb_soft_ce_fwd_bwd(void* logits, long ld, int rows, int C, const float* target, long ldt, float* tsum, float* counts, float gscale,
+                        const float* dscale, float* loss_out, void* logits_copy, long ldcopy, int64_t* acc, vlb_stream_t stream);
 
 /* ---- validation: forward-only loss value + top-1 accuracy, the logits are only READ (one pass per row) -------------
  * The metrics of common/metrics/pretrain_metrics.py:20-85 without copying the logits out: MLMAccuracy / MLMAccuracyWVC /
@@ -260,30 +271,6 @@ int vlb_ce_eval(const void* logits, long ld, int rows, int V, const int64_t* lab
                 float* loss_out0, float* loss_out1, int64_t* acc0, int64_t* acc1, int32_t* pred, vlb_stream_t stream);
 int vlb_soft_ce_eval(const void* logits, long ld, int rows, int C, const float* target, long ldt, float* loss_out, int64_t* acc,
                      vlb_stream_t stream);
-
-/* ---- training-time metrics: the fused forward + backward losses that also count top-1 hits -------------------------
- * vlb_ce_fwd_bwd / vlb_ce_fwd_bwd_compact / vlb_soft_ce_fwd_bwd (and the fp32 forms below) with two additions.  dscale (nullable): the
- * gradient scale is gscale * *dscale as in the *_ds forms, NULL = the static scale.  acc = int64 [2], ACCUMULATED: acc[0] += counted rows
- * whose argmax is the label (soft labels: argmax(logits) == argmax(target) over [0, C)), acc[1] += counted rows, with the rules of
- * vlb_ce_eval / vlb_soft_ce_eval (label in [0, V); |sum(target) - 1| < 0.1; a tie goes to the lowest column; pad columns take no
- * part).  The argmax rides in the pass that already reads the row; loss, gradient, zeroed pad columns and logits_copy are those of
- * the plain entry points.  Integer atomics only: the same inputs give the same counters on every run.  The two-group form counts
- * group 0 into acc0 and group 1 into acc1. */
-int vlb_ce_fwd_bwd_acc(void* logits, long ld, int rows, int V, const int64_t* labels, float* counts, float gscale, const float* dscale,
-                       float* loss_out, void* logits_copy, long ldcopy, int64_t* acc, vlb_stream_t stream);
-int vlb_ce_fwd_bwd_compact_acc(void* logits, long ld, int rows, int V, const int64_t* labels_c, const float* count0, const float* count1,
-                               float gscale, const float* dscale, float* loss_out0, float* loss_out1, int64_t* acc0, int64_t* acc1,
-                               vlb_stream_t stream);
-int vlb_soft_ce_fwd_bwd_acc(void* logits, long ld, int rows, int C, const float* target, long ldt, float* tsum, float* counts, float gscale,
-                            const float* dscale, float* loss_out, void* logits_copy, long ldcopy, int64_t* acc, vlb_stream_t stream);
-int vlb_ce_f32_fwd_bwd_acc(float* logits, long ld, int rows, int V, const int64_t* labels, float* counts, float gscale, const float* dscale,
-                           float* loss_out, float* row_loss, float* logits_copy, long ldcopy, int64_t* acc, vlb_stream_t stream);
-int vlb_ce_f32_fwd_bwd_compact_acc(float* logits, long ld, int rows, int V, const int64_t* labels_c, const float* count0, const float* count1,
-                                   float gscale, const float* dscale, float* loss_out0, float* loss_out1, float* row_loss, int64_t* acc0,
-                                   int64_t* acc1, vlb_stream_t stream);
-int vlb_soft_ce_f32_fwd_bwd_acc(float* logits, long ld, int rows, int C, const float* target, long ldt, float* tsum, float* counts,
-                                float gscale, const float* dscale, float* loss_out, float* row_loss, float* logits_copy, long ldcopy,
-                                int64_t* acc, vlb_stream_t stream);
 
 /* ---- fine-tuning evaluation (csrc/finetune_metrics.hip): the metrics of common/metrics/{vqa,vcr,refcoco}_metrics.py and the
  * predictions of the test-set writers on the device.  All three read fp32 data only, synchronise nothing, allocate nothing and
@@ -313,9 +300,10 @@ int vlb_joint_hits(const int32_t* pred_a, const int64_t* label_a, const int32_t*
 /* VQA answer loss (vqa/modules/resnet_vlbert_for_vqa.py:226): binary_cross_entropy_with_logits(logits[rows,A], label) * A =
  * (1/rows) sum of the element losses; logits (bf16, row stride ld, columns >= A zeroed) are overwritten IN PLACE by
  * gscale * d(loss)/d(logits) = gscale * w * (sigmoid(x) - y) / rows; loss_out is accumulated (+=); logits_copy (optional) keeps the logits.
- * w = pos_weight where y > 0.5, else 1: the element `weight` of the VCR answer loss (vcr/modules/resnet_vlbert_for_vcr.py:333-341; 1 = VQA). */
-int vlb_bce_logits_fwd_bwd(void* logits, long ld, int rows, int A, const float* label, long ldl, float gscale, float pos_weight,
-                           float* loss_out, void* logits_copy, long ldcopy, vlb_stream_t stream);
+ * w = pos_weight where y > 0.5, else 1: the element `weight` of the VCR answer loss (vcr/modules/resnet_vlbert_for_vcr.py:333-341; 1 = VQA).
+ * dscale (nullable): gscale * *dscale, as for vlb_ce_fwd_bwd. */
+int vlb_bce_logits_fwd_bwd(void* logits, long ld, int rows, int A, const float* label, long ldl, float gscale, const float* dscale,
+                           float pos_weight, float* loss_out, void* logits_copy, long ldcopy, vlb_stream_t stream);
 /* y[i] = x[i] * keep(seed, tag, i) / (1 - p): elementwise dropout with the library's counter RNG (the classifier dropouts of the
  * VQA head, resnet_vlbert_for_vqa.py:57-77); the same call on the gradient is its backward. */
 int vlb_dropout_bf16(const void* x, void* y, long n, float drop_p, const uint32_t* seed, uint32_t tag, vlb_stream_t stream);
@@ -364,15 +352,14 @@ int vlb_copy_ranges_f32(const float* src, float* dst, const int64_t* ranges, con
 
 int vlb_sumsq_f32(const float* g, long n, float* out, vlb_stream_t stream);
 /* same sum with a fixed summation order (per-block partials in `partials[partials_len]`, then one block): bit-identical on every
- * data-parallel rank for identical gradients, so the clip coefficient -- and therefore the replicas' parameters -- cannot drift. */
-int vlb_sumsq_f32_det(const float* g, long n, float* partials, int partials_len, float* out, vlb_stream_t stream);
-int vlb_adamw_step(float* p, const float* g, float* m, float* v, void* p_bf16, long n, float* state, float grad_scale,
-                   vlb_stream_t stream);
-/* the same two steps on a bf16 gradient image: the wire format of the data-parallel exchange (DDP all-reduce of
- * pretrain/function/train.py:89-90 carried out in bf16 over RCCL); the reduced gradient is consumed as it arrived. */
-int vlb_sumsq_bf16_det(const void* g_bf16, long n, float* partials, int partials_len, float* out, vlb_stream_t stream);
-int vlb_adamw_step_gbf16(float* p, const void* g_bf16, float* m, float* v, void* p_bf16, long n, float* state, float grad_scale,
-                         vlb_stream_t stream);
+ * data-parallel rank for identical gradients, so the clip coefficient -- and therefore the replicas' parameters -- cannot drift.
+ * g is fp32, or with g_is_bf16 a bf16 gradient image (8-byte aligned): the wire format of the data-parallel exchange (DDP all-reduce
+ * of pretrain/function/train.py:89-90 carried out in bf16 over RCCL); the reduced gradient is consumed as it arrived.
+ * scaler (nullable, here and in the steps below): the dynamic loss scaler described further down; NULL = no loss scaling, and
+ * update_scaler is then ignored. */
+int vlb_sumsq_det(const void* g, int g_is_bf16, long n, float* partials, int partials_len, float* out, vlb_stream_t stream);
+int vlb_adamw_step(float* p, const void* g, int g_is_bf16, float* m, float* v, void* p_bf16, long n, float* state, float* scaler,
+                   int update_scaler, float grad_scale, vlb_stream_t stream);
 /* Sharded optimizer of the data-parallel path (replaces the REPLICATED clip + AdamW that DDP implies, common/trainer.py:139-153 after
  * pretrain/function/train.py:89-90): a rank owns one slice of every gradient bucket, the reduce-scatter leaves the reduced slices in a
  * compact image `g` (fp32, or bf16 when g_is_bf16), and clip + AdamW run over those slices only.  ranges: DEVICE int64 [n][3] =
@@ -384,18 +371,21 @@ int vlb_adamw_step_gbf16(float* p, const void* g_bf16, float* m, float* v, void*
 int vlb_sumsq_ranges_det(const void* g, int g_is_bf16, const int64_t* ranges, const int32_t* block_start, int n, int total_blocks, int chunk,
                          float* partials, int partials_len, float* out, vlb_stream_t stream);
 int vlb_adamw_step_ranges(float* p, const void* g, int g_is_bf16, float* m, float* v, void* p_bf16_compact, const int64_t* ranges,
-                          const int32_t* block_start, int n, int total_blocks, int chunk, float* state, float grad_scale, vlb_stream_t stream);
+                          const int32_t* block_start, int n, int total_blocks, int chunk, float* state, float* scaler, float grad_scale,
+                          vlb_stream_t stream);
 /* SGD with momentum (torch.optim.SGD(lr, momentum, weight_decay), dampening 0, no Nesterov: the optimiser of
  * vcr/function/train.py:124-128) in one pass:  d = coef * g + weight_decay * p ;  buf = momentum * buf + d ;  p -= lr * buf ;
  * p_bf16 (optional) = bf16(p).  coef = grad_scale * min(1, max_norm / (sqrt(*sumsq) * grad_scale + 1e-6)) when `sumsq` (device,
  * e.g. from vlb_sumsq_f32) is given and max_norm > 0 -- clip_grad_norm_ of common/trainer.py:139-145 -- else grad_scale. */
 int vlb_sgd_momentum_step(float* p, const float* g, float* momentum_buf, void* p_bf16, long n, float lr, float momentum,
-                          float weight_decay, const float* sumsq, float max_norm, float grad_scale, vlb_stream_t stream);
+                          float weight_decay, const float* sumsq, float max_norm, float grad_scale, float* scaler, int update_scaler,
+                          vlb_stream_t stream);
 /* lr schedule evaluated on the device from state[5] (steps taken): state[0] = base_lr * lambda(step + 1), matching the
  * reference's scheduler.step() -> optimizer.step() order (common/trainer.py:131-135).  kind 0 = ConstantLRSchedule,
  * 1 = WarmupConstantSchedule, 2 = WarmupLinearSchedule (common/nlp/bert/optimization.py:27-62).  Call before
  * vlb_adamw_step; graph-replayable (no host value changes between steps). */
-int vlb_lr_schedule_step(float* state, int kind, float base_lr, float warmup_steps, float t_total, vlb_stream_t stream);
+int vlb_lr_schedule_step(float* state, const float* scaler, int kind, float base_lr, float warmup_steps, float t_total,
+                         vlb_stream_t stream);
 
 /* ---- dynamic loss scaling of the fp16 build (Apex FP16_Optimizer(dynamic_loss_scale=True), the reference's
  *      TRAIN.FP16_LOSS_SCALE: 'dynamic') -- skip decision, scale, unscale and schedule counter on the device ----------------------
@@ -412,14 +402,15 @@ int vlb_lr_schedule_step(float* state, int kind, float base_lr, float warmup_ste
  * well: conservative and harmless (the scale halves and the step is retried on the next batch).
  * Defaults are Apex's (scale 2^16, factors 2 / 0.5, interval 2000, max 2^24).  Two deviations: min_scale defaults to 1 (Apex has no
  * floor), and a step is one OPTIMIZER step on the accumulated gradient (Apex checks every micro-batch under accumulation).
- * The *_scaled steps read the gradient as loss-scaled: coef = grad_scale * (1 / scale) (one division), the clip norm from the same
- * unscaled value -- at scale S the bits of the plain entry point called with grad_scale / S when S is a power of two.
- * vlb_adamw_step_ranges_scaled on a skipped step still writes p_bf16_compact = cast(unchanged p): the weight all-gather reads that
- * image, and before the first step that is really taken nothing else has filled it.
+ * The steps above, given a scaler, read the gradient as loss-scaled: coef = grad_scale * (1 / scale) (one division), the clip norm
+ * from the same unscaled value -- at scale S the bits of the call with scaler == NULL and grad_scale / S when S is a power of two.
+ * vlb_adamw_step_ranges with a scaler still writes p_bf16_compact = cast(unchanged p) on a skipped step: the weight all-gather reads
+ * that image, and before the first step that is really taken nothing else has filled it; it always applies the rule.
  * update_scaler = 0: the rule is not applied (all but the last of several flat runs that share one scaler); the step count and sumsq
- * are handled either way.  vlb_sgd_momentum_step_scaled needs `sumsq` (it carries the decision) and leaves it to the caller.
- * vlb_lr_schedule_step_scaled: lambda(step + skipped_total + 1) -- the reference's scheduler steps on every iteration
- * (common/trainer.py:131-136) while a skipped optimizer.step() leaves Adam's state['step'] alone. */
+ * are handled either way.  vlb_sgd_momentum_step with a scaler needs `sumsq` (it carries the decision) and leaves it to the caller.
+ * vlb_lr_schedule_step with a scaler: lambda(step + skipped_total + 1) -- the reference's scheduler steps on every iteration
+ * (common/trainer.py:131-136) while a skipped optimizer.step() leaves Adam's state['step'] alone.
+ * The losses take the scale as `dscale` (= &scaler[VLB_SCALER_SCALE]). */
 #define VLB_SCALER_FLOATS 9
 #define VLB_SCALER_SCALE 0
 #define VLB_SCALER_GROWTH_FACTOR 1
@@ -430,26 +421,6 @@ int vlb_lr_schedule_step(float* state, int kind, float base_lr, float warmup_ste
 #define VLB_SCALER_SKIPPED_IN_A_ROW 6
 #define VLB_SCALER_MIN_SCALE 7
 #define VLB_SCALER_MAX_SCALE 8
-int vlb_adamw_step_scaled(float* p, const void* g, int g_is_bf16, float* m, float* v, void* p_bf16, long n, float* state, float* scaler,
-                          int update_scaler, float grad_scale, vlb_stream_t stream);
-int vlb_adamw_step_ranges_scaled(float* p, const void* g, int g_is_bf16, float* m, float* v, void* p_bf16_compact, const int64_t* ranges,
-                                 const int32_t* block_start, int n, int total_blocks, int chunk, float* state, float* scaler,
-                                 float grad_scale, vlb_stream_t stream);
-int vlb_sgd_momentum_step_scaled(float* p, const float* g, float* momentum_buf, void* p_bf16, long n, float lr, float momentum,
-                                 float weight_decay, const float* sumsq, float max_norm, float grad_scale, float* scaler, int update_scaler,
-                                 vlb_stream_t stream);
-int vlb_lr_schedule_step_scaled(float* state, const float* scaler, int kind, float base_lr, float warmup_steps, float t_total,
-                                vlb_stream_t stream);
-/* the loss kernels with the gradient scale gscale * *dscale (dscale: DEVICE float, e.g. &scaler[0]; NULL = the plain form): the product
- * is formed once per block and used where gscale is, so a launch at *dscale = S gives the bits of the plain launch given gscale * S */
-int vlb_ce_fwd_bwd_ds(void* logits, long ld, int rows, int V, const int64_t* labels, float* counts, float gscale, const float* dscale,
-                      float* loss_out, void* logits_copy, long ldcopy, vlb_stream_t stream);
-int vlb_ce_fwd_bwd_compact_ds(void* logits, long ld, int rows, int V, const int64_t* labels_c, const float* count0, const float* count1,
-                              float gscale, const float* dscale, float* loss_out0, float* loss_out1, vlb_stream_t stream);
-int vlb_soft_ce_fwd_bwd_ds(void* logits, long ld, int rows, int C, const float* target, long ldt, float* tsum, float* counts, float gscale,
-                           const float* dscale, float* loss_out, void* logits_copy, long ldcopy, vlb_stream_t stream);
-int vlb_bce_logits_fwd_bwd_ds(void* logits, long ld, int rows, int A, const float* label, long ldl, float gscale, const float* dscale,
-                              float pos_weight, float* loss_out, void* logits_copy, long ldcopy, vlb_stream_t stream);
 int vlb_cast_f32_bf16(const float* in, void* out, long n, vlb_stream_t stream);
 int vlb_cast_bf16_f32(const void* in, float* out, long n, vlb_stream_t stream);
 int vlb_rng_advance(uint32_t* seed, vlb_stream_t stream);
@@ -655,7 +626,9 @@ int vlb_bce_logits_f32_fwd_bwd(float* logits, long ld, int rows, int A, const fl
  *                            vlb_head_grad_combine on fp32 rows (idx < 0: a zero row / skipped)
  *   vlb_ce_f32_fwd_bwd / _compact, vlb_soft_ce_f32_fwd_bwd : the losses of vlb_ce_fwd_bwd / _compact / vlb_soft_ce_fwd_bwd on fp32
  *                            logits (ld % 4 == 0, pad columns take no part and get a zero gradient, gradient in place, counts written,
- *                            loss_out +=); row_loss = scratch of `rows` floats, summed in a fixed order */
+ *                            loss_out +=); row_loss = scratch of `rows` floats, summed in a fixed order.  acc / acc0, acc1 (nullable,
+ *                            the compact pair both given or both NULL) and dscale (nullable) as for vlb_ce_fwd_bwd, except that
+ *                            dscale needs acc: dscale without acc is VLB_ERR_ARG */
 int vlb_mask_feature_f32(float* a, const float* boxes, long ldbox, const int64_t* sel, const float* mask_emb, int rows, float drop_p,
                          const uint32_t* seed, uint32_t tag, vlb_stream_t stream);
 int vlb_masked_colsum_f32(const float* src, long lds, const int64_t* sel, int rows, int C, float* dst, float drop_p, const uint32_t* seed,
@@ -668,12 +641,14 @@ int vlb_gather_rows_f32(const float* src, const int32_t* idx, float* out, int n,
 int vlb_scatter_rows_f32(const float* src, const int32_t* idx, float* out, int n, int H, vlb_stream_t stream);
 int vlb_head_grad_combine_f32(const float* d_text, const float* d_obj, const int32_t* code, float* dx, int B, int T, int R, int S, int H,
                               vlb_stream_t stream);
-int vlb_ce_f32_fwd_bwd(float* logits, long ld, int rows, int V, const int64_t* labels, float* counts, float gscale, float* loss_out,
-                       float* row_loss, float* logits_copy, long ldcopy, vlb_stream_t stream);
+int vlb_ce_f32_fwd_bwd(float* logits, long ld, int rows, int V, const int64_t* labels, float* counts, float gscale, const float* dscale,
+                       float* loss_out, float* row_loss, float* logits_copy, long ldcopy, int64_t* acc, vlb_stream_t stream);
 int vlb_ce_f32_fwd_bwd_compact(float* logits, long ld, int rows, int V, const int64_t* labels_c, const float* count0, const float* count1,
-                               float gscale, float* loss_out0, float* loss_out1, float* row_loss, vlb_stream_t stream);
+                               float gscale, const float* dscale, float* loss_out0, float* loss_out1, float* row_loss, int64_t* acc0,
+                               int64_t* acc1, vlb_stream_t stream);
 int vlb_soft_ce_f32_fwd_bwd(float* logits, long ld, int rows, int C, const float* target, long ldt, float* tsum, float* counts, float gscale,
-                            float* loss_out, float* row_loss, float* logits_copy, long ldcopy, vlb_stream_t stream);
+                            const float* dscale, float* loss_out, float* row_loss, float* logits_copy, long ldcopy, int64_t* acc,
+                            vlb_stream_t stream);
 
 /* ---- data-parallel gradient exchange for a C / C++ host: RCCL over xGMI (csrc/comm.hip) ---------------------------------------
  * Replaces the gradient all-reduce that torch DistributedDataParallel / apex DDP issue for the reference

@@ -84,6 +84,33 @@ def test_fp16_build_of_the_library_exports_the_same_abi():
     assert h.vlb_act_dtype() == 1
 
 
+# Entry points of library version 0.1.0 that 0.2.0 folded into their base names (optional features became nullable arguments).
+RETIRED = ("vlb_ce_fwd_bwd_ds", "vlb_ce_fwd_bwd_acc", "vlb_ce_fwd_bwd_compact_ds", "vlb_ce_fwd_bwd_compact_acc", "vlb_soft_ce_fwd_bwd_ds",
+           "vlb_soft_ce_fwd_bwd_acc", "vlb_bce_logits_fwd_bwd_ds", "vlb_ce_f32_fwd_bwd_acc", "vlb_ce_f32_fwd_bwd_compact_acc",
+           "vlb_soft_ce_f32_fwd_bwd_acc", "vlb_adamw_step_gbf16", "vlb_adamw_step_scaled", "vlb_adamw_step_ranges_scaled",
+           "vlb_sgd_momentum_step_scaled", "vlb_lr_schedule_step_scaled", "vlb_sumsq_f32_det", "vlb_sumsq_bf16_det")
+
+
+def test_one_entry_point_per_fused_loss_and_optimizer_step():
+    """One symbol per operation: no prototype carries a feature suffix, and the retired names are gone from the header, the bindings
+    and both builds of the library, whose version says that signatures changed under existing names."""
+    import ctypes
+    lib = importlib.import_module("vl-bert_amd._lib")
+    protos = header_prototypes()
+    for name in protos:
+        assert not name.endswith(("_ds", "_acc", "_scaled", "_gbf16")), name
+    for path in (lib._default_path("bf16"), lib._default_path("f16")):
+        if not os.path.isfile(path):
+            import __graft_entry__
+            __graft_entry__.build()
+        h = ctypes.CDLL(path)
+        h.vlb_version.restype = ctypes.c_int
+        assert h.vlb_version() >= 200
+        for name in RETIRED:
+            assert name not in protos and name not in lib._SIGS, name
+            assert not hasattr(h, name), "%s still exports %s" % (os.path.basename(path), name)
+
+
 def test_missing_library_fails_loudly(monkeypatch):
     lib = importlib.import_module("vl-bert_amd._lib")
     monkeypatch.setattr(lib, "_lib", None)

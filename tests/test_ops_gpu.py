@@ -984,7 +984,7 @@ def test_adamw_and_sumsq(ops):
 
 
 def test_adamw_and_sumsq_on_bf16_wire_gradient(ops):
-    """vlb_sumsq_bf16_det / vlb_adamw_step_gbf16: the optimizer fed with the bf16 wire image of the data-parallel exchange must
+    """vlb_sumsq_det / vlb_adamw_step with g_is_bf16: the optimizer fed with the bf16 wire image of the data-parallel exchange must
     equal the fp32 entry points fed with the same (bf16-representable) values; grad_scale = 1/world folded in."""
     from oracle import vlbert_oracle as O
     n = 70001
@@ -1112,7 +1112,7 @@ def test_bce_logits_and_dropout(ops):
 
 
 def test_sumsq_deterministic(ops):
-    """vlb_sumsq_f32_det: right value, accumulates into *out, and the same bits on every call (the atomic version is not)."""
+    """vlb_sumsq_det: right value, accumulates into *out, and the same bits on every call (the atomic version is not)."""
     n = 3_000_017
     g = torch.randn(n, generator=torch.Generator().manual_seed(51)).to(dev())
     ws = torch.zeros(2048, device=dev())

@@ -81,7 +81,7 @@ def part_a():
     mlm = {
         "restore the logits (a copy; part of every variant below)": restore,
         "vlb_ce_fwd_bwd_compact": lambda: (restore(), ops.ce_fwd_bwd_compact(x, V, lab, counts[0:1], counts[1:2], loss[0:1], loss[1:2])),
-        "vlb_ce_fwd_bwd_compact_acc": lambda: (restore(), ops.ce_fwd_bwd_compact(x, V, lab, counts[0:1], counts[1:2], loss[0:1], loss[1:2],
+        "vlb_ce_fwd_bwd_compact, acc given": lambda: (restore(), ops.ce_fwd_bwd_compact(x, V, lab, counts[0:1], counts[1:2], loss[0:1], loss[1:2],
                                                                                  acc=acc[0], acc1=acc[1])),
         "vlb_ce_fwd_bwd + kept copy, then vlb_ce_eval on it": lambda: (restore(), ops.ce_fwd_bwd(x, V, lab, counts[2:3], loss[0:1], logits_copy=cp),
                                                                         ops.ce_eval(cp, V, lab, loss[1:2], acc[0])),
@@ -97,7 +97,7 @@ def part_a():
     mvrc = {
         "restore the logits (a copy; part of every variant below)": restore2,
         "vlb_soft_ce_fwd_bwd": lambda: (restore2(), ops.soft_ce_fwd_bwd(x2, C, t, tsum, c2, loss[0:1])),
-        "vlb_soft_ce_fwd_bwd_acc": lambda: (restore2(), ops.soft_ce_fwd_bwd(x2, C, t, tsum, c2, loss[0:1], acc=acc[0])),
+        "vlb_soft_ce_fwd_bwd, acc given": lambda: (restore2(), ops.soft_ce_fwd_bwd(x2, C, t, tsum, c2, loss[0:1], acc=acc[0])),
         "vlb_soft_ce_fwd_bwd + kept copy, then vlb_soft_ce_eval on it": lambda: (restore2(), ops.soft_ce_fwd_bwd(x2, C, t, tsum, c2, loss[0:1], logits_copy=cp2),
                                                                                   ops.soft_ce_eval(cp2, C, t, loss[1:2], acc[0])),
     }
@@ -109,7 +109,7 @@ def part_a():
     rel = {
         "restore the logits (a copy; part of every variant below)": restore3,
         "vlb_ce_fwd_bwd": lambda: (restore3(), ops.ce_fwd_bwd(x3, 2, lab3, c2, loss[0:1])),
-        "vlb_ce_fwd_bwd_acc": lambda: (restore3(), ops.ce_fwd_bwd(x3, 2, lab3, c2, loss[0:1], acc=acc[0])),
+        "vlb_ce_fwd_bwd, acc given": lambda: (restore3(), ops.ce_fwd_bwd(x3, 2, lab3, c2, loss[0:1], acc=acc[0])),
         "vlb_ce_fwd_bwd + kept copy, then vlb_ce_eval on it": lambda: (restore3(), ops.ce_fwd_bwd(x3, 2, lab3, c2, loss[0:1], logits_copy=cp3),
                                                                         ops.ce_eval(cp3, 2, lab3, loss[1:2], acc[0])),
     }

@@ -58,47 +58,31 @@ _SIGS = {
     "vlb_gather_rows": "pppiis",
     "vlb_scatter_rows": "pppiis",
     "vlb_mlm_compact": "ppiiiipppppps",
-    "vlb_ce_fwd_bwd_compact": "pliipppfpps",
+    "vlb_ce_fwd_bwd_compact": "pliipppfppppps",
     "vlb_head_grad_combine": "ppppiiiiis",
     "vlb_relu_bwd_cast": "pppls",
     "vlb_dgelu_mul": "pppls",
     "vlb_mul_bf16": "pppls",
     "vlb_tanh_bwd": "pppls",
-    "vlb_ce_fwd_bwd": "pliippfppls",
-    "vlb_soft_ce_fwd_bwd": "pliiplppfppls",
+    # (the fused losses: nullable dscale, nullable int64 [2] counters)
+    "vlb_ce_fwd_bwd": "pliippfppplps",
+    "vlb_soft_ce_fwd_bwd": "pliiplppfppplps",
     "vlb_ce_eval": "plii" + "p" * 8 + "s",
     "vlb_soft_ce_eval": "pliiplpps",
-    # training-time metrics: the fused losses + [hits, counted rows] (nullable dscale, int64 [2] counters)
-    "vlb_ce_fwd_bwd_acc": "pliippfppplps",
-    "vlb_ce_fwd_bwd_compact_acc": "pliipppfppppps",
-    "vlb_soft_ce_fwd_bwd_acc": "pliiplppfppplps",
-    "vlb_ce_f32_fwd_bwd_acc": "pliippfpppplps",
-    "vlb_ce_f32_fwd_bwd_compact_acc": "pliipppfpppppps",
-    "vlb_soft_ce_f32_fwd_bwd_acc": "pliiplppfpppplps",
     "vlb_argmax_eval": "pliiiplppplpps",
     "vlb_binary_cls_eval": "plpliips",
     "vlb_joint_hits": "ppppips",
     "vlb_sumsq_f32": "plps",
     "vlb_zero_padded_rows_bf16": "plpliis",
-    "vlb_bce_logits_fwd_bwd": "pliiplffppls",
+    "vlb_bce_logits_fwd_bwd": "pliiplfpfppls",
     "vlb_dropout_bf16": "pplfpus",
-    "vlb_sumsq_f32_det": "plpips",
-    "vlb_adamw_step": "ppppplpfs",
-    "vlb_adamw_step_gbf16": "ppppplpfs",
-    "vlb_sgd_momentum_step": "pppplfffpffs",
-    "vlb_sumsq_bf16_det": "plpips",
+    # optimizer steps: g_is_bf16 flags a 16-bit gradient image, the scaler (device-resident loss-scaler state) is nullable
+    "vlb_sumsq_det": "pilpips",
+    "vlb_adamw_step": "ppippplppifs",
+    "vlb_sgd_momentum_step": "pppplfffpffpis",
     "vlb_sumsq_ranges_det": "pippiiipips",
-    "vlb_adamw_step_ranges": "ppipppppiiipfs",
-    "vlb_lr_schedule_step": "pifffs",
-    # dynamic loss scaling (device-resident scaler state, include/vlbert_hip.h)
-    "vlb_adamw_step_scaled": "ppippplppifs",
-    "vlb_adamw_step_ranges_scaled": "ppipppppiiippfs",
-    "vlb_sgd_momentum_step_scaled": "pppplfffpffpis",
-    "vlb_lr_schedule_step_scaled": "ppifffs",
-    "vlb_ce_fwd_bwd_ds": "pliippfpppls",
-    "vlb_ce_fwd_bwd_compact_ds": "pliipppfppps",
-    "vlb_soft_ce_fwd_bwd_ds": "pliiplppfpppls",
-    "vlb_bce_logits_fwd_bwd_ds": "pliiplfpfppls",
+    "vlb_adamw_step_ranges": "ppipppppiiippfs",
+    "vlb_lr_schedule_step": "ppifffs",
     "vlb_conv_weight_prepare": "pppppfppppiiiis",
     "vlb_conv_weight_prepare_batched": "ppiifs",
     "vlb_conv_wgrad_finalize": "pppiiiis",
@@ -143,9 +127,9 @@ _SIGS = {
     "vlb_gather_rows_f32": "pppiis",
     "vlb_scatter_rows_f32": "pppiis",
     "vlb_head_grad_combine_f32": "ppppiiiiis",
-    "vlb_ce_f32_fwd_bwd": "pliippfpppls",
-    "vlb_ce_f32_fwd_bwd_compact": "pliipppfppps",
-    "vlb_soft_ce_f32_fwd_bwd": "pliiplppfpppls",
+    "vlb_ce_f32_fwd_bwd": "pliippfpppplps",
+    "vlb_ce_f32_fwd_bwd_compact": "pliipppfpppppps",
+    "vlb_soft_ce_f32_fwd_bwd": "pliiplppfpppplps",
     "vlb_scale_f32": "plfs",
     "vlb_cast_f32_bf16": "ppls",
     "vlb_cast_bf16_f32": "ppls",

@@ -606,20 +606,31 @@ extern "C" int vlb_head_grad_combine_f32(const float* d_text, const float* d_obj
   return VLB_OK;
 }
 
-static int ce_f32_check(const char* name, const float* logits, long ld, int V, const float* logits_copy, long ldcopy) {
+// acc (nullable) selects the ACC kernels: [hits, counted rows] added to an int64[2] per group.  dscale (nullable) is theirs alone: the
+// plain kernels take no dynamic scale, so dscale without acc is refused.
+static int ce_f32_check(const char* name, const float* logits, long ld, int V, const float* logits_copy, long ldcopy, const float* dscale,
+                        const int64_t* acc) {
+  VLB_CHECK_ARG(!dscale || acc, "%s: dscale needs acc (the kernels without the counters take no dynamic scale)", name);
   VLB_CHECK_ARG(V > 0 && ld >= V && (ld % 4) == 0 && al16(logits), "%s: ld=%ld must be >= V=%d and a multiple of 4, rows 16-byte aligned", name, ld, V);
   VLB_CHECK_ARG(!logits_copy || (ldcopy >= V && (ldcopy % 4) == 0 && al16(logits_copy)), "%s: logits_copy needs ldcopy >= V, ldcopy %% 4 == 0", name);
   return VLB_OK;
 }
 
-extern "C" int vlb_ce_f32_fwd_bwd(float* logits, long ld, int rows, int V, const int64_t* labels, float* counts, float gscale, float* loss_out,
-                                  float* row_loss, float* logits_copy, long ldcopy, hipStream_t stream) {
+extern "C" int vlb_ce_f32_fwd_bwd(float* logits, long ld, int rows, int V, const int64_t* labels, float* counts, float gscale,
+                                  const float* dscale, float* loss_out, float* row_loss, float* logits_copy, long ldcopy, int64_t* acc,
+                                  hipStream_t stream) {
   if (rows <= 0) return VLB_OK;
   VLB_CHECK_ARG(logits && labels && counts && loss_out && row_loss, "vlb_ce_f32_fwd_bwd: null argument");
-  if (ce_f32_check("vlb_ce_f32_fwd_bwd", logits, ld, V, logits_copy, ldcopy) != VLB_OK) return VLB_ERR_ARG;
-  hipLaunchKernelGGL(count_labels_f32_kernel, dim3(1), dim3(256), 0, stream, labels, rows, counts);
-  hipLaunchKernelGGL(ce_f32_kernel, dim3(rows), dim3(256), 0, stream, logits, ld, V, labels, (const float*)counts, (const float*)nullptr, gscale,
-                     row_loss, logits_copy, ldcopy);
+  if (ce_f32_check("vlb_ce_f32_fwd_bwd", logits, ld, V, logits_copy, ldcopy, dscale, acc) != VLB_OK) return VLB_ERR_ARG;
+  if (acc) {
+    hipLaunchKernelGGL(count_labels_f32_acc_kernel, dim3(1), dim3(256), 0, stream, labels, rows, V, counts, (vlb_u64*)acc);
+    hipLaunchKernelGGL(ce_f32_acc_kernel, dim3(rows), dim3(256), 0, stream, logits, ld, V, labels, (const float*)counts, (const float*)nullptr,
+                       gscale, row_loss, logits_copy, ldcopy, dscale, (vlb_u64*)acc, (vlb_u64*)nullptr);
+  } else {
+    hipLaunchKernelGGL(count_labels_f32_kernel, dim3(1), dim3(256), 0, stream, labels, rows, counts);
+    hipLaunchKernelGGL(ce_f32_kernel, dim3(rows), dim3(256), 0, stream, logits, ld, V, labels, (const float*)counts, (const float*)nullptr,
+                       gscale, row_loss, logits_copy, ldcopy);
+  }
   hipLaunchKernelGGL(loss_sum_f32_kernel, dim3(1), dim3(64), 0, stream, (const float*)row_loss, rows, (const float*)counts, (const float*)nullptr,
                      loss_out, (float*)nullptr);
   VLB_CHECK_LAUNCH("vlb_ce_f32_fwd_bwd");
@@ -627,74 +638,39 @@ extern "C" int vlb_ce_f32_fwd_bwd(float* logits, long ld, int rows, int V, const
 }
 
 extern "C" int vlb_ce_f32_fwd_bwd_compact(float* logits, long ld, int rows, int V, const int64_t* labels_c, const float* count0,
-                                          const float* count1, float gscale, float* loss_out0, float* loss_out1, float* row_loss,
-                                          hipStream_t stream) {
+                                          const float* count1, float gscale, const float* dscale, float* loss_out0, float* loss_out1,
+                                          float* row_loss, int64_t* acc0, int64_t* acc1, hipStream_t stream) {
   if (rows <= 0) return VLB_OK;
-  VLB_CHECK_ARG(logits && labels_c && count0 && count1 && loss_out0 && loss_out1 && row_loss, "vlb_ce_f32_fwd_bwd_compact: null argument");
-  if (ce_f32_check("vlb_ce_f32_fwd_bwd_compact", logits, ld, V, nullptr, 0) != VLB_OK) return VLB_ERR_ARG;
-  hipLaunchKernelGGL(ce_f32_kernel, dim3(rows), dim3(256), 0, stream, logits, ld, V, labels_c, count0, count1, gscale, row_loss, (float*)nullptr, 0L);
+  VLB_CHECK_ARG(logits && labels_c && count0 && count1 && loss_out0 && loss_out1 && row_loss && !acc0 == !acc1,
+                "vlb_ce_f32_fwd_bwd_compact: null argument");
+  if (ce_f32_check("vlb_ce_f32_fwd_bwd_compact", logits, ld, V, nullptr, 0, dscale, acc0) != VLB_OK) return VLB_ERR_ARG;
+  if (acc0)
+    hipLaunchKernelGGL(ce_f32_acc_kernel, dim3(rows), dim3(256), 0, stream, logits, ld, V, labels_c, count0, count1, gscale, row_loss,
+                       (float*)nullptr, 0L, dscale, (vlb_u64*)acc0, (vlb_u64*)acc1);
+  else
+    hipLaunchKernelGGL(ce_f32_kernel, dim3(rows), dim3(256), 0, stream, logits, ld, V, labels_c, count0, count1, gscale, row_loss,
+                       (float*)nullptr, 0L);
   hipLaunchKernelGGL(loss_sum_f32_kernel, dim3(1), dim3(64), 0, stream, (const float*)row_loss, rows, count0, count1, loss_out0, loss_out1);
   VLB_CHECK_LAUNCH("vlb_ce_f32_fwd_bwd_compact");
   return VLB_OK;
 }
 
 extern "C" int vlb_soft_ce_f32_fwd_bwd(float* logits, long ld, int rows, int C, const float* target, long ldt, float* tsum, float* counts,
-                                       float gscale, float* loss_out, float* row_loss, float* logits_copy, long ldcopy, hipStream_t stream) {
+                                       float gscale, const float* dscale, float* loss_out, float* row_loss, float* logits_copy, long ldcopy,
+                                       int64_t* acc, hipStream_t stream) {
   if (rows <= 0) return VLB_OK;
   VLB_CHECK_ARG(logits && target && tsum && counts && loss_out && row_loss && ldt >= C, "vlb_soft_ce_f32_fwd_bwd: null argument or ldt < C");
-  if (ce_f32_check("vlb_soft_ce_f32_fwd_bwd", logits, ld, C, logits_copy, ldcopy) != VLB_OK) return VLB_ERR_ARG;
+  if (ce_f32_check("vlb_soft_ce_f32_fwd_bwd", logits, ld, C, logits_copy, ldcopy, dscale, acc) != VLB_OK) return VLB_ERR_ARG;
   hipLaunchKernelGGL(soft_valid_f32_kernel, dim3(vlb_cdiv(rows, 4)), dim3(256), 0, stream, target, ldt, C, rows, tsum);
   hipLaunchKernelGGL(soft_count_f32_kernel, dim3(1), dim3(256), 0, stream, (const float*)tsum, rows, counts);
-  hipLaunchKernelGGL(soft_ce_f32_kernel, dim3(rows), dim3(256), 0, stream, logits, ld, C, target, ldt, (const float*)tsum, (const float*)counts, gscale,
-                     row_loss, logits_copy, ldcopy);
+  if (acc)
+    hipLaunchKernelGGL(soft_ce_f32_acc_kernel, dim3(rows), dim3(256), 0, stream, logits, ld, C, target, ldt, (const float*)tsum,
+                       (const float*)counts, gscale, row_loss, logits_copy, ldcopy, dscale, (vlb_u64*)acc);
+  else
+    hipLaunchKernelGGL(soft_ce_f32_kernel, dim3(rows), dim3(256), 0, stream, logits, ld, C, target, ldt, (const float*)tsum,
+                       (const float*)counts, gscale, row_loss, logits_copy, ldcopy);
   hipLaunchKernelGGL(loss_sum_f32_kernel, dim3(1), dim3(64), 0, stream, (const float*)row_loss, rows, (const float*)counts, (const float*)nullptr,
                      loss_out, (float*)nullptr);
   VLB_CHECK_LAUNCH("vlb_soft_ce_f32_fwd_bwd");
-  return VLB_OK;
-}
-
-// the *_acc forms: the same launches with the ACC kernels -- [hits, counted rows] added to an int64[2] per group; dscale nullable
-extern "C" int vlb_ce_f32_fwd_bwd_acc(float* logits, long ld, int rows, int V, const int64_t* labels, float* counts, float gscale,
-                                      const float* dscale, float* loss_out, float* row_loss, float* logits_copy, long ldcopy, int64_t* acc,
-                                      hipStream_t stream) {
-  if (rows <= 0) return VLB_OK;
-  VLB_CHECK_ARG(logits && labels && counts && loss_out && row_loss && acc, "vlb_ce_f32_fwd_bwd_acc: null argument");
-  if (ce_f32_check("vlb_ce_f32_fwd_bwd_acc", logits, ld, V, logits_copy, ldcopy) != VLB_OK) return VLB_ERR_ARG;
-  hipLaunchKernelGGL(count_labels_f32_acc_kernel, dim3(1), dim3(256), 0, stream, labels, rows, V, counts, (vlb_u64*)acc);
-  hipLaunchKernelGGL(ce_f32_acc_kernel, dim3(rows), dim3(256), 0, stream, logits, ld, V, labels, (const float*)counts, (const float*)nullptr, gscale,
-                     row_loss, logits_copy, ldcopy, dscale, (vlb_u64*)acc, (vlb_u64*)nullptr);
-  hipLaunchKernelGGL(loss_sum_f32_kernel, dim3(1), dim3(64), 0, stream, (const float*)row_loss, rows, (const float*)counts, (const float*)nullptr,
-                     loss_out, (float*)nullptr);
-  VLB_CHECK_LAUNCH("vlb_ce_f32_fwd_bwd_acc");
-  return VLB_OK;
-}
-
-extern "C" int vlb_ce_f32_fwd_bwd_compact_acc(float* logits, long ld, int rows, int V, const int64_t* labels_c, const float* count0,
-                                              const float* count1, float gscale, const float* dscale, float* loss_out0, float* loss_out1,
-                                              float* row_loss, int64_t* acc0, int64_t* acc1, hipStream_t stream) {
-  if (rows <= 0) return VLB_OK;
-  VLB_CHECK_ARG(logits && labels_c && count0 && count1 && loss_out0 && loss_out1 && row_loss && acc0 && acc1,
-                "vlb_ce_f32_fwd_bwd_compact_acc: null argument");
-  if (ce_f32_check("vlb_ce_f32_fwd_bwd_compact_acc", logits, ld, V, nullptr, 0) != VLB_OK) return VLB_ERR_ARG;
-  hipLaunchKernelGGL(ce_f32_acc_kernel, dim3(rows), dim3(256), 0, stream, logits, ld, V, labels_c, count0, count1, gscale, row_loss, (float*)nullptr,
-                     0L, dscale, (vlb_u64*)acc0, (vlb_u64*)acc1);
-  hipLaunchKernelGGL(loss_sum_f32_kernel, dim3(1), dim3(64), 0, stream, (const float*)row_loss, rows, count0, count1, loss_out0, loss_out1);
-  VLB_CHECK_LAUNCH("vlb_ce_f32_fwd_bwd_compact_acc");
-  return VLB_OK;
-}
-
-extern "C" int vlb_soft_ce_f32_fwd_bwd_acc(float* logits, long ld, int rows, int C, const float* target, long ldt, float* tsum, float* counts,
-                                           float gscale, const float* dscale, float* loss_out, float* row_loss, float* logits_copy, long ldcopy,
-                                           int64_t* acc, hipStream_t stream) {
-  if (rows <= 0) return VLB_OK;
-  VLB_CHECK_ARG(logits && target && tsum && counts && loss_out && row_loss && acc && ldt >= C, "vlb_soft_ce_f32_fwd_bwd_acc: null argument or ldt < C");
-  if (ce_f32_check("vlb_soft_ce_f32_fwd_bwd_acc", logits, ld, C, logits_copy, ldcopy) != VLB_OK) return VLB_ERR_ARG;
-  hipLaunchKernelGGL(soft_valid_f32_kernel, dim3(vlb_cdiv(rows, 4)), dim3(256), 0, stream, target, ldt, C, rows, tsum);
-  hipLaunchKernelGGL(soft_count_f32_kernel, dim3(1), dim3(256), 0, stream, (const float*)tsum, rows, counts);
-  hipLaunchKernelGGL(soft_ce_f32_acc_kernel, dim3(rows), dim3(256), 0, stream, logits, ld, C, target, ldt, (const float*)tsum, (const float*)counts,
-                     gscale, row_loss, logits_copy, ldcopy, dscale, (vlb_u64*)acc);
-  hipLaunchKernelGGL(loss_sum_f32_kernel, dim3(1), dim3(64), 0, stream, (const float*)row_loss, rows, (const float*)counts, (const float*)nullptr,
-                     loss_out, (float*)nullptr);
-  VLB_CHECK_LAUNCH("vlb_soft_ce_f32_fwd_bwd_acc");
   return VLB_OK;
 }

@@ -301,21 +301,23 @@ extern "C" int vlb_mlm_compact(const int64_t* labels, const int32_t* src_rows, i
 }
 
 // CE forward + backward on COMPACTED rows: counts are given (vlb_mlm_compact wrote them), two groups with their own means.
-static int ce_fwd_bwd_compact(void* logits, long ld, int rows, int V, const int64_t* labels_c, const float* count0, const float* count1,
-                              float gscale, const float* dscale, float* loss_out0, float* loss_out1, hipStream_t stream,
-                              int64_t* acc0 = nullptr, int64_t* acc1 = nullptr) {
+// dscale (nullable): gscale * *dscale from a device scalar -- the dynamic loss scale of an fp16 run.  acc0 / acc1 (both or neither):
+// [hits, counted rows] of the two groups added to an int64[2] each.
+extern "C" int vlb_ce_fwd_bwd_compact(void* logits, long ld, int rows, int V, const int64_t* labels_c, const float* count0,
+                                      const float* count1, float gscale, const float* dscale, float* loss_out0, float* loss_out1,
+                                      int64_t* acc0, int64_t* acc1, hipStream_t stream) {
+  VLB_CHECK_ARG(!acc0 == !acc1, "vlb_ce_fwd_bwd_compact: null counters");
   if (rows <= 0) return VLB_OK;
   VLB_CHECK_ARG(logits && labels_c && count0 && count1 && loss_out0 && loss_out1, "vlb_ce_fwd_bwd_compact: null argument");
   VLB_CHECK_ARG(ld >= V && (ld % 8) == 0, "vlb_ce_fwd_bwd_compact: ld=%ld must be >= V=%d and a multiple of 8", ld, V);
   if (acc0) {      // the ACC form: its own instantiations, the launches below are the ones they were
-    VLB_CHECK_ARG(acc1, "vlb_ce_fwd_bwd_compact_acc: acc1 is null");
     if (dscale)
       hipLaunchKernelGGL((ce_fwd_bwd_kernel<true, true>), dim3(rows), dim3(256), 0, stream, (bf16_t*)logits, ld, V, labels_c, count0, gscale,
                          loss_out0, (bf16_t*)nullptr, 0L, count1, loss_out1, dscale, (vlb_u64*)acc0, (vlb_u64*)acc1);
     else
       hipLaunchKernelGGL((ce_fwd_bwd_kernel<false, true>), dim3(rows), dim3(256), 0, stream, (bf16_t*)logits, ld, V, labels_c, count0, gscale,
                          loss_out0, (bf16_t*)nullptr, 0L, count1, loss_out1, (const float*)nullptr, (vlb_u64*)acc0, (vlb_u64*)acc1);
-    VLB_CHECK_LAUNCH("vlb_ce_fwd_bwd_compact_acc");
+    VLB_CHECK_LAUNCH("vlb_ce_fwd_bwd_compact");
     return VLB_OK;
   }
   if (dscale)
@@ -326,25 +328,6 @@ static int ce_fwd_bwd_compact(void* logits, long ld, int rows, int V, const int6
                        (bf16_t*)nullptr, 0L, count1, loss_out1, (const float*)nullptr);
   VLB_CHECK_LAUNCH("vlb_ce_fwd_bwd_compact");
   return VLB_OK;
-}
-
-extern "C" int vlb_ce_fwd_bwd_compact(void* logits, long ld, int rows, int V, const int64_t* labels_c, const float* count0,
-                                      const float* count1, float gscale, float* loss_out0, float* loss_out1, hipStream_t stream) {
-  return ce_fwd_bwd_compact(logits, ld, rows, V, labels_c, count0, count1, gscale, nullptr, loss_out0, loss_out1, stream);
-}
-
-// (the *_ds forms: gscale * *dscale from a device scalar, nullable = the plain form -- the dynamic loss scale of an fp16 run)
-extern "C" int vlb_ce_fwd_bwd_compact_ds(void* logits, long ld, int rows, int V, const int64_t* labels_c, const float* count0,
-                                         const float* count1, float gscale, const float* dscale, float* loss_out0, float* loss_out1,
-                                         hipStream_t stream) {
-  return ce_fwd_bwd_compact(logits, ld, rows, V, labels_c, count0, count1, gscale, dscale, loss_out0, loss_out1, stream);
-}
-
-extern "C" int vlb_ce_fwd_bwd_compact_acc(void* logits, long ld, int rows, int V, const int64_t* labels_c, const float* count0,
-                                          const float* count1, float gscale, const float* dscale, float* loss_out0, float* loss_out1,
-                                          int64_t* acc0, int64_t* acc1, hipStream_t stream) {
-  VLB_CHECK_ARG(acc0 && acc1, "vlb_ce_fwd_bwd_compact_acc: null counters");
-  return ce_fwd_bwd_compact(logits, ld, rows, V, labels_c, count0, count1, gscale, dscale, loss_out0, loss_out1, stream, acc0, acc1);
 }
 
 // row validity for the soft-label loss: valid[r] = |sum_c t[r,c] - 1| < 0.1 ; counts[0] += #valid
@@ -432,8 +415,9 @@ __global__ __launch_bounds__(256) void soft_ce_fwd_bwd_kernel(bf16_t* __restrict
   }
 }
 
-static int ce_fwd_bwd(void* logits, long ld, int rows, int V, const int64_t* labels, float* counts, float gscale, const float* dscale,
-                      float* loss_out, void* logits_copy, long ldcopy, hipStream_t stream, int64_t* acc = nullptr) {
+// dscale, acc: nullable, as in vlb_ce_fwd_bwd_compact (one group, one int64[2])
+extern "C" int vlb_ce_fwd_bwd(void* logits, long ld, int rows, int V, const int64_t* labels, float* counts, float gscale, const float* dscale,
+                              float* loss_out, void* logits_copy, long ldcopy, int64_t* acc, hipStream_t stream) {
   if (rows <= 0) return VLB_OK;
   VLB_CHECK_ARG(logits && labels && counts && loss_out, "vlb_ce_fwd_bwd: null argument");
   VLB_CHECK_ARG(ld >= V && (ld % 8) == 0, "vlb_ce_fwd_bwd: ld=%ld must be >= V=%d and a multiple of 8", ld, V);
@@ -448,7 +432,7 @@ static int ce_fwd_bwd(void* logits, long ld, int rows, int V, const int64_t* lab
       hipLaunchKernelGGL((ce_fwd_bwd_kernel<false, true>), dim3(rows), dim3(256), 0, stream, (bf16_t*)logits, ld, V, labels, counts, gscale,
                          loss_out, (bf16_t*)logits_copy, ldcopy, (const float*)nullptr, (float*)nullptr, (const float*)nullptr, (vlb_u64*)acc,
                          (vlb_u64*)nullptr);
-    VLB_CHECK_LAUNCH("vlb_ce_fwd_bwd_acc");
+    VLB_CHECK_LAUNCH("vlb_ce_fwd_bwd");
     return VLB_OK;
   }
   hipLaunchKernelGGL(count_labels_kernel, dim3(vlb_cdiv(rows, 256) > 64 ? 64 : vlb_cdiv(rows, 256)), dim3(256), 0, stream, labels, rows,
@@ -463,25 +447,9 @@ static int ce_fwd_bwd(void* logits, long ld, int rows, int V, const int64_t* lab
   return VLB_OK;
 }
 
-extern "C" int vlb_ce_fwd_bwd(void* logits, long ld, int rows, int V, const int64_t* labels, float* counts, float gscale,
-                              float* loss_out, void* logits_copy, long ldcopy, hipStream_t stream) {
-  return ce_fwd_bwd(logits, ld, rows, V, labels, counts, gscale, nullptr, loss_out, logits_copy, ldcopy, stream);
-}
-
-extern "C" int vlb_ce_fwd_bwd_ds(void* logits, long ld, int rows, int V, const int64_t* labels, float* counts, float gscale,
-                                 const float* dscale, float* loss_out, void* logits_copy, long ldcopy, hipStream_t stream) {
-  return ce_fwd_bwd(logits, ld, rows, V, labels, counts, gscale, dscale, loss_out, logits_copy, ldcopy, stream);
-}
-
-// (the *_acc forms: the fused loss + [hits, counted rows] added to an int64[2]; dscale nullable = the static scale)
-extern "C" int vlb_ce_fwd_bwd_acc(void* logits, long ld, int rows, int V, const int64_t* labels, float* counts, float gscale,
-                                  const float* dscale, float* loss_out, void* logits_copy, long ldcopy, int64_t* acc, hipStream_t stream) {
-  VLB_CHECK_ARG(acc, "vlb_ce_fwd_bwd_acc: null counters");
-  return ce_fwd_bwd(logits, ld, rows, V, labels, counts, gscale, dscale, loss_out, logits_copy, ldcopy, stream, acc);
-}
-
-static int soft_ce_fwd_bwd(void* logits, long ld, int rows, int C, const float* target, long ldt, float* tsum, float* counts, float gscale,
-                           const float* dscale, float* loss_out, void* logits_copy, long ldcopy, hipStream_t stream, int64_t* acc = nullptr) {
+extern "C" int vlb_soft_ce_fwd_bwd(void* logits, long ld, int rows, int C, const float* target, long ldt, float* tsum, float* counts,
+                                   float gscale, const float* dscale, float* loss_out, void* logits_copy, long ldcopy, int64_t* acc,
+                                   hipStream_t stream) {
   if (rows <= 0) return VLB_OK;
   VLB_CHECK_ARG(logits && target && tsum && counts && loss_out, "vlb_soft_ce_fwd_bwd: null argument");
   VLB_CHECK_ARG(ld >= C && ldt >= C, "vlb_soft_ce_fwd_bwd: bad leading dimensions");
@@ -494,7 +462,7 @@ static int soft_ce_fwd_bwd(void* logits, long ld, int rows, int C, const float* 
     else
       hipLaunchKernelGGL((soft_ce_fwd_bwd_kernel<false, true>), dim3(rows), dim3(256), 0, stream, (bf16_t*)logits, ld, C, target, ldt, tsum, counts,
                          gscale, loss_out, (bf16_t*)logits_copy, ldcopy, (const float*)nullptr, (vlb_u64*)acc);
-    VLB_CHECK_LAUNCH("vlb_soft_ce_fwd_bwd_acc");
+    VLB_CHECK_LAUNCH("vlb_soft_ce_fwd_bwd");
     return VLB_OK;
   }
   if (dscale)
@@ -505,25 +473,6 @@ static int soft_ce_fwd_bwd(void* logits, long ld, int rows, int C, const float* 
                        gscale, loss_out, (bf16_t*)logits_copy, ldcopy, (const float*)nullptr);
   VLB_CHECK_LAUNCH("vlb_soft_ce_fwd_bwd");
   return VLB_OK;
-}
-
-extern "C" int vlb_soft_ce_fwd_bwd(void* logits, long ld, int rows, int C, const float* target, long ldt, float* tsum,
-                                   float* counts, float gscale, float* loss_out, void* logits_copy, long ldcopy,
-                                   hipStream_t stream) {
-  return soft_ce_fwd_bwd(logits, ld, rows, C, target, ldt, tsum, counts, gscale, nullptr, loss_out, logits_copy, ldcopy, stream);
-}
-
-extern "C" int vlb_soft_ce_fwd_bwd_ds(void* logits, long ld, int rows, int C, const float* target, long ldt, float* tsum, float* counts,
-                                      float gscale, const float* dscale, float* loss_out, void* logits_copy, long ldcopy,
-                                      hipStream_t stream) {
-  return soft_ce_fwd_bwd(logits, ld, rows, C, target, ldt, tsum, counts, gscale, dscale, loss_out, logits_copy, ldcopy, stream);
-}
-
-extern "C" int vlb_soft_ce_fwd_bwd_acc(void* logits, long ld, int rows, int C, const float* target, long ldt, float* tsum, float* counts,
-                                       float gscale, const float* dscale, float* loss_out, void* logits_copy, long ldcopy, int64_t* acc,
-                                       hipStream_t stream) {
-  VLB_CHECK_ARG(acc, "vlb_soft_ce_fwd_bwd_acc: null counters");
-  return soft_ce_fwd_bwd(logits, ld, rows, C, target, ldt, tsum, counts, gscale, dscale, loss_out, logits_copy, ldcopy, stream, acc);
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -562,8 +511,9 @@ __global__ __launch_bounds__(256) void bce_logits_fwd_bwd_kernel(bf16_t* __restr
   if (threadIdx.x == 0) atomicAdd(loss_out, s * inv_rows);
 }
 
-static int bce_logits_fwd_bwd(void* logits, long ld, int rows, int A, const float* label, long ldl, float gscale, const float* dscale,
-                              float pos_weight, float* loss_out, void* logits_copy, long ldcopy, hipStream_t stream) {
+extern "C" int vlb_bce_logits_fwd_bwd(void* logits, long ld, int rows, int A, const float* label, long ldl, float gscale,
+                                      const float* dscale, float pos_weight, float* loss_out, void* logits_copy, long ldcopy,
+                                      hipStream_t stream) {
   if (rows <= 0) return VLB_OK;
   VLB_CHECK_ARG(logits && label && loss_out && A > 0 && ld >= A && ldl >= A, "vlb_bce_logits_fwd_bwd: bad argument");
   VLB_CHECK_ARG(!logits_copy || ldcopy >= A, "vlb_bce_logits_fwd_bwd: ldcopy too small");
@@ -575,17 +525,6 @@ static int bce_logits_fwd_bwd(void* logits, long ld, int rows, int A, const floa
                        pos_weight, loss_out, (bf16_t*)logits_copy, ldcopy, (const float*)nullptr);
   VLB_CHECK_LAUNCH("vlb_bce_logits_fwd_bwd");
   return VLB_OK;
-}
-
-extern "C" int vlb_bce_logits_fwd_bwd(void* logits, long ld, int rows, int A, const float* label, long ldl, float gscale, float pos_weight,
-                                      float* loss_out, void* logits_copy, long ldcopy, hipStream_t stream) {
-  return bce_logits_fwd_bwd(logits, ld, rows, A, label, ldl, gscale, nullptr, pos_weight, loss_out, logits_copy, ldcopy, stream);
-}
-
-extern "C" int vlb_bce_logits_fwd_bwd_ds(void* logits, long ld, int rows, int A, const float* label, long ldl, float gscale,
-                                         const float* dscale, float pos_weight, float* loss_out, void* logits_copy, long ldcopy,
-                                         hipStream_t stream) {
-  return bce_logits_fwd_bwd(logits, ld, rows, A, label, ldl, gscale, dscale, pos_weight, loss_out, logits_copy, ldcopy, stream);
 }
 
 // y = x * keep(idx) / (1 - p) with the counter RNG (element index = position in the [n] array); the same call on dy is the backward.

@@ -333,64 +333,20 @@ extern "C" int vlb_sumsq_f32(const float* g, long n, float* out, hipStream_t str
   return VLB_OK;
 }
 
-extern "C" int vlb_sumsq_f32_det(const float* g, long n, float* partials, int partials_len, float* out, hipStream_t stream) {
+// out += sum(g^2) in a fixed summation order.  g_is_bf16: a bf16 gradient image (the wire format of the data-parallel exchange: the
+// reduced gradient is consumed as it arrived, no conversion pass back to fp32)
+extern "C" int vlb_sumsq_det(const void* g, int g_is_bf16, long n, float* partials, int partials_len, float* out, hipStream_t stream) {
   if (n <= 0) return VLB_OK;
-  VLB_CHECK_ARG(g && out && partials && partials_len >= 1, "vlb_sumsq_f32_det: null argument");
+  VLB_CHECK_ARG(g && out && partials && partials_len >= 1, "vlb_sumsq_det: null argument");
+  VLB_CHECK_ARG(!g_is_bf16 || ((uintptr_t)g % 8) == 0, "vlb_sumsq_det: gradient must be 8-byte aligned");
   int blocks = grid_for((n + 3) / 4);
   if (blocks > partials_len) blocks = partials_len;
-  hipLaunchKernelGGL(sumsq_partial_kernel<float>, dim3(blocks), dim3(256), 0, stream, g, n, partials);
+  if (!g_is_bf16)
+    hipLaunchKernelGGL(sumsq_partial_kernel<float>, dim3(blocks), dim3(256), 0, stream, (const float*)g, n, partials);
+  else
+    hipLaunchKernelGGL(sumsq_partial_kernel<bf16_t>, dim3(blocks), dim3(256), 0, stream, (const bf16_t*)g, n, partials);
   hipLaunchKernelGGL(sumsq_final_kernel, dim3(1), dim3(256), 0, stream, partials, blocks, out);
-  VLB_CHECK_LAUNCH("vlb_sumsq_f32_det");
-  return VLB_OK;
-}
-
-// the same on a bf16 gradient image (the wire format of the data-parallel exchange: the reduced gradient is consumed as it
-// arrived, no conversion pass back to fp32)
-extern "C" int vlb_sumsq_bf16_det(const void* g, long n, float* partials, int partials_len, float* out, hipStream_t stream) {
-  if (n <= 0) return VLB_OK;
-  VLB_CHECK_ARG(g && out && partials && partials_len >= 1, "vlb_sumsq_bf16_det: null argument");
-  VLB_CHECK_ARG(((uintptr_t)g % 8) == 0, "vlb_sumsq_bf16_det: gradient must be 8-byte aligned");
-  int blocks = grid_for((n + 3) / 4);
-  if (blocks > partials_len) blocks = partials_len;
-  hipLaunchKernelGGL(sumsq_partial_kernel<bf16_t>, dim3(blocks), dim3(256), 0, stream, (const bf16_t*)g, n, partials);
-  hipLaunchKernelGGL(sumsq_final_kernel, dim3(1), dim3(256), 0, stream, partials, blocks, out);
-  VLB_CHECK_LAUNCH("vlb_sumsq_bf16_det");
-  return VLB_OK;
-}
-
-// state: device pointer to 8 floats {lr, beta1, beta2, eps, weight_decay, step, max_norm, sumsq}
-extern "C" int vlb_adamw_step(float* p, const float* g, float* m, float* v, void* p_bf16, long n, float* state, float grad_scale,
-                              hipStream_t stream) {
-  if (n <= 0) return VLB_OK;
-  VLB_CHECK_ARG(p && g && m && v && state, "vlb_adamw_step: null argument");
-  hipLaunchKernelGGL((adamw_kernel<float, false>), dim3(adamw_grid(n)), dim3(256), 0, stream, p, g, m, v, (bf16_t*)p_bf16, n,
-                     (VlbAdamState*)state, grad_scale, (const VlbScaler*)nullptr);
-  hipLaunchKernelGGL(adam_advance_kernel, dim3(1), dim3(1), 0, stream, (VlbAdamState*)state);
-  VLB_CHECK_LAUNCH("vlb_adamw_step");
-  return VLB_OK;
-}
-
-extern "C" int vlb_sgd_momentum_step(float* p, const float* g, float* momentum_buf, void* p_bf16, long n, float lr, float momentum,
-                                     float weight_decay, const float* sumsq, float max_norm, float grad_scale, hipStream_t stream) {
-  if (n <= 0) return VLB_OK;
-  VLB_CHECK_ARG(p && g && momentum_buf, "vlb_sgd_momentum_step: null argument");
-  VLB_CHECK_ARG(momentum >= 0.f && lr >= 0.f && weight_decay >= 0.f, "vlb_sgd_momentum_step: negative hyper-parameter");
-  hipLaunchKernelGGL(sgd_momentum_kernel<false>, dim3(grid_for((n + 3) / 4)), dim3(256), 0, stream, p, g, momentum_buf, (bf16_t*)p_bf16, n, lr,
-                     momentum, weight_decay, sumsq, max_norm, grad_scale, (const VlbScaler*)nullptr);
-  VLB_CHECK_LAUNCH("vlb_sgd_momentum_step");
-  return VLB_OK;
-}
-
-// vlb_adamw_step with the gradient given as a bf16 image (see vlb_sumsq_bf16_det)
-extern "C" int vlb_adamw_step_gbf16(float* p, const void* g_bf16, float* m, float* v, void* p_bf16, long n, float* state,
-                                    float grad_scale, hipStream_t stream) {
-  if (n <= 0) return VLB_OK;
-  VLB_CHECK_ARG(p && g_bf16 && m && v && state, "vlb_adamw_step_gbf16: null argument");
-  VLB_CHECK_ARG(((uintptr_t)g_bf16 % 8) == 0, "vlb_adamw_step_gbf16: gradient must be 8-byte aligned");
-  hipLaunchKernelGGL((adamw_kernel<bf16_t, false>), dim3(adamw_grid(n)), dim3(256), 0, stream, p, (const bf16_t*)g_bf16, m, v,
-                     (bf16_t*)p_bf16, n, (VlbAdamState*)state, grad_scale, (const VlbScaler*)nullptr);
-  hipLaunchKernelGGL(adam_advance_kernel, dim3(1), dim3(1), 0, stream, (VlbAdamState*)state);
-  VLB_CHECK_LAUNCH("vlb_adamw_step_gbf16");
+  VLB_CHECK_LAUNCH("vlb_sumsq_det");
   return VLB_OK;
 }
 
@@ -501,6 +457,17 @@ __global__ __launch_bounds__(256) void adamw_ranges_kernel(float* __restrict__ p
   }
 }
 
+// The compiler lays the instantiations out in the code object in the order in which they are first named.  This list names them in
+// the order they have always had, so that the entry points below can be arranged by what they do without moving a byte of device code.
+[[maybe_unused]] static const void* const kInstantiationOrder[] = {
+    (const void*)adamw_kernel<float, false>,         (const void*)sgd_momentum_kernel<false>,
+    (const void*)adamw_kernel<bf16_t, false>,        (const void*)sumsq_ranges_partial_kernel<bf16_t>,
+    (const void*)sumsq_ranges_partial_kernel<float>, (const void*)adamw_ranges_kernel<bf16_t, false>,
+    (const void*)adamw_ranges_kernel<float, false>,  (const void*)adamw_kernel<bf16_t, true>,
+    (const void*)adamw_kernel<float, true>,          (const void*)adamw_ranges_kernel<bf16_t, true>,
+    (const void*)adamw_ranges_kernel<float, true>,   (const void*)sgd_momentum_kernel<true>,
+    (const void*)lr_schedule_kernel<true>,           (const void*)lr_schedule_kernel<false>};
+
 // out += sum over the ranges of g^2 (fixed summation order; g = the compact reduced-gradient image, fp32 or bf16)
 extern "C" int vlb_sumsq_ranges_det(const void* g, int g_is_bf16, const int64_t* ranges, const int32_t* block_start, int n, int total_blocks,
                                     int chunk, float* partials, int partials_len, float* out, hipStream_t stream) {
@@ -521,47 +488,33 @@ extern "C" int vlb_sumsq_ranges_det(const void* g, int g_is_bf16, const int64_t*
   return VLB_OK;
 }
 
-// AdamW over the ranges (see vlb_adamw_step for the arithmetic); p_bf16_compact (nullable) receives the bf16 copy of the updated
-// parameters at the ranges' g_start offsets; then step += 1 and sumsq = 0.
-extern "C" int vlb_adamw_step_ranges(float* p, const void* g, int g_is_bf16, float* m, float* v, void* p_bf16_compact,
-                                     const int64_t* ranges, const int32_t* block_start, int n, int total_blocks, int chunk, float* state,
-                                     float grad_scale, hipStream_t stream) {
-  VLB_CHECK_ARG(state, "vlb_adamw_step_ranges: null state");
-  if (n > 0 && total_blocks > 0) {
-    VLB_CHECK_ARG(p && g && m && v && ranges && block_start, "vlb_adamw_step_ranges: null argument");
-    VLB_CHECK_ARG(chunk >= 1024 && (chunk % 1024) == 0, "vlb_adamw_step_ranges: chunk must be a positive multiple of 1024");
-    VLB_CHECK_ARG(((uintptr_t)g % 16) == 0 && ((uintptr_t)p % 16) == 0, "vlb_adamw_step_ranges: buffers must be 16-byte aligned");
-    if (g_is_bf16)
-      hipLaunchKernelGGL((adamw_ranges_kernel<bf16_t, false>), dim3(total_blocks), dim3(256), 0, stream, p, (const bf16_t*)g, m, v,
-                         (bf16_t*)p_bf16_compact, (const long*)ranges, (const int*)block_start, n, chunk, (const VlbAdamState*)state, grad_scale,
-                         (const VlbScaler*)nullptr);
+// ------------------------------------------------------------------------------------------------------------------
+// The steps.  state: device pointer to 8 floats {lr, beta1, beta2, eps, weight_decay, step, max_norm, sumsq}.
+// scaler (nullable: device float[9], see VlbScaler) attaches a dynamic loss scaler: the gradient carries the scale; an overflowed step
+// (non-finite sumsq) leaves p / m / v / step alone.  update_scaler != 0: the scaler's rule is applied after the update (0 for all but
+// the last of several flat runs that share one scaler).  Without a scaler an empty run is no step at all; with one it still counts.
+// ------------------------------------------------------------------------------------------------------------------
+extern "C" int vlb_adamw_step(float* p, const void* g, int g_is_bf16, float* m, float* v, void* p_bf16, long n, float* state, float* scaler,
+                              int update_scaler, float grad_scale, hipStream_t stream) {
+  if (!scaler) {
+    if (n <= 0) return VLB_OK;
+    VLB_CHECK_ARG(p && g && m && v && state, "vlb_adamw_step: null argument");
+    VLB_CHECK_ARG(!g_is_bf16 || ((uintptr_t)g % 8) == 0, "vlb_adamw_step: gradient must be 8-byte aligned");
+    if (!g_is_bf16)
+      hipLaunchKernelGGL((adamw_kernel<float, false>), dim3(adamw_grid(n)), dim3(256), 0, stream, p, (const float*)g, m, v, (bf16_t*)p_bf16, n,
+                         (VlbAdamState*)state, grad_scale, (const VlbScaler*)nullptr);
     else
-      hipLaunchKernelGGL((adamw_ranges_kernel<float, false>), dim3(total_blocks), dim3(256), 0, stream, p, (const float*)g, m, v,
-                         (bf16_t*)p_bf16_compact, (const long*)ranges, (const int*)block_start, n, chunk, (const VlbAdamState*)state, grad_scale,
-                         (const VlbScaler*)nullptr);
+      hipLaunchKernelGGL((adamw_kernel<bf16_t, false>), dim3(adamw_grid(n)), dim3(256), 0, stream, p, (const bf16_t*)g, m, v, (bf16_t*)p_bf16, n,
+                         (VlbAdamState*)state, grad_scale, (const VlbScaler*)nullptr);
+    hipLaunchKernelGGL(adam_advance_kernel, dim3(1), dim3(1), 0, stream, (VlbAdamState*)state);
+    VLB_CHECK_LAUNCH("vlb_adamw_step");
+    return VLB_OK;
   }
-  hipLaunchKernelGGL(adam_advance_kernel, dim3(1), dim3(1), 0, stream, (VlbAdamState*)state);
-  VLB_CHECK_LAUNCH("vlb_adamw_step_ranges");
-  return VLB_OK;
-}
-
-// ------------------------------------------------------------------------------------------------------------------
-// The same steps with a dynamic loss scaler attached (scaler: device float[9], see VlbScaler).  The gradient carries the scale; an
-// overflowed step (non-finite sumsq) leaves p / m / v / step alone.  update_scaler != 0: the scaler's rule is applied after the update
-// (0 for all but the last of several flat runs that share one scaler).
-// ------------------------------------------------------------------------------------------------------------------
-static int check_scaler_arg(const float* scaler, const char* who) {
-  VLB_CHECK_ARG(scaler && ((uintptr_t)scaler % 4) == 0, "%s: null or misaligned scaler", who);
-  return VLB_OK;
-}
-
-extern "C" int vlb_adamw_step_scaled(float* p, const void* g, int g_is_bf16, float* m, float* v, void* p_bf16, long n, float* state,
-                                     float* scaler, int update_scaler, float grad_scale, hipStream_t stream) {
-  VLB_CHECK_ARG(state, "vlb_adamw_step_scaled: null state");
-  if (check_scaler_arg(scaler, "vlb_adamw_step_scaled") != VLB_OK) return VLB_ERR_ARG;
+  VLB_CHECK_ARG(state, "vlb_adamw_step: null state");
+  VLB_CHECK_ARG(((uintptr_t)scaler % 4) == 0, "vlb_adamw_step: misaligned scaler");
   if (n > 0) {
-    VLB_CHECK_ARG(p && g && m && v, "vlb_adamw_step_scaled: null argument");
-    VLB_CHECK_ARG(!g_is_bf16 || ((uintptr_t)g % 8) == 0, "vlb_adamw_step_scaled: gradient must be 8-byte aligned");
+    VLB_CHECK_ARG(p && g && m && v, "vlb_adamw_step: null argument");
+    VLB_CHECK_ARG(!g_is_bf16 || ((uintptr_t)g % 8) == 0, "vlb_adamw_step: gradient must be 8-byte aligned");
     if (g_is_bf16)
       hipLaunchKernelGGL((adamw_kernel<bf16_t, true>), dim3(adamw_grid(n)), dim3(256), 0, stream, p, (const bf16_t*)g, m, v, (bf16_t*)p_bf16, n,
                          (VlbAdamState*)state, grad_scale, (const VlbScaler*)scaler);
@@ -571,20 +524,30 @@ extern "C" int vlb_adamw_step_scaled(float* p, const void* g, int g_is_bf16, flo
   }
   hipLaunchKernelGGL(scaler_advance_kernel, dim3(1), dim3(1), 0, stream, (VlbAdamState*)state, (const float*)(state + 7), (VlbScaler*)scaler,
                      update_scaler);
-  VLB_CHECK_LAUNCH("vlb_adamw_step_scaled");
+  VLB_CHECK_LAUNCH("vlb_adamw_step");
   return VLB_OK;
 }
 
-extern "C" int vlb_adamw_step_ranges_scaled(float* p, const void* g, int g_is_bf16, float* m, float* v, void* p_bf16_compact,
-                                            const int64_t* ranges, const int32_t* block_start, int n, int total_blocks, int chunk,
-                                            float* state, float* scaler, float grad_scale, hipStream_t stream) {
-  VLB_CHECK_ARG(state, "vlb_adamw_step_ranges_scaled: null state");
-  if (check_scaler_arg(scaler, "vlb_adamw_step_ranges_scaled") != VLB_OK) return VLB_ERR_ARG;
+// AdamW over the ranges (see vlb_adamw_step for the arithmetic); p_bf16_compact (nullable) receives the bf16 copy of the updated
+// parameters at the ranges' g_start offsets; then step += 1 and sumsq = 0 -- with a scaler, its rule -- also for a rank that owns nothing.
+extern "C" int vlb_adamw_step_ranges(float* p, const void* g, int g_is_bf16, float* m, float* v, void* p_bf16_compact,
+                                     const int64_t* ranges, const int32_t* block_start, int n, int total_blocks, int chunk, float* state,
+                                     float* scaler, float grad_scale, hipStream_t stream) {
+  VLB_CHECK_ARG(state, "vlb_adamw_step_ranges: null state");
+  VLB_CHECK_ARG(((uintptr_t)scaler % 4) == 0, "vlb_adamw_step_ranges: misaligned scaler");
   if (n > 0 && total_blocks > 0) {
-    VLB_CHECK_ARG(p && g && m && v && ranges && block_start, "vlb_adamw_step_ranges_scaled: null argument");
-    VLB_CHECK_ARG(chunk >= 1024 && (chunk % 1024) == 0, "vlb_adamw_step_ranges_scaled: chunk must be a positive multiple of 1024");
-    VLB_CHECK_ARG(((uintptr_t)g % 16) == 0 && ((uintptr_t)p % 16) == 0, "vlb_adamw_step_ranges_scaled: buffers must be 16-byte aligned");
-    if (g_is_bf16)
+    VLB_CHECK_ARG(p && g && m && v && ranges && block_start, "vlb_adamw_step_ranges: null argument");
+    VLB_CHECK_ARG(chunk >= 1024 && (chunk % 1024) == 0, "vlb_adamw_step_ranges: chunk must be a positive multiple of 1024");
+    VLB_CHECK_ARG(((uintptr_t)g % 16) == 0 && ((uintptr_t)p % 16) == 0, "vlb_adamw_step_ranges: buffers must be 16-byte aligned");
+    if (!scaler && g_is_bf16)
+      hipLaunchKernelGGL((adamw_ranges_kernel<bf16_t, false>), dim3(total_blocks), dim3(256), 0, stream, p, (const bf16_t*)g, m, v,
+                         (bf16_t*)p_bf16_compact, (const long*)ranges, (const int*)block_start, n, chunk, (const VlbAdamState*)state, grad_scale,
+                         (const VlbScaler*)nullptr);
+    else if (!scaler)
+      hipLaunchKernelGGL((adamw_ranges_kernel<float, false>), dim3(total_blocks), dim3(256), 0, stream, p, (const float*)g, m, v,
+                         (bf16_t*)p_bf16_compact, (const long*)ranges, (const int*)block_start, n, chunk, (const VlbAdamState*)state, grad_scale,
+                         (const VlbScaler*)nullptr);
+    else if (g_is_bf16)
       hipLaunchKernelGGL((adamw_ranges_kernel<bf16_t, true>), dim3(total_blocks), dim3(256), 0, stream, p, (const bf16_t*)g, m, v,
                          (bf16_t*)p_bf16_compact, (const long*)ranges, (const int*)block_start, n, chunk, (const VlbAdamState*)state, grad_scale,
                          (const VlbScaler*)scaler);
@@ -593,46 +556,52 @@ extern "C" int vlb_adamw_step_ranges_scaled(float* p, const void* g, int g_is_bf
                          (bf16_t*)p_bf16_compact, (const long*)ranges, (const int*)block_start, n, chunk, (const VlbAdamState*)state, grad_scale,
                          (const VlbScaler*)scaler);
   }
-  hipLaunchKernelGGL(scaler_advance_kernel, dim3(1), dim3(1), 0, stream, (VlbAdamState*)state, (const float*)(state + 7), (VlbScaler*)scaler, 1);
-  VLB_CHECK_LAUNCH("vlb_adamw_step_ranges_scaled");
+  if (scaler)
+    hipLaunchKernelGGL(scaler_advance_kernel, dim3(1), dim3(1), 0, stream, (VlbAdamState*)state, (const float*)(state + 7), (VlbScaler*)scaler, 1);
+  else
+    hipLaunchKernelGGL(adam_advance_kernel, dim3(1), dim3(1), 0, stream, (VlbAdamState*)state);
+  VLB_CHECK_LAUNCH("vlb_adamw_step_ranges");
   return VLB_OK;
 }
 
-// sumsq is required (it carries the overflow decision) and is left as it is: the caller owns it
-extern "C" int vlb_sgd_momentum_step_scaled(float* p, const float* g, float* momentum_buf, void* p_bf16, long n, float lr, float momentum,
-                                            float weight_decay, const float* sumsq, float max_norm, float grad_scale, float* scaler,
-                                            int update_scaler, hipStream_t stream) {
-  VLB_CHECK_ARG(sumsq, "vlb_sgd_momentum_step_scaled: the squared gradient norm is required");
-  if (check_scaler_arg(scaler, "vlb_sgd_momentum_step_scaled") != VLB_OK) return VLB_ERR_ARG;
-  VLB_CHECK_ARG(momentum >= 0.f && lr >= 0.f && weight_decay >= 0.f, "vlb_sgd_momentum_step_scaled: negative hyper-parameter");
+// with a scaler, sumsq is required (it carries the overflow decision) and is left as it is: the caller owns it
+extern "C" int vlb_sgd_momentum_step(float* p, const float* g, float* momentum_buf, void* p_bf16, long n, float lr, float momentum,
+                                     float weight_decay, const float* sumsq, float max_norm, float grad_scale, float* scaler,
+                                     int update_scaler, hipStream_t stream) {
+  if (!scaler) {
+    if (n <= 0) return VLB_OK;
+    VLB_CHECK_ARG(p && g && momentum_buf, "vlb_sgd_momentum_step: null argument");
+    VLB_CHECK_ARG(momentum >= 0.f && lr >= 0.f && weight_decay >= 0.f, "vlb_sgd_momentum_step: negative hyper-parameter");
+    hipLaunchKernelGGL(sgd_momentum_kernel<false>, dim3(grid_for((n + 3) / 4)), dim3(256), 0, stream, p, g, momentum_buf, (bf16_t*)p_bf16, n,
+                       lr, momentum, weight_decay, sumsq, max_norm, grad_scale, (const VlbScaler*)nullptr);
+    VLB_CHECK_LAUNCH("vlb_sgd_momentum_step");
+    return VLB_OK;
+  }
+  VLB_CHECK_ARG(sumsq, "vlb_sgd_momentum_step: the squared gradient norm is required");
+  VLB_CHECK_ARG(((uintptr_t)scaler % 4) == 0, "vlb_sgd_momentum_step: misaligned scaler");
+  VLB_CHECK_ARG(momentum >= 0.f && lr >= 0.f && weight_decay >= 0.f, "vlb_sgd_momentum_step: negative hyper-parameter");
   if (n > 0) {
-    VLB_CHECK_ARG(p && g && momentum_buf, "vlb_sgd_momentum_step_scaled: null argument");
+    VLB_CHECK_ARG(p && g && momentum_buf, "vlb_sgd_momentum_step: null argument");
     hipLaunchKernelGGL(sgd_momentum_kernel<true>, dim3(grid_for((n + 3) / 4)), dim3(256), 0, stream, p, g, momentum_buf, (bf16_t*)p_bf16, n,
                        lr, momentum, weight_decay, sumsq, max_norm, grad_scale, (const VlbScaler*)scaler);
   }
   if (update_scaler)
     hipLaunchKernelGGL(scaler_advance_kernel, dim3(1), dim3(1), 0, stream, (VlbAdamState*)nullptr, sumsq, (VlbScaler*)scaler, 1);
-  VLB_CHECK_LAUNCH("vlb_sgd_momentum_step_scaled");
+  VLB_CHECK_LAUNCH("vlb_sgd_momentum_step");
   return VLB_OK;
 }
 
-extern "C" int vlb_lr_schedule_step_scaled(float* state, const float* scaler, int kind, float base_lr, float warmup_steps, float t_total,
-                                           hipStream_t stream) {
-  VLB_CHECK_ARG(state && scaler, "vlb_lr_schedule_step_scaled: null state / scaler");
-  VLB_CHECK_ARG(kind >= 0 && kind <= 2, "vlb_lr_schedule_step_scaled: kind must be 0 (constant), 1 (warmup-constant) or 2 (warmup-linear)");
-  VLB_CHECK_ARG(base_lr >= 0.f && warmup_steps >= 0.f, "vlb_lr_schedule_step_scaled: negative base_lr / warmup_steps");
-  hipLaunchKernelGGL(lr_schedule_kernel<true>, dim3(1), dim3(1), 0, stream, (VlbAdamState*)state, kind, base_lr, warmup_steps, t_total,
-                     (const VlbScaler*)scaler);
-  VLB_CHECK_LAUNCH("vlb_lr_schedule_step_scaled");
-  return VLB_OK;
-}
-
-extern "C" int vlb_lr_schedule_step(float* state, int kind, float base_lr, float warmup_steps, float t_total, hipStream_t stream) {
+extern "C" int vlb_lr_schedule_step(float* state, const float* scaler, int kind, float base_lr, float warmup_steps, float t_total,
+                                    hipStream_t stream) {
   VLB_CHECK_ARG(state, "vlb_lr_schedule_step: null state");
   VLB_CHECK_ARG(kind >= 0 && kind <= 2, "vlb_lr_schedule_step: kind must be 0 (constant), 1 (warmup-constant) or 2 (warmup-linear)");
   VLB_CHECK_ARG(base_lr >= 0.f && warmup_steps >= 0.f, "vlb_lr_schedule_step: negative base_lr / warmup_steps");
-  hipLaunchKernelGGL(lr_schedule_kernel<false>, dim3(1), dim3(1), 0, stream, (VlbAdamState*)state, kind, base_lr, warmup_steps, t_total,
-                     (const VlbScaler*)nullptr);
+  if (scaler)
+    hipLaunchKernelGGL(lr_schedule_kernel<true>, dim3(1), dim3(1), 0, stream, (VlbAdamState*)state, kind, base_lr, warmup_steps, t_total,
+                       (const VlbScaler*)scaler);
+  else
+    hipLaunchKernelGGL(lr_schedule_kernel<false>, dim3(1), dim3(1), 0, stream, (VlbAdamState*)state, kind, base_lr, warmup_steps, t_total,
+                       (const VlbScaler*)nullptr);
   VLB_CHECK_LAUNCH("vlb_lr_schedule_step");
   return VLB_OK;
 }

@@ -399,19 +399,10 @@ def mul_bf16(a, b, out):
 
 def ce_fwd_bwd(logits, V, labels, counts, loss_out, gscale=1.0, logits_copy=None, dscale=None, acc=None):
     """dscale (fp32 device scalar, e.g. the scale slot of a loss scaler): the gradient scale is gscale * dscale, formed on the device.
-    acc (int64 [2], training-time metrics): += [rows whose argmax is the label, rows with a label in [0, V)] (vlb_ce_fwd_bwd_acc)."""
-    rows = logits.shape[0]
-    if acc is not None:
-        _lib.call("vlb_ce_fwd_bwd_acc", _p(logits, BF16), _ld(logits), rows, V, _p(labels, torch.int64), _p(counts, torch.float32),
-                  float(gscale), _p(dscale, torch.float32), _p(loss_out, torch.float32), _p(logits_copy, BF16), _ld(logits_copy),
-                  _p(acc, torch.int64), _stream())
-        return
-    if dscale is not None:
-        _lib.call("vlb_ce_fwd_bwd_ds", _p(logits, BF16), _ld(logits), rows, V, _p(labels, torch.int64), _p(counts, torch.float32),
-                  float(gscale), _p(dscale, torch.float32), _p(loss_out, torch.float32), _p(logits_copy, BF16), _ld(logits_copy), _stream())
-        return
-    _lib.call("vlb_ce_fwd_bwd", _p(logits, BF16), _ld(logits), rows, V, _p(labels, torch.int64), _p(counts, torch.float32),
-              float(gscale), _p(loss_out, torch.float32), _p(logits_copy, BF16), _ld(logits_copy), _stream())
+    acc (int64 [2], training-time metrics): += [rows whose argmax is the label, rows with a label in [0, V)] (vlb_ce_fwd_bwd)."""
+    _lib.call("vlb_ce_fwd_bwd", _p(logits, BF16), _ld(logits), logits.shape[0], V, _p(labels, torch.int64), _p(counts, torch.float32),
+              float(gscale), _p(dscale, torch.float32), _p(loss_out, torch.float32), _p(logits_copy, BF16), _ld(logits_copy),
+              _p(acc, torch.int64), _stream())
 
 
 def mlm_compact(labels, src_rows, n_split, V, sel_pos, sel_src, labels_c, count0, count1, overflow):
@@ -422,22 +413,12 @@ def mlm_compact(labels, src_rows, n_split, V, sel_pos, sel_src, labels_c, count0
 
 
 def ce_fwd_bwd_compact(logits, V, labels_c, count0, count1, loss_out0, loss_out1, gscale=1.0, dscale=None, acc=None, acc1=None):
-    """acc / acc1 (int64 [2] each, both or neither): += [hits, counted rows] of group 0 / group 1 (vlb_ce_fwd_bwd_compact_acc)."""
-    if acc is not None or acc1 is not None:
-        if acc is None or acc1 is None:
-            raise ValueError("ce_fwd_bwd_compact: acc and acc1 go together (one counter pair per group)")
-        _lib.call("vlb_ce_fwd_bwd_compact_acc", _p(logits, BF16), _ld(logits), logits.shape[0], V, _p(labels_c, torch.int64),
-                  _p(count0, torch.float32), _p(count1, torch.float32), float(gscale), _p(dscale, torch.float32),
-                  _p(loss_out0, torch.float32), _p(loss_out1, torch.float32), _p(acc, torch.int64), _p(acc1, torch.int64), _stream())
-        return
-    if dscale is not None:
-        _lib.call("vlb_ce_fwd_bwd_compact_ds", _p(logits, BF16), _ld(logits), logits.shape[0], V, _p(labels_c, torch.int64),
-                  _p(count0, torch.float32), _p(count1, torch.float32), float(gscale), _p(dscale, torch.float32),
-                  _p(loss_out0, torch.float32), _p(loss_out1, torch.float32), _stream())
-        return
+    """acc / acc1 (int64 [2] each, both or neither): += [hits, counted rows] of group 0 / group 1 (vlb_ce_fwd_bwd_compact)."""
+    if (acc is None) != (acc1 is None):
+        raise ValueError("ce_fwd_bwd_compact: acc and acc1 go together (one counter pair per group)")
     _lib.call("vlb_ce_fwd_bwd_compact", _p(logits, BF16), _ld(logits), logits.shape[0], V, _p(labels_c, torch.int64),
-              _p(count0, torch.float32), _p(count1, torch.float32), float(gscale), _p(loss_out0, torch.float32),
-              _p(loss_out1, torch.float32), _stream())
+              _p(count0, torch.float32), _p(count1, torch.float32), float(gscale), _p(dscale, torch.float32),
+              _p(loss_out0, torch.float32), _p(loss_out1, torch.float32), _p(acc, torch.int64), _p(acc1, torch.int64), _stream())
 
 
 def scatter_rows(src, idx, out):
@@ -446,21 +427,10 @@ def scatter_rows(src, idx, out):
 
 
 def soft_ce_fwd_bwd(logits, C, target, tsum, counts, loss_out, gscale=1.0, logits_copy=None, dscale=None, acc=None):
-    """acc (int64 [2]): += [valid rows with argmax(logits) == argmax(target), valid rows] (vlb_soft_ce_fwd_bwd_acc)."""
-    rows = logits.shape[0]
-    if acc is not None:
-        _lib.call("vlb_soft_ce_fwd_bwd_acc", _p(logits, BF16), _ld(logits), rows, C, _p(target, torch.float32), _ld(target),
-                  _p(tsum, torch.float32), _p(counts, torch.float32), float(gscale), _p(dscale, torch.float32),
-                  _p(loss_out, torch.float32), _p(logits_copy, BF16), _ld(logits_copy), _p(acc, torch.int64), _stream())
-        return
-    if dscale is not None:
-        _lib.call("vlb_soft_ce_fwd_bwd_ds", _p(logits, BF16), _ld(logits), rows, C, _p(target, torch.float32), _ld(target),
-                  _p(tsum, torch.float32), _p(counts, torch.float32), float(gscale), _p(dscale, torch.float32),
-                  _p(loss_out, torch.float32), _p(logits_copy, BF16), _ld(logits_copy), _stream())
-        return
-    _lib.call("vlb_soft_ce_fwd_bwd", _p(logits, BF16), _ld(logits), rows, C, _p(target, torch.float32), _ld(target),
-              _p(tsum, torch.float32), _p(counts, torch.float32), float(gscale), _p(loss_out, torch.float32),
-              _p(logits_copy, BF16), _ld(logits_copy), _stream())
+    """acc (int64 [2]): += [valid rows with argmax(logits) == argmax(target), valid rows] (vlb_soft_ce_fwd_bwd)."""
+    _lib.call("vlb_soft_ce_fwd_bwd", _p(logits, BF16), _ld(logits), logits.shape[0], C, _p(target, torch.float32), _ld(target),
+              _p(tsum, torch.float32), _p(counts, torch.float32), float(gscale), _p(dscale, torch.float32),
+              _p(loss_out, torch.float32), _p(logits_copy, BF16), _ld(logits_copy), _p(acc, torch.int64), _stream())
 
 
 def ce_eval(logits, V, labels, loss_out, acc, count0=None, count1=None, loss_out1=None, acc1=None, pred=None):
@@ -523,14 +493,8 @@ def joint_hits(pred_a, label_a, pred_r, label_r, acc):
 def bce_logits_fwd_bwd(logits, A, label, loss_out, gscale=1.0, logits_copy=None, pos_weight=1.0, dscale=None):
     """logits bf16 [rows, >=A] <- gscale * w * (sigmoid(x) - y) / rows in place; loss_out += BCE-with-logits * A (reference convention);
     w = pos_weight on the positive labels (VCR), 1 elsewhere.  dscale: fp32 device scalar multiplied into gscale on the device."""
-    rows = logits.shape[0]
-    if dscale is not None:
-        _lib.call("vlb_bce_logits_fwd_bwd_ds", _p(logits, BF16), _ld(logits), rows, A, _p(label, torch.float32), _ld(label), float(gscale),
-                  _p(dscale, torch.float32), float(pos_weight), _p(loss_out, torch.float32), _p(logits_copy, BF16), _ld(logits_copy),
-                  _stream())
-        return
-    _lib.call("vlb_bce_logits_fwd_bwd", _p(logits, BF16), _ld(logits), rows, A, _p(label, torch.float32), _ld(label), float(gscale),
-              float(pos_weight), _p(loss_out, torch.float32), _p(logits_copy, BF16), _ld(logits_copy), _stream())
+    _lib.call("vlb_bce_logits_fwd_bwd", _p(logits, BF16), _ld(logits), logits.shape[0], A, _p(label, torch.float32), _ld(label), float(gscale),
+              _p(dscale, torch.float32), float(pos_weight), _p(loss_out, torch.float32), _p(logits_copy, BF16), _ld(logits_copy), _stream())
 
 
 def _aligned(t):
@@ -589,41 +553,27 @@ def sumsq(g, out):
 
 def sumsq_det(g, partials, out):
     """out += sum(g^2) with a fixed summation order (same bits on every data-parallel rank); g fp32, or the bf16 wire image."""
-    if g.dtype == BF16:
-        _lib.call("vlb_sumsq_bf16_det", _p(g, BF16), g.numel(), _p(partials, torch.float32), partials.numel(), _p(out, torch.float32),
-                  _stream())
-        return
-    _lib.call("vlb_sumsq_f32_det", _p(g, torch.float32), g.numel(), _p(partials, torch.float32), partials.numel(), _p(out, torch.float32),
-              _stream())
+    bf16 = g.dtype == BF16
+    _lib.call("vlb_sumsq_det", _p(g, BF16 if bf16 else torch.float32), 1 if bf16 else 0, g.numel(), _p(partials, torch.float32),
+              partials.numel(), _p(out, torch.float32), _stream())
 
 
 def adamw_step(p, g, m, v, p16, state, grad_scale=1.0, scaler=None, update_scaler=True):
     """scaler (fp32 device [SCALER_FLOATS], loss_scale.py): the gradient carries the dynamic loss scale; an overflowed step is skipped on
-    the device and the scaler's rule applied after the update (vlb_adamw_step_scaled)."""
-    if scaler is not None:
-        _lib.call("vlb_adamw_step_scaled", _p(p, torch.float32), _p(g), 1 if g.dtype == BF16 else 0, _p(m, torch.float32),
-                  _p(v, torch.float32), _p(p16, BF16), p.numel(), _p(state, torch.float32), _scaler_p(scaler), 1 if update_scaler else 0,
-                  float(grad_scale), _stream())
-        return
-    if g.dtype == BF16:
-        _lib.call("vlb_adamw_step_gbf16", _p(p, torch.float32), _p(g, BF16), _p(m, torch.float32), _p(v, torch.float32),
-                  _p(p16, BF16), p.numel(), _p(state, torch.float32), float(grad_scale), _stream())
-        return
-    _lib.call("vlb_adamw_step", _p(p, torch.float32), _p(g, torch.float32), _p(m, torch.float32), _p(v, torch.float32),
-              _p(p16, BF16), p.numel(), _p(state, torch.float32), float(grad_scale), _stream())
+    the device and the scaler's rule applied after the update.  g: fp32, or the bf16 wire image."""
+    bf16 = g.dtype == BF16
+    _lib.call("vlb_adamw_step", _p(p, torch.float32), _p(g, BF16 if bf16 else torch.float32), 1 if bf16 else 0, _p(m, torch.float32),
+              _p(v, torch.float32), _p(p16, BF16), p.numel(), _p(state, torch.float32), _scaler_p(scaler), 1 if update_scaler else 0,
+              float(grad_scale), _stream())
 
 
 def sgd_momentum_step(p, g, buf, lr, momentum=0.9, weight_decay=0.0, p16=None, sumsq=None, max_norm=0.0, grad_scale=1.0, scaler=None,
                       update_scaler=True):
     """torch.optim.SGD(lr, momentum, weight_decay) on flat fp32 tensors (vlb_sgd_momentum_step); sumsq: device scalar for the clip.
     scaler: dynamic loss scaler (see adamw_step); sumsq is then required."""
-    if scaler is not None:
-        _lib.call("vlb_sgd_momentum_step_scaled", _p(p, torch.float32), _p(g, torch.float32), _p(buf, torch.float32), _p(p16, BF16),
-                  p.numel(), float(lr), float(momentum), float(weight_decay), _p(sumsq, torch.float32), float(max_norm), float(grad_scale),
-                  _scaler_p(scaler), 1 if update_scaler else 0, _stream())
-        return
     _lib.call("vlb_sgd_momentum_step", _p(p, torch.float32), _p(g, torch.float32), _p(buf, torch.float32), _p(p16, BF16), p.numel(),
-              float(lr), float(momentum), float(weight_decay), _p(sumsq, torch.float32), float(max_norm), float(grad_scale), _stream())
+              float(lr), float(momentum), float(weight_decay), _p(sumsq, torch.float32), float(max_norm), float(grad_scale),
+              _scaler_p(scaler), 1 if update_scaler else 0, _stream())
 
 
 LR_CONSTANT, LR_WARMUP_CONSTANT, LR_WARMUP_LINEAR = 0, 1, 2
@@ -631,6 +581,8 @@ SCALER_FLOATS = 9      # include/vlbert_hip.h: VLB_SCALER_*
 
 
 def _scaler_p(scaler):
+    if scaler is None:
+        return None
     if scaler.numel() < SCALER_FLOATS or not scaler.is_contiguous():
         raise RuntimeError("loss scaler: expected %d contiguous fp32 values" % SCALER_FLOATS)
     return _p(scaler, torch.float32)
@@ -639,12 +591,8 @@ def _scaler_p(scaler):
 def lr_schedule_step(state, kind, base_lr, warmup_steps=0, t_total=0, scaler=None):
     """state[0] = base_lr * lambda(steps_taken + 1) on the device (common/nlp/bert/optimization.py:27-62); with a loss scaler the
     skipped steps count too (the reference's scheduler steps on every iteration)."""
-    if scaler is not None:
-        _lib.call("vlb_lr_schedule_step_scaled", _p(state, torch.float32), _scaler_p(scaler), int(kind), float(base_lr),
-                  float(warmup_steps), float(t_total), _stream())
-        return
-    _lib.call("vlb_lr_schedule_step", _p(state, torch.float32), int(kind), float(base_lr), float(warmup_steps), float(t_total),
-              _stream())
+    _lib.call("vlb_lr_schedule_step", _p(state, torch.float32), _scaler_p(scaler), int(kind), float(base_lr), float(warmup_steps),
+              float(t_total), _stream())
 
 
 def scale_f32(x, alpha):
@@ -873,14 +821,9 @@ class ShardRanges:
                   self.total_blocks, self.chunk, _p(partials, torch.float32), partials.numel(), _p(out, torch.float32), _stream())
 
     def adamw(self, p, g, m, v, p16c, state, grad_scale=1.0, scaler=None):
-        if scaler is not None:
-            _lib.call("vlb_adamw_step_ranges_scaled", _p(p, torch.float32), _p(g), 1 if g.dtype == BF16 else 0, _p(m, torch.float32),
-                      _p(v, torch.float32), _p(p16c, BF16), self.ranges.data_ptr(), self.starts.data_ptr(), self.n, self.total_blocks,
-                      self.chunk, _p(state, torch.float32), _scaler_p(scaler), float(grad_scale), _stream())
-            return
         _lib.call("vlb_adamw_step_ranges", _p(p, torch.float32), _p(g), 1 if g.dtype == BF16 else 0, _p(m, torch.float32),
                   _p(v, torch.float32), _p(p16c, BF16), self.ranges.data_ptr(), self.starts.data_ptr(), self.n, self.total_blocks,
-                  self.chunk, _p(state, torch.float32), float(grad_scale), _stream())
+                  self.chunk, _p(state, torch.float32), _scaler_p(scaler), float(grad_scale), _stream())
 
 
 # ---------------------------------------------------------------------------------------------------------------
@@ -1090,39 +1033,29 @@ def _row_loss(logits, row_loss):
 
 def ce_f32_fwd_bwd(logits, V, labels, counts, loss_out, gscale=1.0, logits_copy=None, row_loss=None, acc=None, dscale=None):
     """ce_fwd_bwd on fp32 logits [rows, ld % 4 == 0]; the rows' losses go through `row_loss` (scratch, allocated when not given) and
-    are added in a fixed order: the same bits on every run.  acc (int64 [2]): += [hits, counted rows] (the *_acc entry points, which
-    also take a device scale `dscale`)."""
-    row_loss = _row_loss(logits, row_loss)
-    if acc is not None:
-        _lib.call("vlb_ce_f32_fwd_bwd_acc", _pf(logits), _ld(logits), logits.shape[0], V, _p(labels, torch.int64), _pf(counts), float(gscale),
-                  _pf(dscale), _pf(loss_out), _pf(row_loss), _pf(logits_copy), _ld(logits_copy), _p(acc, torch.int64), _stream())
-        return
-    assert dscale is None, "ce_f32_fwd_bwd: dscale comes with acc (vlb_ce_f32_fwd_bwd_acc)"
+    are added in a fixed order: the same bits on every run.  acc (int64 [2]): += [hits, counted rows]; a device scale `dscale` comes
+    with acc only (the kernels without the counters take none)."""
+    if dscale is not None and acc is None:
+        raise ValueError("ce_f32_fwd_bwd: dscale comes with acc")
     _lib.call("vlb_ce_f32_fwd_bwd", _pf(logits), _ld(logits), logits.shape[0], V, _p(labels, torch.int64), _pf(counts), float(gscale),
-              _pf(loss_out), _pf(row_loss), _pf(logits_copy), _ld(logits_copy), _stream())
+              _pf(dscale), _pf(loss_out), _pf(_row_loss(logits, row_loss)), _pf(logits_copy), _ld(logits_copy), _p(acc, torch.int64),
+              _stream())
 
 
 def ce_f32_fwd_bwd_compact(logits, V, labels_c, count0, count1, loss_out0, loss_out1, gscale=1.0, row_loss=None, acc=None, acc1=None,
                            dscale=None):
-    row_loss = _row_loss(logits, row_loss)
-    if acc is not None or acc1 is not None:
-        if acc is None or acc1 is None:
-            raise ValueError("ce_f32_fwd_bwd_compact: acc and acc1 go together (one counter pair per group)")
-        _lib.call("vlb_ce_f32_fwd_bwd_compact_acc", _pf(logits), _ld(logits), logits.shape[0], V, _p(labels_c, torch.int64), _pf(count0),
-                  _pf(count1), float(gscale), _pf(dscale), _pf(loss_out0), _pf(loss_out1), _pf(row_loss), _p(acc, torch.int64),
-                  _p(acc1, torch.int64), _stream())
-        return
-    assert dscale is None, "ce_f32_fwd_bwd_compact: dscale comes with acc / acc1"
+    if (acc is None) != (acc1 is None):
+        raise ValueError("ce_f32_fwd_bwd_compact: acc and acc1 go together (one counter pair per group)")
+    if dscale is not None and acc is None:
+        raise ValueError("ce_f32_fwd_bwd_compact: dscale comes with acc / acc1")
     _lib.call("vlb_ce_f32_fwd_bwd_compact", _pf(logits), _ld(logits), logits.shape[0], V, _p(labels_c, torch.int64), _pf(count0),
-              _pf(count1), float(gscale), _pf(loss_out0), _pf(loss_out1), _pf(row_loss), _stream())
+              _pf(count1), float(gscale), _pf(dscale), _pf(loss_out0), _pf(loss_out1), _pf(_row_loss(logits, row_loss)),
+              _p(acc, torch.int64), _p(acc1, torch.int64), _stream())
 
 
 def soft_ce_f32_fwd_bwd(logits, C, target, tsum, counts, loss_out, gscale=1.0, logits_copy=None, row_loss=None, acc=None, dscale=None):
-    row_loss = _row_loss(logits, row_loss)
-    if acc is not None:
-        _lib.call("vlb_soft_ce_f32_fwd_bwd_acc", _pf(logits), _ld(logits), logits.shape[0], C, _pf(target), _ld(target), _pf(tsum), _pf(counts),
-                  float(gscale), _pf(dscale), _pf(loss_out), _pf(row_loss), _pf(logits_copy), _ld(logits_copy), _p(acc, torch.int64), _stream())
-        return
-    assert dscale is None, "soft_ce_f32_fwd_bwd: dscale comes with acc"
+    if dscale is not None and acc is None:
+        raise ValueError("soft_ce_f32_fwd_bwd: dscale comes with acc")
     _lib.call("vlb_soft_ce_f32_fwd_bwd", _pf(logits), _ld(logits), logits.shape[0], C, _pf(target), _ld(target), _pf(tsum), _pf(counts),
-              float(gscale), _pf(loss_out), _pf(row_loss), _pf(logits_copy), _ld(logits_copy), _stream())
+              float(gscale), _pf(dscale), _pf(loss_out), _pf(_row_loss(logits, row_loss)), _pf(logits_copy), _ld(logits_copy),
+              _p(acc, torch.int64), _stream())

@@ -29,7 +29,7 @@ Two exchange modes (VLB_DP_MODE, default "sharded" when the buffer can be cut ev
 Wire format: bf16 by default up to 8 ranks (VLB_DP_WIRE=fp32 keeps fp32; above 8 ranks the default is fp32 -- a bf16 running sum
 over many ranks is not validated, tests/test_parallel_cpu.py bounds the 8-rank case against the fp32 sum).  Each bucket is converted
 into its slice of ONE persistent flat bf16 image right when it becomes ready (a 16 B/lane HIP cast, ~20 us per 64 MB bucket, under
-the rest of backward), RCCL reduces that slice, and the optimizer (vlb_sumsq_*_det / vlb_adamw_step_*) consumes the reduced image as
+the rest of backward), RCCL reduces that slice, and the optimizer (vlb_sumsq_det / vlb_adamw_step with g_is_bf16) consumes the reduced image as
 it arrived: half the bytes on every xGMI link and no conversion pass back to fp32.  Every rank receives the same reduced bits, so
 replicas stay bit-identical.  The tied word-embedding gradient (94 MB fp32: decoder wgrad + embedding scatter-add) completes last
 and cannot overlap; it is its own bucket ("word_emb"), launched right after the embedding backward, in front of the remaining
