@@ -57,8 +57,8 @@ def test_fp32_full_check_is_static_and_has_eval_step_refusal():
     E.PretrainEngine._check_fp32_full(E.ModelConfig(), 64, 36, False, True, None, "allreduce", 0, None)      # the supported call: silent
     E.PretrainEngine._check_fp32_full(E.ModelConfig(), 64, 36, False, True, None, "allreduce", 0, 1.0)
 
-    class Stub:
-        core, fp32_full = False, True
+    class Stub:      # the refusal is the fp32 heads' (the engine's `back` under fp32_full), asked before anything runs
+        core, back = False, object.__new__(pkg("pretrain_f32").PretrainF32)
     with pytest.raises(ValueError, match="eval_step: not built for an fp32_full engine"):
         E.PretrainEngine.eval_step(Stub())
 

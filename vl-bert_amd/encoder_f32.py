@@ -11,9 +11,10 @@ Where the precision boundary lies: the embedding side and the heads stay on the 
 VLB_PRECISION=f16: 2^-12 per rounding, a handful of roundings in total); `forward` takes the embedding output X[0] up to fp32,
 `backward` hands the 16-bit d X[0] back.  The 24 (12) layers in between -- where rounding error accumulates with depth, 10 operand
 roundings per layer in a 16-bit build -- see none.  Measured: tests/test_f32_encoder_gpu.py.
-With the engine's `fp32_ends` the boundary is gone on the VQA fine-tuning route: the fused fp32 embedding (csrc/f32_ends.hip) writes
-X[0] here, the caller reads X[L] and hands an fp32 d X[L] in, and `forward` / `backward` skip their casts (tests/test_fp32_ends_gpu.py).
-The engine's `fp32_full` does the same for the pre-training step (pretrain_f32.py writes X[0], its heads read X[L]).
+The three 16-bit boundary buffers (X[0], X[L], d X[L]) belong to this object (`cast=True`).  With fp32 neighbours (`cast=False`) the
+boundary is gone: on the VQA fine-tuning route (the engine's `fp32_ends`, core_f32.py) the fused fp32 embedding writes X[0] here, the
+caller reads X[L] and hands an fp32 d X[L] in (tests/test_fp32_ends_gpu.py); in the pre-training step (`fp32_full`, pretrain_f32.py)
+the fp32 front end writes X[0] and the fp32 heads read X[L].
 
 Attention is composed from the batched GEMM: scores = Q.K^T / 8 per (sample, head) -> softmax (+ key mask, + dropout) -> P.V with V
 transposed per head; the backward is the five products of the same shapes.  The probabilities are kept per layer ([B, h, S, Sp] fp32:
@@ -28,16 +29,14 @@ import os
 import torch
 
 from . import ops
-
-F32 = torch.float32
-
-
-def _ru(x, m):
-    return (x + m - 1) // m * m
+from .engine import F32, _ru
 
 
 class EncoderF32:
-    def __init__(self, eng):
+    def __init__(self, eng, cast):
+        """cast: the neighbours are 16-bit -- the front end writes a 16-bit X[0] and the heads read a 16-bit X[L] and leave a 16-bit
+        d X[L]; these three boundary buffers are this object's, and forward / backward cast through them.  Without it the neighbours
+        write and read the fp32 X[0] / X[L] themselves and hand the fp32 d X[L] in."""
         cfg = eng.cfg
         self.eng = eng
         d = eng.dev
@@ -79,6 +78,12 @@ class EncoderF32:
         # on the under-filled 1024 x 1024 outputs than the 23 ms of transposes it removes (DESIGN.md, fp32 path)
         self.tn = os.environ.get("VLB_F32_TN", "0") == "1"
         self.w = [self._w(l) for l in range(L)]      # views into the engine's flat buffers (never rebound), built once
+        self.cast = bool(cast)
+        self.x_in, self.x_out, self.dx_in = self.X[0], self.X[L], None      # (no cast: d X[L] arrives in the neighbour's own buffer)
+        if self.cast:
+            z16 = lambda: torch.zeros((M, H), dtype=ops.BF16, device=d)
+            self.x_in, self.x_out, self.dx_in = z16(), z16(), z16()
+            self.X16 = [self.x_in] + [None] * (L - 1) + [self.x_out]      # what engine.X reads: the two ends, indexed as the layers are
 
     # -- parameters ---------------------------------------------------------------------------------------------------
     def _w(self, l):
@@ -111,6 +116,12 @@ class EncoderF32:
             ops.transpose_f32(w["w2"], I, t["f2"], H, H, I, H)
         self._fresh = True
 
+    def transposes(self):
+        return []        # no 16-bit weight copy: refresh() transposes the fp32 master
+
+    def overwritten(self):
+        return None      # every weight gradient is ACCUMULATED (read-modify-write / atomics)
+
     # -- helpers ------------------------------------------------------------------------------------------------------
     def _linear(self, x, K, w, N, out, **kw):
         ops.gemm_nt_f32(x, K, w, K, out, N, self.M, N, K, **kw)
@@ -140,7 +151,7 @@ class EncoderF32:
 
     # -- forward ------------------------------------------------------------------------------------------------------
     def forward(self, p_h, p_a):
-        """engine.X[0] (16-bit embedding output) -> 24 / 12 fp32 layers -> engine.X[L] (16-bit, for the heads)."""
+        """X[0] (cast: from the 16-bit x_in) -> 24 / 12 fp32 layers -> X[L] (cast: to the 16-bit x_out)."""
         e = self.eng
         H, I, L, nh, M, S, Sp, Bt = self.H, self.I, self.L, self.nh, self.M, self.S, self.Sp, self.Bt
         if not self._fresh:
@@ -148,9 +159,8 @@ class EncoderF32:
         if p_a > 0 and self.Pd is None:
             self.Pd = [torch.zeros((Bt * nh * S, Sp), dtype=F32, device=e.dev) for _ in range(L)]
         seed, mask = e.seed, e.lay["attn_mask"]
-        ends = getattr(e, "fp32_ends", False) or getattr(e, "fp32_full", False)      # X[0] was written in fp32 by the embedding; X[L] is read in fp32
-        if not ends:
-            ops.cast_bf16_f32(e.X[0], self.X[0])
+        if self.cast:
+            ops.cast_bf16_f32(self.x_in, self.X[0])
         bh = (Bt, nh)
         for l in range(L):
             w = self.w[l]
@@ -169,20 +179,19 @@ class EncoderF32:
             self._linear(self.Y1[l], H, w["w1"], I, self.G[l], bias=w["b1"], epi=1, pre=self.dG[l], ldpre=I)
             self._linear(self.G[l], I, w["w2"], H, self.Z2[l], bias=w["b2"], drop_p=p_h, seed=seed, tag=l * 8 + 2, res=self.Y1[l], ldres=H)
             ops.layernorm_f32_fwd(self.Z2[l], w["g2"], w["be2"], self.X[l + 1], self.ST2[l])
-        if not ends:
-            ops.cast_f32_bf16(self.X[L], e.X[L])
+        if self.cast:
+            ops.cast_f32_bf16(self.X[L], self.x_out)
 
     # -- backward -----------------------------------------------------------------------------------------------------
     def backward(self, dx16, p_h, p_a, on_layer_done=None, will_launch=None):
         """dx16: 16-bit d X[L] [M, H] -> weight gradients ACCUMULATED into the engine's flat fp32 gradient; returns the 16-bit d X[0]
-        (written over dx16's buffer).  With the engine's fp32_ends dx16 is the fp32 d X[L] and the fp32 d X[0] is returned."""
+        (written over dx16's buffer).  Without the cast dx16 is the fp32 d X[L] and the fp32 d X[0] is returned."""
         e = self.eng
         H, I, L, nh, M, S, Sp, Bt = self.H, self.I, self.L, self.nh, self.M, self.S, self.Sp, self.Bt
         seed = e.seed
         bh = (Bt, nh)
-        ends = getattr(e, "fp32_ends", False) or getattr(e, "fp32_full", False)
-        dx = dx16 if ends else self.dx[0]
-        if not ends:
+        dx = self.dx[0] if self.cast else dx16
+        if self.cast:
             ops.cast_bf16_f32(dx16, dx)
         for l in reversed(range(L)):
             w, t = self.w[l], self.wT[l]
@@ -229,7 +238,7 @@ class EncoderF32:
             dx = dx_next
             if on_layer_done and (will_launch is None or will_launch(l)):
                 on_layer_done(l)
-        if ends:
+        if not self.cast:
             return dx
         ops.cast_f32_bf16(dx, dx16)
         return dx16

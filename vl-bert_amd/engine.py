@@ -20,7 +20,6 @@ import math
 import os
 from collections import OrderedDict
 from dataclasses import dataclass
-from types import SimpleNamespace
 
 import torch
 
@@ -270,40 +269,13 @@ class PretrainEngine:
         self.w16 = P.named(P.w16)
         self.w32 = P.named(P.master)
         self.g32 = P.named(P.grad)
-        self.vision = None
         if cfg.e2e:
-            from .vision import VisionStack
-            self.vision = VisionStack(B, image_size[0], image_size[1], R, device=d, num_layers=cfg.image_num_layers,
-                                      frozen_stages=cfg.image_frozen_stages, storage=lambda n, shape: (self.w32[n], self.g32[n]))
             self.in_image = torch.zeros((B, 3, image_size[0], image_size[1]), dtype=F32, device=d)
-
-        def zb(*s):
-            return torch.zeros(s, dtype=ops.BF16, device=d)
 
         def zf(*s):
             return torch.zeros(s, dtype=F32, device=d)
 
-        # bf16 transposed weights for dgrad GEMMs (dX = dY . (W^T)^T); refreshed after every optimizer step
-        self.wT = {}
-        self._tbatch = None
         self._zero_small, self._fresh_grads = None, False
-        for l in range(L):
-            p = "vlbert.encoder.layer.%d." % l
-            self.wT[p + "qkv"] = zb(H, 3 * H)
-            self.wT[p + "attention.output.dense.weight"] = zb(H, H)
-            self.wT[p + "intermediate.dense.weight"] = zb(H, I)
-            self.wT[p + "output.dense.weight"] = zb(I, H)
-        self.wT["vlbert.mlm_head.predictions.transform.dense.weight"] = zb(H, H)
-        self.wT["vlbert.word_embeddings.weight"] = zb(H, self.Vp)
-        self.wT["vlbert.mvrc_head.transform.dense.weight"] = zb(H, H)
-        self.wT["vlbert.mvrc_head.region_cls_pred.weight"] = zb(H, self.Cp)
-        self.wT["image_feature_extractor.obj_downsample.1.weight"] = zb(2 * VIS_DIM, H)
-        if cfg.with_pooler:
-            self.wT["vlbert.pooler.dense.weight"] = zb(H, H)
-        if cfg.with_rel_loss:
-            self.wT["vlbert.relationsip_head.caption_image_relationship.weight"] = zb(H, 64)   # K padded to one 64-wide tile
-
-        self.layer = [self._layer_record(l) for l in range(L)]
 
         # device-resident step state
         # odd (the advance kernel keeps it odd) and injective in `seed`: `seed | 1` collapsed ranks 2k / 2k+1 of a
@@ -339,104 +311,20 @@ class PretrainEngine:
         self.lay = dict(code=i32(Bt, self.S), text_len=i32(Bt), nobj=i32(Bt), text_rows=i32(Bt, T), obj_rows=i32(Bt, R),
                         attn_mask=zf(Bt, self.S))
 
-        # activations
-        M, BT, BR, S, nh = self.M, self.BT, self.BR, self.S, cfg.num_attention_heads
-        # Operands of the per-layer weight gradients are allocated with their row count rounded up to 128 (the pad rows stay zero:
-        # every kernel writes M rows) and used through [:M] views; the grouped large-tile wgrad (gemm_tn8.hip, K tiles of 128 rows)
-        # gets the padded tensors, so it also serves the per-GPU batches of a strong-scaling run (M = 3232 at 32 samples).
-        self.Mp128 = _ru(M, 128)
-        self._row_padded = {}
-
-        def zbm(cols):
-            full = zb(self.Mp128, cols)
-            view = full[:M]
-            self._row_padded[view.data_ptr()] = full
-            return view
-        self.a_ds = zb(BR, 2 * VIS_DIM)
-        self.obj_reps = zb(BR, H)
-        self.objvis, self.st_objvis = zb(BR, H), zf(BR, 2)
-        self.textvis, self.st_textvis = zb(Bt, H), zf(Bt, 2)
-        self.emb_pre, self.st_emb = zb(M, H), zf(M, 2)
-        self.X = [zbm(H) for _ in range(L + 1)]
-        self.QKV = [zb(M, 3 * H) for _ in range(L)]
-        self.CTX = [zbm(H) for _ in range(L)]
-        self.LSE = [zf(Bt, nh, S) for _ in range(L)]
-        # Residual stream precision (DESIGN.md "precision"): the pre-LayerNorm sums Z1 / Z2 are kept in fp16 (3 more mantissa bits
-        # than bf16, same bytes; |Z| = O(1..10)) and the residual a sublayer adds is the previous LayerNorm's output re-materialised
-        # in fp32 from (Z, mean, rstd, gamma, beta) inside the GEMM epilogue, so nothing on the residual path is ever rounded to
-        # bf16 -- only the GEMM operands are.  At 12 layers this takes the logits' error against the fp32 reference from 1.3e-2 to
-        # ~6e-3 (relative Frobenius; 5e-3 of it is the bf16 rounding of the weights).  VLB_RESIDUAL_STREAM=bf16: the old behaviour.
-        self.hp_res = os.environ.get("VLB_RESIDUAL_STREAM", "f16ln") != "bf16"
-        zdt = torch.float16 if self.hp_res else ops.BF16
-        zz = lambda *s: torch.zeros(s, dtype=zdt, device=d)
-        self.Z1, self.ST1, self.Y1 = [zz(M, H) for _ in range(L)], [zf(M, 2) for _ in range(L)], [zbm(H) for _ in range(L)]
-        self.U, self.G = [zb(M, I) for _ in range(L)], [zbm(I) for _ in range(L)]
-        self.Z2, self.ST2 = [zz(M, H) for _ in range(L)], [zf(M, 2) for _ in range(L)]
-        self.text_out, self.obj_out = zb(BT, H), zb(BR, H)
-        self.mlm_u, self.mlm_g, self.mlm_h, self.st_mlm = zb(BT, H), zb(BT, H), zb(BT, H), zf(BT, 2)
-        self.mlm_logits = zb(BT, self.Vp)
-        self.mvrc_u, self.mvrc_g = zb(BR, H), zb(BR, H)
-        self.mvrc_logits = zb(BR, self.Cp)
-        self.mvrc_tsum = zf(BR)
-        if cfg.with_pooler:
-            self.pooled, self.d_pooled, self.d_pool_pre = zb(B, H), zb(B, H), zb(B, H)
-        if cfg.with_rel_loss:
-            self.rel_logits = zb(B, 64)                   # 2 logits, row padded to 64 (pad columns stay zero)
-            self.rel_logits_copy = zb(B, 64) if keep_logits else None
-        self.mlm_logits_copy = zb(BT, self.Vp) if keep_logits else None
         # MLM head compaction (DESIGN.md "MLM head"): ~85 % of the text positions carry no label -- their logits are never read by the
         # loss and their d(logits) rows are exactly zero -- so transform -> LayerNorm -> decoder and the head's whole backward run on
         # the labelled rows only, gathered into the first `mlm_cap` rows of the same buffers.  Capacity is a contract with the data
         # pipeline (BERT masking labels 15 % of the valid tokens; at 16384 positions 20 % is 17 standard deviations away): 20 % of the B*T
         # positions rounded up to 256; a batch that exceeds it raises (the
         # device flag is checked at loss_values(); labels handed over as CPU tensors are counted exactly and such a batch simply
-        # takes the full path).  Off with keep_logits (the module mirrors return every logit) and in module-API mode.
+        # takes the full path).  Off with keep_logits (the module mirrors return every logit) and in module-API mode.  Batch state of
+        # the engine (set_batch decides per batch); the heads -- 16-bit or fp32 -- own the buffers that go with it
+        BT = self.BT
         cap = min(self.BTp, max(256, _ru(int(math.ceil(0.20 * BT)), 256)))
         want = os.environ.get("VLB_MLM_COMPACT", "1") != "0" and not keep_logits and not core and cap < BT
         self.mlm_cap = cap if want else None
         self._mlm_compact_now = want
-        if want:
-            self.sel_pos = torch.full((cap,), -1, dtype=torch.int32, device=d)
-            self.sel_src = torch.full((cap,), -1, dtype=torch.int32, device=d)
-            self.labels_c = torch.full((cap,), -1, dtype=torch.int64, device=d)
-            self.mlm_overflow = torch.zeros((1,), dtype=torch.int32, device=d)
-            self.d_text_out_c = zb(cap, H)
-        self.mvrc_logits_copy = zb(BR, self.Cp) if keep_logits else None
 
-        # backward scratch
-        self.dXa, self.dXb = zb(M, H), zb(M, H)
-        # The four weight gradients of a layer go out as ONE grouped launch at the end of the layer's backward (side stream), so their
-        # gradient operands (LN2 / LN1 outputs through dropout, dU, dQKV) stay alive until then and are double-buffered by layer
-        # parity: the next layer writes the other set while the group still reads this one.
-        self.dZ = zb(M, H)
-        # Round 6: the weight gradients of TWO layers go out as one table launch of full-K work items (216 items for 256 CUs like the
-        # grouped launch of one layer, but no K slices: no fp32 slabs, no reduce launch) -- the upper layer of a pair keeps its operands
-        # until the lower one is done, so there are four sets (layer & 3) instead of two.  VLB_WGRAD_PAIRS=0: one grouped launch per layer.
-        self._pairs = os.environ.get("VLB_WGRAD_PAIRS", "1") != "0"
-        self._pair_tables = {}
-        nset = 4 if self._pairs else 2
-        self.dD2, self.dD1 = [zbm(H) for _ in range(nset)], [zbm(H) for _ in range(nset)]
-        self.dU2 = [zbm(I) for _ in range(nset)]
-        self.dQKV2 = [zbm(3 * H) for _ in range(nset)]
-        self.dCTX = zb(M, H)
-        self.d_mlm_h, self.d_mlm_g, self.d_mlm_u = zb(BT, H), zb(BT, H), zb(BT, H)
-        self.d_text_out, self.d_obj_out = zb(BT, H), zb(BR, H)
-        self.d_mvrc_u = zb(BR, H)
-        self.d_textvis, self.d_objvis = zf(Bt, H), zf(BR, H)
-        self.d_obj_reps = zf(BR, H)
-        self.d_yds = zb(BR, H)
-        self.d_afeat = zb(BR, VIS_DIM)
-        if core:
-            self.in_text_type = torch.zeros((Bt, T), dtype=torch.int64, device=d)
-            self.tv_in, self.ovl_in = zb(BT, H), zb(BR, 2 * H)          # inputs as bf16: text_visual [B,T,H], object_vl [B,R,2H]
-            self.tv_n, self.st_tv = zb(BT, H), zf(BT, 2)                # visual_ln_text per token
-            self.d_tv_n, self.d_ol = zf(BT, H), zf(BR, H)               # d(LN(text_visual)), d(object linguistic half)
-            self.d_tv_in, self.d_ovl_in = zb(BT, H), zb(BR, 2 * H)      # gradients handed back to autograd
-            if self.fp32_ends:     # the same tensors in fp32: inputs, the two visual LayerNorm outputs, the pre-LayerNorm sum, d X[L]
-                self.tv_in32, self.ovl_in32 = zf(BT, H), zf(BR, 2 * H)
-                self.tv_n32, self.objvis32, self.emb_pre32 = zf(BT, H), zf(BR, H), zf(M, H)
-                self.d_tv_in32, self.d_ovl_in32 = zf(BT, H), zf(BR, 2 * H)
-                self.dX32 = zf(M, H)
         # fp32 slab workspace for split-K weight gradients (largest request over this engine's wgrad shapes)
         need = [ops.wgrad_workspace_floats(n, k, rp) for n, k, rp in
                 ((3 * H, H, self.Mp), (H, H, self.Mp), (I, H, self.Mp), (H, I, self.Mp), (V, H, self.BTp), (H, H, self.BTp),
@@ -478,29 +366,56 @@ class PretrainEngine:
                 # wshard = the compact bf16 image of the updated slices the weight all-gather distributes (parallel.py)
                 self.shard_tbl = ops.ShardRanges(self.buckets.owned_rows(), d)
                 self.wshard = torch.zeros(self.P.numel // world, dtype=ops.BF16, device=d)
-                # the tensors forward / backward read from the fp32 MASTER (not from the gathered 16-bit copy) are replicated after
-                # every owner-only update (parallel.GradBuckets.set_replicated_fp32)
-                self.buckets.set_replicated_fp32(self._fp32_read_ranges())
-        # fp32 compute mode of the encoder (the reference's TRAIN.FP16: false configurations; encoder_f32.py): the layers run on fp32
-        # tensors and the fp32 MASTER weights, the embedding side and the heads stay on the 16-bit kernels (use the fp16 build) unless
-        # fp32_ends moves the module-API front end and the hand-over of the sequence output to fp32 as well
-        self.enc32 = None
+        # The three parts of the step, chosen here and nowhere else: `front` (inputs -> X[0] and back), `encoder` (X[0] -> X[L] and
+        # back) and `back` (X[L] -> logits, losses, d X[L]).  Each is a plain object that owns every buffer only it touches and answers
+        # the same few questions (transposes / refresh / overwritten, a front also grads); the step functions below call them in order
+        # and never ask which they are.
+        # encoder_fp32 (the reference's TRAIN.FP16: false configurations; encoder_f32.py): the layers run on fp32 tensors and the fp32
+        # MASTER weights; the ends stay on the 16-bit kernels (use the fp16 build) and the encoder casts at its two boundaries, unless
+        # fp32_ends (module API, sequence output: core_f32.py) or fp32_full (the pre-training step: pretrain_f32.py) make them fp32 too
+        self.wT, self.vision, self.enc32, self.pre32 = {}, None, None, None      # wT: every 16-bit W^T copy of the dgrad GEMMs, by name
         if encoder_fp32:
             if self.buckets is not None and self.buckets.sharded:
                 raise ValueError("encoder_fp32 reads the fp32 master weights on every rank: use dp_mode='allreduce' (the sharded optimizer "
                                  "keeps them authoritative on the owner only)")
             from .encoder_f32 import EncoderF32
-            self.enc32 = EncoderF32(self)
-        self.pre32 = None
+            self.encoder = self.enc32 = EncoderF32(self, cast=not (self.fp32_ends or self.fp32_full))
+            self.X = self.encoder.X16 if self.encoder.cast else self.encoder.X
+        else:
+            from .encoder_16 import Encoder16
+            self.encoder = Encoder16(self)
+            self.wT.update(self.encoder.wT)
+            self._alias(self.encoder, "X", "QKV", "LSE")
         if self.fp32_full:
-            # the buffers callers read are the fp32 ones: X is the fp32 encoder's, the logits (and their kept copies) are fp32 twins
-            # of the 16-bit tensors allocated above, which are released
             from .pretrain_f32 import PretrainF32
-            self.X = self.enc32.X
-            self.mlm_logits, self.mvrc_logits = zf(BT, self.Vp), zf(BR, self.Cp)
-            self.mlm_logits_copy = zf(BT, self.Vp) if keep_logits else None
-            self.mvrc_logits_copy = zf(BR, self.Cp) if keep_logits else None
-            self.pre32 = PretrainF32(self)
+            self.front = self.back = self.pre32 = PretrainF32(self)
+        elif self.fp32_ends:
+            from .core_f32 import CoreFrontF32, SequenceOutF32
+            self.front, self.back = CoreFrontF32(self), SequenceOutF32(self)
+        else:
+            from .ends_16 import CoreFront16, Heads16, PretrainFront16
+            self.front = CoreFront16(self) if core else PretrainFront16(self, image_size)
+            self.back = Heads16(self)
+            self.vision = None if core else self.front.vision
+            self.wT.update(self.back.wT)
+            self.wT.update(self.front.wT)
+        self._parts = list(dict.fromkeys((self.encoder, self.back, self.front)))      # (one object may serve as front and back)
+        # what callers read on the engine itself (tests, tools, the module mirrors): plain aliases of the parts' tensors
+        self._alias(self.front, "st_objvis", "st_textvis", "st_emb", "st_tv")
+        self._alias(self.back, "mlm_logits", "mlm_logits_copy", "mvrc_logits", "mvrc_logits_copy", "rel_logits", "rel_logits_copy",
+                    "text_out", "obj_out", "pooled", "st_mlm", "mvrc_tsum", "labels_c", "sel_pos", "sel_src", "mlm_overflow")
+        self._tbatch = None      # every 16-bit (weight, W^T copy) pair of the parts as one launch, built on first use
+        over = [part.overwritten() for part in self._parts]
+        self._overwritten = None if any(o is None for o in over) else [n for o in over for n in o]
+        if self.buckets is not None and self.buckets.sharded:
+            # the tensors forward / backward read from the fp32 MASTER (not from the gathered 16-bit copy) are replicated after
+            # every owner-only update (parallel.GradBuckets.set_replicated_fp32)
+            self.buckets.set_replicated_fp32(self._fp32_read_ranges())
+
+    def _alias(self, part, *names):
+        for n in names:
+            if hasattr(part, n):
+                setattr(self, n, getattr(part, n))
 
     @staticmethod
     def _check_fp32_ends(cfg, T, R, core, core_heads, core_sequence, encoder_fp32, image_size, dp_mode, B_aux):
@@ -556,22 +471,6 @@ class PretrainEngine:
     # ------------------------------------------------------------------------------------------
     # parameters
     # ------------------------------------------------------------------------------------------
-    def _layer_record(self, l):
-        """Views of encoder layer l's parameters in the flat buffers, built once (nothing rebinds P.master / P.grad / P.w16): per Linear
-        (qkv = the fused [3H,H] operand, ao, f1, f2) w (16-bit) / b (fp32) / gw / gb / wT, per LayerNorm (ln1, ln2) g / b / gg / gb."""
-        P, H, p = self.P, self.cfg.hidden_size, "vlbert.encoder.layer.%d." % l
-        q = p + "attention.self.query."
-        rec = SimpleNamespace(qkv=SimpleNamespace(
-            w=P.view(P.w16, q + "weight", (3 * H, H), span=3), b=P.view(P.master, q + "bias", (3 * H,), span=3),
-            gw=P.view(P.grad, q + "weight", (3 * H, H), span=3), gb=P.view(P.grad, q + "bias", (3 * H,), span=3), wT=self.wT[p + "qkv"]))
-        for k, n in (("ao", "attention.output.dense."), ("f1", "intermediate.dense."), ("f2", "output.dense.")):
-            setattr(rec, k, SimpleNamespace(w=self.w16[p + n + "weight"], b=self.w32[p + n + "bias"], gw=self.g32[p + n + "weight"],
-                                            gb=self.g32[p + n + "bias"], wT=self.wT[p + n + "weight"]))
-        for k, n in (("ln1", "attention.output.LayerNorm."), ("ln2", "output.LayerNorm.")):
-            setattr(rec, k, SimpleNamespace(g=self.w32[p + n + "weight"], b=self.w32[p + n + "bias"], gg=self.g32[p + n + "weight"],
-                                            gb=self.g32[p + n + "bias"]))
-        return rec
-
     def load_state_dict(self, sd):
         """sd: {reference state_dict name: tensor}.  The tied decoder key is accepted and ignored."""
         vis = self._vision_names()
@@ -622,21 +521,14 @@ class PretrainEngine:
         self._weights_dirty = False
 
     def _refresh_transposes(self):
-        """bf16 W^T copies for the dgrad GEMMs (dX = dY W as an NT product): all ~50 of them in one launch."""
+        """Every weight copy the parts read: the 16-bit W^T copies of the dgrad GEMMs (dX = dY W as an NT product) of all parts in
+        one launch, all ~50 of them, then whatever each part derives from the weights itself (the fp32 parts' own transposes)."""
         if self._tbatch is None:
-            pairs = [(lin.w, lin.wT) for r in self.layer for lin in (r.qkv, r.ao, r.f1, r.f2)]
-            extra = [n for n in ("vlbert.pooler.dense.weight", "vlbert.relationsip_head.caption_image_relationship.weight")
-                     if n in self.wT]
-            for n in ["vlbert.mlm_head.predictions.transform.dense.weight", "vlbert.word_embeddings.weight",
-                      "vlbert.mvrc_head.transform.dense.weight", "vlbert.mvrc_head.region_cls_pred.weight",
-                      "image_feature_extractor.obj_downsample.1.weight"] + extra:
-                pairs.append((self.w16[n], self.wT[n]))
-            self._tbatch = ops.TransposeBatch(pairs, self.dev)
-        self._tbatch.run()
-        if self.enc32 is not None:
-            self.enc32.refresh()
-        if self.pre32 is not None:
-            self.pre32.refresh()
+            self._tbatch = ops.TransposeBatch([p for part in self._parts for p in part.transposes()], self.dev)
+        if self._tbatch.n:
+            self._tbatch.run()
+        for part in self._parts:
+            part.refresh()
 
     # ------------------------------------------------------------------------------------------
     # batch
@@ -714,25 +606,29 @@ class PretrainEngine:
         """Everything of a forward up to the logits (loss slots zeroed, losses not yet computed): shared by forward() and eval_step()."""
         if self._weights_dirty:
             self.sync_weights()
-        cfg, B, T, R, S, Bt, Ba = self.cfg, self.B, self.T, self.R, self.S, self.Bt, self.Ba
-        H, I, V, C, L, nh = cfg.hidden_size, cfg.intermediate_size, cfg.vocab_size, cfg.visual_region_classes, \
-            cfg.num_hidden_layers, cfg.num_attention_heads
         p_h, p_a, p_ds = self._p(train)
-        w16, w32, seed = self.w16, self.w32, self.seed
         self.losses.zero_()
-        ops.seq_layout_into(self.text_mask, self.box_mask, S, self.lay)
-        if self._gather_pending:    # sharded optimizer: the bf16 weights of the last update arrive bucket by bucket (parallel.gather_params)
+        ops.seq_layout_into(self.text_mask, self.box_mask, self.S, self.lay)
+        stale = self._gather_pending
+        if stale:    # sharded optimizer: the bf16 weights of the last update arrive bucket by bucket (parallel.gather_params)
             if self.vision is not None:
                 self.buckets.wait_params("vision")
                 if self._vision_stale:
                     self.vision.refresh_weights(trainable_only=True)
                     self._vision_stale = False
             self.buckets.wait_params("front")
-        if self.core:
-            self._front_core_fwd(p_h)
-        else:
-            self._front_pretrain_fwd(p_h, p_ds)
-        self._encoder_heads_fwd(p_h, p_a)
+        self.front.front_fwd(p_h, p_ds)
+        self._last_p_a, self._seed_moved = p_a, False      # attention_probs() recomputes this forward's dropout masks
+        self.encoder.forward(p_h, p_a)
+        if stale:
+            self.buckets.wait_params("heads")
+            self._gather_pending = False
+        self.back.heads_fwd()
+
+    def _losses_fwd_bwd(self, gscale, keep):
+        """Loss values + d(logits) written in place over the logits.  Called again by the nn.Module mirror (keep=False:
+        logits restored from the kept copies, loss slots untouched) when autograd hands down an upstream scale != 1."""
+        self.back.losses(gscale, keep)
 
     # ------------------------------------------------------------------------------------------
     # validation (forward only)
@@ -748,22 +644,9 @@ class PretrainEngine:
         touched.  No host synchronisation (read with metric_counts() / loss_values(), whose MLM-overflow contract applies)."""
         if self.core:
             raise ValueError("eval_step: the module-API engine has no loss heads (metrics belong to the wrapper that owns the labels)")
-        if self.fp32_full:
-            raise ValueError("eval_step: not built for an fp32_full engine (the validation kernels of csrc/metrics.hip read 16-bit logits); "
-                             "validate on an engine without fp32_full")
+        self.back.eval_check()
         self._forward_to_logits(False)
-        B, T, Ba, V, C = self.B, self.T, self.Ba, self.cfg.vocab_size, self.cfg.visual_region_classes
-        losses, acc, nw = self.losses, self.metric_acc, B * T
-        if self._mlm_compact_now:      # labelled rows only: caption rows, then the aux rows (their counts came from mlm_compact)
-            ops.ce_eval(self.mlm_logits[:self.mlm_cap], V, self.labels_c, losses[0:1], acc[0], count0=self.counts[0:1],
-                        count1=self.counts[2:3], loss_out1=losses[2:3], acc1=acc[1])
-        else:
-            ops.ce_eval(self.mlm_logits[:nw], V, self.in_mlm_labels.view(-1)[:nw], losses[0:1], acc[0])
-            if Ba:
-                ops.ce_eval(self.mlm_logits[nw:], V, self.in_mlm_labels.view(-1)[nw:], losses[2:3], acc[1])
-        ops.soft_ce_eval(self.mvrc_logits, C, self.in_mvrc_labels.view(self.BR, C), losses[1:2], acc[2])
-        if self.cfg.with_rel_loss:
-            ops.ce_eval(self.rel_logits, 2, self.in_rel_label, losses[3:4], acc[3])
+        self.back.eval_losses()
 
     def reset_metrics(self):
         self.metric_acc.zero_()
@@ -802,170 +685,6 @@ class PretrainEngine:
         self._need_train_metrics("train_metrics_source")
         return self._TrainMetricsSource(self)
 
-    def _front_core_fwd(self, p_h):
-        """VisualLinguisticBert.embedding (common/visual_linguistic_bert.py:173-241) on caller-provided embeddings."""
-        cfg, T, R, S, Bt = self.cfg, self.T, self.R, self.S, self.Bt
-        H = cfg.hidden_size
-        w16, w32, seed = self.w16, self.w32, self.seed
-        if self.fp32_ends:      # fp32 inputs, fp32 master tables, written straight into the fp32 encoder's X[0]
-            ops.layernorm_f32_fwd(self.tv_in32, w32["vlbert.visual_ln_text.weight"], w32["vlbert.visual_ln_text.bias"], self.tv_n32,
-                                  self.st_tv)
-            ops.layernorm_f32_fwd(self.ovl_in32[:, :H], w32["vlbert.visual_ln_object.weight"], w32["vlbert.visual_ln_object.bias"],
-                                  self.objvis32, self.st_objvis)
-            ops.embed_f32_fwd(self.lay, self.in_text, self.in_text_type, w32["vlbert.word_embeddings.weight"],
-                              w32["vlbert.position_embeddings.weight"], w32["vlbert.token_type_embeddings.weight"],
-                              w32["vlbert.end_embedding.weight"], self.tv_n32, (T * H, H), self.objvis32, (R * H, H),
-                              (self.ovl_in32, H), (R * 2 * H, 2 * H), None, w32["vlbert.embedding_LayerNorm.weight"],
-                              w32["vlbert.embedding_LayerNorm.bias"], self.emb_pre32, self.st_emb, self.enc32.X[0], Bt, T, R, S, H,
-                              drop_p=p_h, seed=seed, tag=TAG_EMBED)
-            return
-        ops.layernorm_fwd(self.tv_in, w32["vlbert.visual_ln_text.weight"], w32["vlbert.visual_ln_text.bias"], self.tv_n, self.st_tv)
-        ops.layernorm_fwd(self.ovl_in[:, :H], w32["vlbert.visual_ln_object.weight"], w32["vlbert.visual_ln_object.bias"], self.objvis,
-                          self.st_objvis)
-        ops.embed_fwd(self.lay, self.in_text, self.in_text_type, w16["vlbert.word_embeddings.weight"],
-                      w16["vlbert.position_embeddings.weight"], w16["vlbert.token_type_embeddings.weight"],
-                      w16["vlbert.end_embedding.weight"], self.tv_n, (T * H, H), self.objvis, (R * H, H),
-                      self.ovl_in[:, H:], (R * 2 * H, 2 * H), None, w32["vlbert.embedding_LayerNorm.weight"],
-                      w32["vlbert.embedding_LayerNorm.bias"], self.emb_pre, self.st_emb, self.X[0], Bt, T, R, S, H, drop_p=p_h,
-                      seed=seed, tag=TAG_EMBED)
-
-    def _front_pretrain_fwd(self, p_h, p_ds):
-        cfg, B, T, R, S, Bt, Ba = self.cfg, self.B, self.T, self.R, self.S, self.Bt, self.Ba
-        H = cfg.hidden_size
-        w16, w32, seed = self.w16, self.w32, self.seed
-        if self.fp32_full:      # every tensor fp32, written straight into the fp32 encoder's X[0] (pretrain_f32.py)
-            self.pre32.front_fwd(p_h, p_ds)
-            return
-        # --- e2e: ResNet trunk -> ROIAlign -> layer4 head -> avg-pool, written into the feature slots of in_boxes; the raw
-        #     pixels are masked by the dataset, so no mask embedding is substituted (mask_visual_embed=None, :120-127) ----
-        e2e = self.vision is not None
-        if e2e:
-            self.vision.forward(self.in_image, self.in_boxes)
-        # --- FastRCNN: (coord || feature) -> Dropout -> Linear(4096->H) -> ReLU (common/fast_rcnn.py:165-175) -------
-        ops.obj_prep_fwd(self.in_boxes, self.in_im_info, None if e2e else self.in_mvrc_ops.view(-1),
-                         w32["object_mask_visual_embedding.weight"], self.a_ds, drop_p=p_ds, seed=seed, tag=TAG_DOWNSAMPLE)
-        ops.gemm_nt(self.a_ds, w16["image_feature_extractor.obj_downsample.1.weight"], self.obj_reps,
-                    bias=w32["image_feature_extractor.obj_downsample.1.bias"], act=ops.ACT_RELU)
-        ops.zero_padded_rows(self.obj_reps, self.in_boxes)      # pad_sequence zeros (a padded box 0 feeds the text tokens' visual embedding)
-        # --- visual LayerNorms + fused embedding ---------------------------------------------------------
-        ops.layernorm_fwd(self.obj_reps, w32["vlbert.visual_ln_object.weight"], w32["vlbert.visual_ln_object.bias"], self.objvis,
-                          self.st_objvis)
-        reps0 = self.obj_reps.view(B, R * H)[:, :H]          # obj_reps[:, 0]  (text tags are all 0, :132-135)
-        ops.layernorm_fwd(reps0, w32["vlbert.visual_ln_text.weight"], w32["vlbert.visual_ln_text.bias"], self.textvis[:B],
-                          self.st_textvis[:B])
-        if Ba:   # aux text-only samples: every token sees LN(aux_text_visual_embedding) (multitask.py:176)
-            ops.layernorm_fwd(w16["aux_text_visual_embedding.weight"], w32["vlbert.visual_ln_text.weight"],
-                              w32["vlbert.visual_ln_text.bias"], self.textvis[B:], self.st_textvis[B:], rows=Ba, ldx=0)
-        ops.embed_fwd(self.lay, self.in_text, None, w16["vlbert.word_embeddings.weight"], w16["vlbert.position_embeddings.weight"],
-                      w16["vlbert.token_type_embeddings.weight"], w16["vlbert.end_embedding.weight"], self.textvis, (H, 0),
-                      self.objvis, (R * H, H), w16["object_linguistic_embeddings.weight"], (0, 0), self.in_mvrc_ops,
-                      w32["vlbert.embedding_LayerNorm.weight"], w32["vlbert.embedding_LayerNorm.bias"], self.emb_pre, self.st_emb,
-                      self.X[0], Bt, T, R, S, H, drop_p=p_h, seed=seed, tag=TAG_EMBED)
-
-    def _encoder_heads_fwd(self, p_h, p_a):
-        cfg, S, Bt = self.cfg, self.S, self.Bt
-        H, V, C, L, nh = cfg.hidden_size, cfg.vocab_size, cfg.visual_region_classes, cfg.num_hidden_layers, cfg.num_attention_heads
-        w16, w32, seed = self.w16, self.w32, self.seed
-        # --- encoder -------------------------------------------------------------------------------------
-        mask = self.lay["attn_mask"]
-        stale = self._gather_pending
-        self._last_p_a, self._seed_moved = p_a, False      # attention_probs() recomputes this forward's dropout masks
-        if self.enc32 is not None:
-            self.enc32.forward(p_h, p_a)
-            if self.fp32_ends:      # the caller reads enc32.X[L] (sequence_output): no 16-bit copy, no gathers from one
-                return
-            if self.fp32_full:      # the fp32 heads gather from enc32.X[L]
-                self.pre32.heads_fwd()
-                return
-        for l in range(L if self.enc32 is None else 0):
-            r, x = self.layer[l], self.X[l]
-            if stale:
-                self.buckets.wait_params(l)
-            ops.gemm_nt(x, r.qkv.w, self.QKV[l], bias=r.qkv.b)
-            ops.attention_fwd(self.QKV[l], mask, self.CTX[l], self.LSE[l], Bt, S, H, nh, drop_p=p_a, seed=seed, tag=l * 8 + 0)
-            if self.hp_res and l > 0:    # residual = LayerNorm(Z2[l-1]) in fp32 (layer 0: the bf16 embedding output, one rounding)
-                ln = self.layer[l - 1].ln2
-                res_kw = dict(res=self.Z2[l - 1], res_ln=(self.ST2[l - 1], ln.g, ln.b))
-            else:
-                res_kw = dict(res=x)
-            ops.gemm_nt(self.CTX[l], r.ao.w, self.Z1[l], bias=r.ao.b, drop_p=p_h, seed=seed, tag=l * 8 + 1, **res_kw)
-            ops.layernorm_fwd(self.Z1[l], r.ln1.g, r.ln1.b, self.Y1[l], self.ST1[l])
-            ops.gemm_nt(self.Y1[l], r.f1.w, self.G[l], bias=r.f1.b, act=ops.ACT_GELU_D, pre=self.U[l])
-            if self.hp_res:
-                res_kw = dict(res=self.Z1[l], res_ln=(self.ST1[l], r.ln1.g, r.ln1.b))
-            else:
-                res_kw = dict(res=self.Y1[l])
-            ops.gemm_nt(self.G[l], r.f2.w, self.Z2[l], bias=r.f2.b, drop_p=p_h, seed=seed, tag=l * 8 + 2, **res_kw)
-            ops.layernorm_fwd(self.Z2[l], r.ln2.g, r.ln2.b, self.X[l + 1], self.ST2[l])
-        # --- heads ---------------------------------------------------------------------------------------
-        if stale:
-            self.buckets.wait_params("heads")
-            self._gather_pending = False
-        xl = self.X[L]
-        compact = self._mlm_compact_now and self.with_heads
-        nr = self.mlm_cap if compact else self.BT          # rows the MLM head runs on
-        if compact:
-            ops.mlm_compact(self.in_mlm_labels.view(-1), self.lay["text_rows"].view(-1), self.B * self.T, V, self.sel_pos, self.sel_src,
-                            self.labels_c, self.counts[0:1], self.counts[2:3], self.mlm_overflow)
-            ops.gather_rows(xl, self.sel_src, self.text_out[:nr])
-        else:
-            ops.gather_rows(xl, self.lay["text_rows"].view(-1), self.text_out)
-        ops.gather_rows(xl, self.lay["obj_rows"].view(-1)[:self.BR], self.obj_out)
-        if cfg.with_pooler:       # BertPooler: tanh(dense(first token)) for the image-caption samples; A operand = strided view of X[L]
-            x0 = xl.view(Bt, S * H)[:self.B, :H]
-            ops.gemm_nt(x0, w16["vlbert.pooler.dense.weight"], self.pooled, bias=w32["vlbert.pooler.dense.bias"], act=ops.ACT_TANH)
-        if not self.with_heads:
-            return
-        if cfg.with_rel_loss:     # relationsip_head: Linear(H -> 2) on the pooled output (common/visual_linguistic_bert.py:505-516)
-            pr = "vlbert.relationsip_head.caption_image_relationship."
-            ops.gemm_nt(self.pooled, w16[pr + "weight"], self.rel_logits[:, :2], bias=w32[pr + "bias"])
-        pm = "vlbert.mlm_head.predictions."
-        ops.gemm_nt(self.text_out[:nr], w16[pm + "transform.dense.weight"], self.mlm_g[:nr], bias=w32[pm + "transform.dense.bias"],
-                    act=ops.ACT_GELU_D, pre=self.mlm_u[:nr])
-        ops.layernorm_fwd(self.mlm_g[:nr], w32[pm + "transform.LayerNorm.weight"], w32[pm + "transform.LayerNorm.bias"], self.mlm_h[:nr],
-                          self.st_mlm[:nr])
-        ops.gemm_nt(self.mlm_h[:nr], w16["vlbert.word_embeddings.weight"], self.mlm_logits[:nr, :V], bias=w32[pm + "bias"])
-        ops.gemm_nt(self.obj_out, w16["vlbert.mvrc_head.transform.dense.weight"], self.mvrc_g,
-                    bias=w32["vlbert.mvrc_head.transform.dense.bias"], act=ops.ACT_GELU_D, pre=self.mvrc_u)
-        ops.gemm_nt(self.mvrc_g, w16["vlbert.mvrc_head.region_cls_pred.weight"], self.mvrc_logits[:, :C],
-                    bias=w32["vlbert.mvrc_head.region_cls_pred.bias"])
-
-    def _losses_fwd_bwd(self, gscale, keep):
-        """Loss values + d(logits) written in place over the logits.  Called again by the nn.Module mirror (keep=False:
-        logits restored from the kept copies, loss slots untouched) when autograd hands down an upstream scale != 1."""
-        B, T, Ba, V, C = self.B, self.T, self.Ba, self.cfg.vocab_size, self.cfg.visual_region_classes
-        if self.fp32_full:
-            self.pre32.losses(gscale, keep)
-            return
-        if keep:
-            losses, mcopy, vcopy = self.losses, self.mlm_logits_copy, self.mvrc_logits_copy
-        else:
-            self.mlm_logits.copy_(self.mlm_logits_copy)
-            self.mvrc_logits.copy_(self.mvrc_logits_copy)
-            losses, mcopy, vcopy = torch.zeros_like(self.losses), None, None
-        nw = B * T     # rows of the image-caption samples; the aux rows follow and get their own mean (multitask.py:224-246)
-        ds = self.scaler.scale if self.scaler is not None else None      # dynamic loss scale: multiplied into gscale on the device
-        # train_metrics: the launches below become their ACC forms and add [hits, counted rows] to a row of train_metric_acc
-        # (METRIC_ROWS) -- on the keep=True pass only, so that the mirror's re-run counts nothing twice
-        tm = self.train_metric_acc if keep else None
-        acc = (lambda *rows: dict(zip(("acc", "acc1"), (tm[r] for r in rows)))) if tm is not None else (lambda *rows: {})
-        if self._mlm_compact_now:      # labelled rows only: caption rows first, then the aux rows, each group with its own mean
-            ops.ce_fwd_bwd_compact(self.mlm_logits[:self.mlm_cap], V, self.labels_c, self.counts[0:1], self.counts[2:3], losses[0:1],
-                                   losses[2:3], gscale=gscale, dscale=ds, **acc(0, 1))
-        else:
-            ops.ce_fwd_bwd(self.mlm_logits[:nw], V, self.in_mlm_labels.view(-1)[:nw], self.counts[0:1], losses[0:1], gscale=gscale,
-                           logits_copy=mcopy[:nw] if mcopy is not None else None, dscale=ds, **acc(0))
-            if Ba:
-                ops.ce_fwd_bwd(self.mlm_logits[nw:], V, self.in_mlm_labels.view(-1)[nw:], self.counts[2:3], losses[2:3],
-                               gscale=gscale, logits_copy=mcopy[nw:] if mcopy is not None else None, dscale=ds, **acc(1))
-        ops.soft_ce_fwd_bwd(self.mvrc_logits, C, self.in_mvrc_labels.view(self.BR, C), self.mvrc_tsum, self.counts[1:2],
-                            losses[1:2], gscale=gscale, logits_copy=vcopy, dscale=ds, **acc(2))
-        if self.cfg.with_rel_loss:     # F.cross_entropy(relationship_logits, relationship_label) (resnet_vlbert_for_pretraining.py:160-161)
-            if not keep:
-                self.rel_logits.copy_(self.rel_logits_copy)
-            ops.ce_fwd_bwd(self.rel_logits, 2, self.in_rel_label, self.counts[3:4], losses[3:4], gscale=gscale,
-                           logits_copy=self.rel_logits_copy if keep else None, dscale=ds, **acc(3))
-
     # ------------------------------------------------------------------------------------------
     # backward (explicit; weight gradients are ACCUMULATED into the flat fp32 grad buffer)
     # ------------------------------------------------------------------------------------------
@@ -977,41 +696,6 @@ class PretrainEngine:
         """gw[N,K] (+)= dy^T x ; gb[N] += colsum(dy), straight from the row-major operands (LDS transpose reads), bias gradient fused."""
         acc = not self._fresh_grads
         self._on_side(lambda: ops.wgrad_tn(dy, x, gw, colsum=gb, workspace=self.wg_ws, accumulate=acc), [(dy, x, gw, gb)])
-
-    def _padded(self, items):
-        """items with their row-padded operands (zero pad rows): K a multiple of 128 for the large-tile kernels."""
-        pad = self._row_padded
-        return [(pad.get(dy.data_ptr(), dy), pad.get(x.data_ptr(), x), gw, gb) for dy, x, gw, gb in items]
-
-    def _wgrad_group(self, items):
-        """items: [(dy, x, gw, gb)] over the same rows -- the four Linear layers of an encoder layer -- as one grouped launch on the
-        side stream (ops.wgrad_tn_group)."""
-        acc = not self._fresh_grads
-        items = self._padded(items)
-        if len({t.shape[0] for it in items for t in it[:2]}) != 1:
-            items = [(dy[:self.M], x[:self.M], gw, gb) for dy, x, gw, gb in items]
-        self._on_side(lambda: ops.wgrad_tn_group(items, workspace=self.wg_ws, accumulate=acc), items)
-
-    def _wgrad_pair(self, items):
-        """items: [(dy, x, gw, gb)] of TWO encoder layers (8 products over the same rows) as ONE table launch of full-K 256 x 256 work
-        items on the side stream (ops.WgradTable: no K slices, no slabs, no reduce).  The descriptor table of a pair is built once per
-        (buffers, accumulate) and replayed.  False: not taken (a product outside what the table kernel covers, or a table that would
-        have to be built during stream capture) -- the caller falls back to one grouped launch per layer."""
-        acc = not self._fresh_grads
-        items = self._padded(items)
-        key = (acc,) + tuple(t.data_ptr() for it in items for t in it)
-        tab = self._pair_tables.get(key)
-        if tab is None:
-            if self.dev.type == "cuda" and torch.cuda.is_current_stream_capturing():
-                return False
-            if len({t.shape[0] for it in items for t in it[:2]}) != 1:
-                return False
-            tab = ops.WgradTable([(dy, x, gw, gb, None) for dy, x, gw, gb in items], self.dev, accumulate=acc)
-            self._pair_tables[key] = tab
-        if not tab.ok:
-            return False
-        self._on_side(lambda: tab.run(), items)
-        return True
 
     def _before_write(self, *bufs):
         """Main stream is about to overwrite these buffers: wait for side-stream weight gradients still reading them."""
@@ -1047,221 +731,32 @@ class PretrainEngine:
                 self._flush_ln()
                 user_hook(what)
         train = self.train if train is None else train
-        cfg, B, T, R, S, Bt, Ba = self.cfg, self.B, self.T, self.R, self.S, self.Bt, self.Ba
-        H, I, V, C, L, nh = cfg.hidden_size, cfg.intermediate_size, cfg.vocab_size, cfg.visual_region_classes, \
-            cfg.num_hidden_layers, cfg.num_attention_heads
         p_h, p_a, p_ds = self._p(train)
-        w16, w32, g32, wT, seed = self.w16, self.w32, self.g32, self.wT, self.seed
         if self._wT_stale:           # sharded optimizer: every gathered weight has landed by now -> the dgrad operands W^T
             self.buckets.wait_params("all")
             self._refresh_transposes()
             self._wT_stale = False
         if self.buckets is not None and on_layer_done is None:
             self.buckets.invalidate()      # (a micro-step without the exchange: the reduced images are stale until a hooked backward)
-        if self.fp32_full:      # heads and hand-over in fp32: the fp32 d X[L] goes into the fp32 encoder's backward
-            dx32 = self.pre32.heads_bwd()
-        elif self.with_heads:
-            # --- MLM head ------------------------------------------------------------------------------------
-            pm = "vlbert.mlm_head.predictions."
-            compact = self._mlm_compact_now and not self.core
-            nr = self.mlm_cap if compact else self.BT
-            dlog = self.mlm_logits[:nr]                  # [rows, Vp], pad columns zero
-            self._wgrad(dlog[:, :V], self.mlm_h[:nr], g32["vlbert.word_embeddings.weight"], g32[pm + "bias"])
-            ops.gemm_nt_splitk(dlog, wT["vlbert.word_embeddings.weight"], self.d_mlm_h[:nr], workspace=self.wg_ws_main)
-            self._ln_bwd(self.d_mlm_h[:nr], self.mlm_g[:nr], self.st_mlm[:nr], w32[pm + "transform.LayerNorm.weight"],
-                         g32[pm + "transform.LayerNorm.weight"], g32[pm + "transform.LayerNorm.bias"], dx=self.d_mlm_g[:nr])
-            ops.mul_bf16(self.d_mlm_g[:nr], self.mlm_u[:nr], self.d_mlm_u[:nr])
-            self._wgrad(self.d_mlm_u[:nr], self.text_out[:nr], g32[pm + "transform.dense.weight"], g32[pm + "transform.dense.bias"])
-            if compact:      # gradient of the labelled rows back to their text positions; every other position gets exactly zero
-                ops.gemm_nt(self.d_mlm_u[:nr], wT[pm + "transform.dense.weight"], self.d_text_out_c)
-                self.d_text_out.zero_()
-                ops.scatter_rows(self.d_text_out_c, self.sel_pos, self.d_text_out)
-            else:
-                ops.gemm_nt(self.d_mlm_u, wT[pm + "transform.dense.weight"], self.d_text_out)
-            # --- MVRC head -----------------------------------------------------------------------------------
-            dlog2 = self.mvrc_logits                     # [BR, Cp]
-            self._wgrad(dlog2[:, :C], self.mvrc_g, g32["vlbert.mvrc_head.region_cls_pred.weight"],
-                        g32["vlbert.mvrc_head.region_cls_pred.bias"])
-            ops.gemm_nt(dlog2, wT["vlbert.mvrc_head.region_cls_pred.weight"], self.d_mvrc_u, act=ops.ACT_MULAUX, aux=self.mvrc_u)
-            self._wgrad(self.d_mvrc_u, self.obj_out, g32["vlbert.mvrc_head.transform.dense.weight"],
-                        g32["vlbert.mvrc_head.transform.dense.bias"])
-            ops.gemm_nt(self.d_mvrc_u, wT["vlbert.mvrc_head.transform.dense.weight"], self.d_obj_out)
-            if cfg.with_rel_loss:
-                pr = "vlbert.relationsip_head.caption_image_relationship."
-                self._wgrad(self.rel_logits[:, :2], self.pooled, g32[pr + "weight"], g32[pr + "bias"])
-                ops.gemm_nt(self.rel_logits, wT[pr + "weight"], self.d_pooled)      # K = 64: two logits + zero padding
-        dx = self.dX32 if self.fp32_ends else (dx32 if self.fp32_full else self.dXa)
-        if not self.seq_out and not self.fp32_full:      # (sequence mode: the caller's d(sequence_output) is already in dXa)
-            ops.head_grad_combine(self.d_text_out, self.d_obj_out, self.lay["code"], dx, Bt, T, R, S, H)
-        if cfg.with_pooler and (cfg.with_rel_loss or not self.with_heads):
-            # d(pooled) came from the relationship head (or from the caller in hidden-state mode): through tanh and the
-            # dense layer, then ADDED to the first-token rows of dX (gemm epilogue residual = its own output rows)
-            ops.tanh_bwd(self.d_pooled, self.pooled, self.d_pool_pre)
-            x0 = self.X[L].view(Bt, S * H)[:self.B, :H]
-            self._wgrad(self.d_pool_pre, x0, g32["vlbert.pooler.dense.weight"], g32["vlbert.pooler.dense.bias"])
-            dx0 = dx.view(Bt, S * H)[:self.B, :H]
-            ops.gemm_nt(self.d_pool_pre, wT["vlbert.pooler.dense.weight"], dx0, res=dx0)
+        dx = self.back.heads_bwd()          # d(logits) / the caller's gradients -> d X[L]
         if on_layer_done:
             self._join_side()
             on_layer_done("heads")
-        # --- encoder, last layer first -------------------------------------------------------------------
-        mask = self.lay["attn_mask"]
-        if self.enc32 is not None:
-            dx = self.enc32.backward(dx, p_h, p_a, on_layer_done, will_launch)
-        held = None      # (layer, weight-gradient items) of an odd layer waiting for the layer below it (self._pairs)
-        for l in reversed(range(L if self.enc32 is None else 0)):
-            r = self.layer[l]
-            dx_next = self.dXb if dx is self.dXa else self.dXa
-            par = l & (len(self.dD2) - 1)
-            dD2, dD1, dU, dQKV = self.dD2[par], self.dD1[par], self.dU2[par], self.dQKV2[par]
-            # LN2: dZ2 (residual branch) and dD2 (into output.dense, through its dropout; a plain copy when dropout is off --
-            # dZ is reused inside the layer, the grouped weight gradient at its end needs its own operand)
-            self._before_write(self.dZ, dD2)
-            self._ln_bwd(dx, self.Z2[l], self.ST2[l], r.ln2.g, r.ln2.gg, r.ln2.gb, dx=self.dZ, dx_drop=dD2, drop_p=p_h, seed=seed,
-                         tag=l * 8 + 2)
-            self._before_write(dU)
-            ops.gemm_nt(dD2, r.f2.wT, dU, act=ops.ACT_MULAUX, aux=self.U[l])
-            ops.gemm_nt(dU, r.f1.wT, dx_next, res=self.dZ)                                         # dY1
-            # LN1
-            self._before_write(self.dZ, dD1)
-            self._ln_bwd(dx_next, self.Z1[l], self.ST1[l], r.ln1.g, r.ln1.gg, r.ln1.gb, dx=self.dZ, dx_drop=dD1, drop_p=p_h, seed=seed,
-                         tag=l * 8 + 1)
-            ops.gemm_nt(dD1, r.ao.wT, self.dCTX)
-            self._before_write(dQKV)
-            ops.attention_bwd(self.QKV[l], mask, self.CTX[l], self.LSE[l], self.dCTX, dQKV, Bt, S, H, nh, drop_p=p_a,
-                              seed=seed, tag=l * 8 + 0)
-            ops.gemm_nt(dQKV, r.qkv.wT, dx_next, res=self.dZ)                                      # dX_l (overwrites dY1)
-            # the layer's four weight gradients on the side stream, off the critical dgrad chain: with the layer below as ONE table launch
-            # (an odd layer waits for its partner), or as one grouped launch per layer
-            wg = [(dD2, self.G[l], r.f2.gw, r.f2.gb), (dU, self.Y1[l], r.f1.gw, r.f1.gb), (dD1, self.CTX[l], r.ao.gw, r.ao.gb),
-                  (dQKV, self.X[l], r.qkv.gw, r.qkv.gb)]
-            dx = dx_next
-            if self._pairs and (l & 1):
-                held = (l, wg)              # (its hook fires behind the pair's launch)
-                continue
-            finished = [l]
-            if held is not None:
-                if not self._wgrad_pair(held[1] + wg):
-                    self._wgrad_group(held[1])
-                    self._wgrad_group(wg)
-                finished = [held[0], l]
-                held = None
-            else:
-                self._wgrad_group(wg)
-            for lf in finished:
-                if on_layer_done and (will_launch is None or will_launch(lf)):
-                    self._join_side()       # the bucket's weight gradients must be complete before its all-reduce reads them
-                    on_layer_done(lf)
+        dx = self.encoder.backward(dx, p_h, p_a, on_layer_done, will_launch)      # last layer first -> d X[0]
         # embed_bwd adds into the word-embedding gradient the decoder weight-gradient launch wrote: the front waits for the side
         # launches that wrote one of ITS gradient tensors, not for the encoder's last weight-gradient launch, which it runs beside.
         # With a bucket hook the exchange reads whole buckets behind the front: everything on the side stream completes first.
         if on_layer_done:
             self._join_side()
         else:
-            self._hazards.before_accumulate(*self._front_grads())
-        if self.core:
-            self._front_core_bwd(dx, p_h)
-        elif self.fp32_full:
-            self.pre32.front_bwd(dx, p_h, p_ds, on_layer_done)
-        else:
-            self._front_pretrain_bwd(dx, p_h, p_ds, on_layer_done)
+            self._hazards.before_accumulate(*self.front.grads())
+        self.front.front_bwd(dx, p_h, p_ds, on_layer_done)
         self._join_side()
         self._flush_ln()
         self._fresh_grads = False       # a further backward before the next zero_grad() accumulates
         if on_layer_done:
             on_layer_done("embed")
             on_layer_done("vision")
-
-    FRONT_GRADS = ("vlbert.word_embeddings.weight", "vlbert.position_embeddings.weight", "vlbert.token_type_embeddings.weight",
-                   "vlbert.end_embedding.weight", "vlbert.embedding_LayerNorm.weight", "vlbert.embedding_LayerNorm.bias",
-                   "vlbert.visual_ln_text.weight", "vlbert.visual_ln_text.bias", "vlbert.visual_ln_object.weight",
-                   "vlbert.visual_ln_object.bias", "object_linguistic_embeddings.weight", "object_mask_word_embedding.weight",
-                   "aux_text_visual_embedding.weight", "object_mask_visual_embedding.weight", "image_feature_extractor.obj_downsample.1.weight",
-                   "image_feature_extractor.obj_downsample.1.bias")
-
-    def _front_grads(self):
-        """Every gradient tensor _front_core_bwd / _front_pretrain_bwd add into or overwrite on the main stream (or hand to a side
-        launch of their own)."""
-        return [self.g32[n] for n in self.FRONT_GRADS if n in self.g32]
-
-    def _front_core_bwd(self, dx, p_h):
-        cfg, T, R, S, Bt = self.cfg, self.T, self.R, self.S, self.Bt
-        H = cfg.hidden_size
-        w32, g32, seed = self.w32, self.g32, self.seed
-        self.d_tv_n.zero_()
-        self.d_objvis.zero_()
-        pe = "vlbert.embedding_LayerNorm."
-        if self.fp32_ends:      # dx: the fp32 d X[0]; d(object linguistic half) is written straight into the handed-back gradient
-            self.d_ovl_in32.zero_()
-            ops.embed_f32_bwd(dx, self.emb_pre32, self.st_emb, w32[pe + "weight"], self.lay, self.in_text, self.in_text_type, None,
-                              g32["vlbert.word_embeddings.weight"], g32["vlbert.position_embeddings.weight"],
-                              g32["vlbert.token_type_embeddings.weight"], g32["vlbert.end_embedding.weight"], g32[pe + "weight"],
-                              g32[pe + "bias"], self.d_tv_n, (T * H, H), self.d_objvis, (R * H, H), (self.d_ovl_in32, H),
-                              (R * 2 * H, 2 * H), Bt, T, R, S, H, drop_p=p_h, seed=seed, tag=TAG_EMBED)
-            ops.layernorm_f32_bwd(self.d_tv_n, self.tv_in32, self.st_tv, w32["vlbert.visual_ln_text.weight"], dx=self.d_tv_in32,
-                                  dgamma=g32["vlbert.visual_ln_text.weight"], dbeta=g32["vlbert.visual_ln_text.bias"])
-            ops.layernorm_f32_bwd(self.d_objvis, self.ovl_in32[:, :H], self.st_objvis, w32["vlbert.visual_ln_object.weight"],
-                                  dx=self.d_ovl_in32[:, :H], dgamma=g32["vlbert.visual_ln_object.weight"],
-                                  dbeta=g32["vlbert.visual_ln_object.bias"])
-            return
-        self.d_ol.zero_()
-        ops.embed_bwd(dx, self.emb_pre, self.st_emb, w32[pe + "weight"], self.lay, self.in_text, self.in_text_type, None,
-                      g32["vlbert.word_embeddings.weight"], g32["vlbert.position_embeddings.weight"],
-                      g32["vlbert.token_type_embeddings.weight"], g32["vlbert.end_embedding.weight"], g32[pe + "weight"],
-                      g32[pe + "bias"], self.d_tv_n, (T * H, H), self.d_objvis, (R * H, H), self.d_ol, (R * H, H), Bt, T, R, S, H,
-                      drop_p=p_h, seed=seed, tag=TAG_EMBED)
-        # gradients of the two inputs (padded positions: zero rows, as the reference's masked scatter gives)
-        ops.layernorm_bwd(self.d_tv_n, self.tv_in, self.st_tv, w32["vlbert.visual_ln_text.weight"], dx=self.d_tv_in,
-                          dgamma=g32["vlbert.visual_ln_text.weight"], dbeta=g32["vlbert.visual_ln_text.bias"], workspace=self.ln_ws)
-        ops.layernorm_bwd(self.d_objvis, self.ovl_in[:, :H], self.st_objvis, w32["vlbert.visual_ln_object.weight"],
-                          dx=self.d_ovl_in[:, :H], dgamma=g32["vlbert.visual_ln_object.weight"],
-                          dbeta=g32["vlbert.visual_ln_object.bias"], workspace=self.ln_ws)
-        self.d_ovl_in[:, H:].copy_(self.d_ol)      # fp32 -> bf16 strided copy (glue: hands the gradient to autograd)
-
-    def _front_pretrain_bwd(self, dx, p_h, p_ds, on_layer_done=None):
-        cfg, B, T, R, S, Bt, Ba = self.cfg, self.B, self.T, self.R, self.S, self.Bt, self.Ba
-        H = cfg.hidden_size
-        w16, w32, g32, wT, seed = self.w16, self.w32, self.g32, self.wT, self.seed
-        # --- embedding + visual LayerNorms + obj_downsample ---------------------------------------------
-        self.d_objvis.zero_()
-        self.d_obj_reps.zero_()
-        self.d_textvis.zero_()
-        pe = "vlbert.embedding_LayerNorm."
-        ops.embed_bwd(dx, self.emb_pre, self.st_emb, w32[pe + "weight"], self.lay, self.in_text, None, self.in_mvrc_ops,
-                      g32["vlbert.word_embeddings.weight"], g32["vlbert.position_embeddings.weight"],
-                      g32["vlbert.token_type_embeddings.weight"], g32["vlbert.end_embedding.weight"], g32[pe + "weight"],
-                      g32[pe + "bias"], self.d_textvis, (H, 0), self.d_objvis, (R * H, H),
-                      self.P.view(self.P.grad, "object_linguistic_embeddings.weight", (2, H), span=2), (0, 0), Bt, T, R, S, H,
-                      drop_p=p_h, seed=seed, tag=TAG_EMBED, text_vis_zeroed=True)
-        if on_layer_done:      # the tied word-embedding gradient (decoder wgrad + this scatter-add) is complete: its 94 MB go out first
-            on_layer_done("word_emb")
-        ops.layernorm_bwd(self.d_objvis, self.obj_reps, self.st_objvis, w32["vlbert.visual_ln_object.weight"],
-                          dx_acc=self.d_obj_reps, dgamma=g32["vlbert.visual_ln_object.weight"],
-                          dbeta=g32["vlbert.visual_ln_object.bias"], workspace=self.ln_ws)
-        reps0 = self.obj_reps.view(B, R * H)[:, :H]
-        ops.layernorm_bwd(self.d_textvis[:B], reps0, self.st_textvis[:B], w32["vlbert.visual_ln_text.weight"],
-                          dx_acc=self.d_obj_reps.view(B, R * H)[:, :H], dgamma=g32["vlbert.visual_ln_text.weight"],
-                          dbeta=g32["vlbert.visual_ln_text.bias"])
-        if Ba:   # all aux samples share one input row: stride-0 input, gradient accumulated into the single parameter row
-            ops.layernorm_bwd(self.d_textvis[B:], w16["aux_text_visual_embedding.weight"], self.st_textvis[B:],
-                              w32["vlbert.visual_ln_text.weight"], dx_acc=g32["aux_text_visual_embedding.weight"],
-                              dgamma=g32["vlbert.visual_ln_text.weight"], dbeta=g32["vlbert.visual_ln_text.bias"],
-                              rows=Ba, ldx=0, ldacc=0)
-        ops.relu_bwd_cast(self.d_obj_reps, self.obj_reps, self.d_yds)
-        pd = "image_feature_extractor.obj_downsample.1."
-        self._wgrad(self.d_yds, self.a_ds, g32[pd + "weight"], g32[pd + "bias"])
-        # gradient of the mask embedding: feature half of dA = dY W, masked regions only
-        ops.gemm_nt(self.d_yds, wT[pd + "weight"][VIS_DIM:], self.d_afeat)
-        if self.vision is not None:      # the features are activations of the CNN: RoI head, ROIAlign and trunk backward
-            self._join_side()
-            hook = None
-            if on_layer_done:     # everything but the convolutions is complete: its bucket goes out under the CNN backward
-                on_layer_done("embed")
-                hook = lambda layer: on_layer_done("vision%d" % layer)
-            self.vision.backward(self.d_afeat, self.in_boxes, drop_p=p_ds, seed=seed, tag=TAG_DOWNSAMPLE, on_stage_done=hook)
-            return
-        ops.masked_colsum(self.d_afeat, self.in_mvrc_ops.view(-1), g32["object_mask_visual_embedding.weight"].view(-1),
-                          drop_p=p_ds, seed=seed, tag=TAG_DOWNSAMPLE, row_elems=2 * VIS_DIM, col_off=VIS_DIM)
 
     # ------------------------------------------------------------------------------------------
     # module-API mode (core=True)
@@ -1277,50 +772,39 @@ class PretrainEngine:
             raise ValueError("core inputs must be text [%d,%d], text_visual [%d,%d,%d], object_vl [%d,%d,%d]"
                              % (Bt, T, Bt, T, H, Bt, R, 2 * H))
         self.in_text.copy_(text_input_ids)
-        self.in_text_type.copy_(text_token_type_ids)
         self.text_mask.view(torch.bool).copy_(text_mask)
         self.box_mask.view(torch.bool).copy_(object_mask)
-        if self.fp32_ends:      # the caller's embeddings stay fp32
-            self.tv_in32.view(Bt, T, H).copy_(text_visual_embeddings)
-            self.ovl_in32.view(Bt, R, 2 * H).copy_(object_vl_embeddings)
-            return
-        self.tv_in.view(Bt, T, H).copy_(text_visual_embeddings)            # dtype conversion to bf16 (glue)
-        self.ovl_in.view(Bt, R, 2 * H).copy_(object_vl_embeddings)
+        self.front.set_inputs(text_token_type_ids, text_visual_embeddings, object_vl_embeddings)      # in the front's own precision
 
     def forward_core(self, train=None):
         """-> (mlm_logits [B,T,V], mvrc_logits [B,R,C], text_out [B,T,H], obj_out [B,R,H], pooled [B,H] | None,
-        relationship_logits [B,2] | None) as bf16 views of the engine buffers."""
+        relationship_logits [B,2] | None) as bf16 views of the back's buffers (all None where the back only hands the sequence over)."""
         self.forward(train)
-        V, C, H = self.cfg.vocab_size, self.cfg.visual_region_classes, self.cfg.hidden_size
-        return (self.mlm_logits[:, :V].view(self.Bt, self.T, V), self.mvrc_logits[:, :C].view(self.B, self.R, C),
-                self.text_out.view(self.Bt, self.T, H), self.obj_out.view(self.B, self.R, H),
-                self.pooled if self.cfg.with_pooler else None, self.rel_logits[:, :2] if self.cfg.with_rel_loss else None)
+        return self.back.outputs()
 
     def backward_core_hidden(self, d_text_out, d_obj_out, d_pooled=None, train=None):
         """core_heads=False: d(text_out) [B,T,H] / d(obj_out) [B,R,H] (/ d(pooled) [B,H]) -> input gradients (see backward_core)."""
-        H = self.cfg.hidden_size
+        H, back = self.cfg.hidden_size, self.back
         if self.cfg.with_pooler:
             if d_pooled is None:
-                self.d_pooled.zero_()
+                back.d_pooled.zero_()
             else:
-                self.d_pooled.copy_(d_pooled)
+                back.d_pooled.copy_(d_pooled)
         if d_text_out is None:
-            self.d_text_out.zero_()
+            back.d_text_out.zero_()
         else:
-            self.d_text_out.copy_(d_text_out.reshape(self.BT, H))
+            back.d_text_out.copy_(d_text_out.reshape(self.BT, H))
         if d_obj_out is None:
-            self.d_obj_out.zero_()
+            back.d_obj_out.zero_()
         else:
-            self.d_obj_out.copy_(d_obj_out.reshape(self.BR, H))
+            back.d_obj_out.copy_(d_obj_out.reshape(self.BR, H))
         self.backward(train)
-        return self.d_tv_in.view(self.Bt, self.T, H), self.d_ovl_in.view(self.Bt, self.R, 2 * H)
+        return self.front.input_grads()
 
     def sequence_output(self):
-        """Last encoder layer as the packed [B, S, H] sequence (text || objects || END || padding), bf16 view (fp32_ends: the fp32
-        encoder's own X[L], fp32)."""
-        if self.fp32_ends:
-            return self.enc32.X[self.cfg.num_hidden_layers].view(self.Bt, self.S, self.cfg.hidden_size)
-        return self.X[self.cfg.num_hidden_layers].view(self.Bt, self.S, self.cfg.hidden_size)
+        """Last encoder layer as the packed [B, S, H] sequence (text || objects || END || padding): a view of what the back reads,
+        16-bit, or the fp32 encoder's own X[L] where the back is fp32."""
+        return self.encoder.x_out.view(self.Bt, self.S, self.cfg.hidden_size)
 
     # ------------------------------------------------------------------------------------------
     # inspection of the last forward (16-bit encoder): no per-layer state beyond what the forward leaves behind anyway
@@ -1351,37 +835,33 @@ class PretrainEngine:
         the reference returns (modeling.py:311-316) -- also once optimizer_step() has advanced the seed: the forward's value is kept.  n defaults to the batch's longest packed sequence.  Each layer's buffer is
         allocated by the call; ask for one layer at a time where all of them together would not fit."""
         layers, n = self._inspect_args("attention_probs", layers, n)
-        cfg = self.cfg
         seed = self._seed_prev if self._seed_moved else self.seed      # optimizer_step has moved on: the forward's value was kept
-        return [ops.attention_probs(self.QKV[l], self.lay["attn_mask"], self.LSE[l], self.Bt, self.S, cfg.hidden_size,
-                                    cfg.num_attention_heads, n=n, drop_p=self._last_p_a, seed=seed, tag=l * 8 + 0) for l in layers]
+        return self.encoder.attention_probs(layers, n, seed)
 
     def encoded_layers(self, layers=None, n=None):
         """Outputs of the encoder layers of the last forward: fp32 copies of X[l + 1] as [Bt, n, H], one per layer in `layers`."""
         layers, n = self._inspect_args("encoded_layers", layers, n)
-        return [self.X[l + 1].view(self.Bt, self.S, self.cfg.hidden_size)[:, :n].float() for l in layers]
+        return self.encoder.encoded_layers(layers, n)
 
     def backward_core_sequence(self, d_seq, d_pooled=None, train=None):
         """core_sequence=True: d(sequence_output) [B, <=S, H] (rows beyond the given length are zero) -> input gradients."""
         H = self.cfg.hidden_size
-        dx = (self.dX32 if self.fp32_ends else self.dXa).view(self.Bt, self.S, H)
+        dx = self.back.dx.view(self.Bt, self.S, H)      # where the back leaves d X[L]: here the caller writes it
         dx.zero_()
         if d_seq is not None:
             dx[:, :d_seq.shape[1]].copy_(d_seq)
         if self.cfg.with_pooler:
             if d_pooled is None:
-                self.d_pooled.zero_()
+                self.back.d_pooled.zero_()
             else:
-                self.d_pooled.copy_(d_pooled)
+                self.back.d_pooled.copy_(d_pooled)
         self.backward(train)
-        if self.fp32_ends:
-            return self.d_tv_in32.view(self.Bt, self.T, H), self.d_ovl_in32.view(self.Bt, self.R, 2 * H)
-        return self.d_tv_in.view(self.Bt, self.T, H), self.d_ovl_in.view(self.Bt, self.R, 2 * H)
+        return self.front.input_grads()
 
     def backward_core(self, d_mlm_logits, d_mvrc_logits, d_rel_logits=None, train=None):
         """d(logits) [B,T,V] / [B,R,C] (any float dtype; None = zero) -> parameter gradients accumulated into the flat
         gradient, returns (d text_visual_embeddings [B,T,H], d object_vl_embeddings [B,R,2H]) as bf16 views."""
-        V, C, H = self.cfg.vocab_size, self.cfg.visual_region_classes, self.cfg.hidden_size
+        V, C = self.cfg.vocab_size, self.cfg.visual_region_classes
         if d_mlm_logits is None:
             self.mlm_logits.zero_()
         else:
@@ -1396,7 +876,7 @@ class PretrainEngine:
             else:
                 self.rel_logits[:, :2].copy_(d_rel_logits)
         self.backward(train)
-        return self.d_tv_in.view(self.Bt, self.T, H), self.d_ovl_in.view(self.Bt, self.R, 2 * H)
+        return self.front.input_grads()
 
     # ------------------------------------------------------------------------------------------
     # optimizer
@@ -1404,13 +884,12 @@ class PretrainEngine:
     def zero_grad(self):
         """Start of an optimizer step.  The Linear weight gradients (97 % of the buffer) are OVERWRITTEN by the first
         backward, so only the ranges that are accumulated with atomics are cleared."""
-        if self.core or self.enc32 is not None:      # (module-API mode may run without the heads: nothing overwrites
-            # their gradients; the fp32 encoder ACCUMULATES its weight gradients with atomics)
+        if self._overwritten is None:      # a part ACCUMULATES its weight gradients, or may not run at all (overwritten() of the parts)
             self.P.grad.zero_()
             self._fresh_grads = False
             return
         if self._zero_small is None:
-            covered = sorted((self.P.offsets[n], self.P.offsets[n] + math.prod(self.P.shapes[n])) for n in self._gemm_weight_names())
+            covered = sorted((self.P.offsets[n], self.P.offsets[n] + math.prod(self.P.shapes[n])) for n in self._overwritten)
             ranges, cur = [], 0
             for lo, hi in covered:
                 ranges.append((cur, lo))
@@ -1421,18 +900,9 @@ class PretrainEngine:
         self._fresh_grads = True
 
     def _gemm_weight_names(self):
-        """Parameters whose gradient is produced (whole tensor) by exactly one _wgrad call per backward."""
-        L = self.cfg.num_hidden_layers
-        names = ["image_feature_extractor.obj_downsample.1.weight", "vlbert.word_embeddings.weight",
-                 "vlbert.mlm_head.predictions.transform.dense.weight", "vlbert.mvrc_head.transform.dense.weight",
-                 "vlbert.mvrc_head.region_cls_pred.weight"]
-        if self.cfg.with_rel_loss:
-            names += ["vlbert.pooler.dense.weight", "vlbert.relationsip_head.caption_image_relationship.weight"]
-        for l in range(L):
-            p = "vlbert.encoder.layer.%d." % l
-            names += [p + "attention.self.query.weight", p + "attention.self.key.weight", p + "attention.self.value.weight",
-                      p + "attention.output.dense.weight", p + "intermediate.dense.weight", p + "output.dense.weight"]
-        return names
+        """Parameters whose gradient is produced (whole tensor) by exactly one weight-gradient product per backward: what the parts
+        answer (overwritten()); empty where a part accumulates and zero_grad() therefore clears everything."""
+        return list(self._overwritten or ())
 
     def optimizer_step(self, lr=None):
         """global-norm clip + AdamW + bf16 / transposed weight refresh + dropout seed advance.  With data

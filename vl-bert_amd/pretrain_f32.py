@@ -20,13 +20,14 @@ engine refreshes its weight copies (load, every optimizer step).
 import torch
 
 from . import ops
-
-F32 = torch.float32
-VIS_DIM = 2048
-TAG_EMBED, TAG_DOWNSAMPLE = 1000, 1001      # engine.py's dropout sites
+from .engine import F32, TAG_DOWNSAMPLE, TAG_EMBED, VIS_DIM
+from .ends_16 import PRETRAIN_FRONT_GRADS
 
 
 class PretrainF32:
+    """Serves as the engine's front AND back: front_fwd / front_bwd around the fp32 encoder's X[0], heads_fwd / losses / heads_bwd
+    around its X[L]."""
+
     def __init__(self, eng):
         self.eng = eng
         cfg, d = eng.cfg, eng.dev
@@ -37,10 +38,20 @@ class PretrainF32:
         # front end
         self.a_ds, self.obj_reps, self.objvis, self.textvis = z(BR, 2 * VIS_DIM), z(BR, H), z(BR, H), z(B, H)
         self.obj_ling, self.emb_pre = z(BR, H), z(M, H)
-        # heads (logits and their kept copies: eng.mlm_logits / eng.mvrc_logits (_copy), fp32 under fp32_full)
-        self.text_out, self.mlm_g, self.mlm_dg, self.mlm_h = z(BT, H), z(BT, H), z(BT, H), z(BT, H)
+        self.st_objvis, self.st_textvis, self.st_emb = z(BR, 2), z(B, 2), z(M, 2)
+        # heads
+        self.text_out, self.mlm_g, self.mlm_dg, self.mlm_h, self.st_mlm = z(BT, H), z(BT, H), z(BT, H), z(BT, H), z(BT, 2)
         self.obj_out, self.mvrc_g, self.mvrc_dg = z(BR, H), z(BR, H), z(BR, H)
+        self.mlm_logits, self.mvrc_logits, self.mvrc_tsum = z(BT, Vp), z(BR, Cp), z(BR)
+        self.mlm_logits_copy = z(BT, Vp) if eng.keep_logits else None
+        self.mvrc_logits_copy = z(BR, Cp) if eng.keep_logits else None
         self.row_loss = z(max(BT, BR, 1))
+        if eng.mlm_cap is not None:      # MLM head compaction (DESIGN.md "MLM head"): the labelled rows, gathered into the first mlm_cap rows
+            cap = eng.mlm_cap
+            self.sel_pos = torch.full((cap,), -1, dtype=torch.int32, device=d)
+            self.sel_src = torch.full((cap,), -1, dtype=torch.int32, device=d)
+            self.labels_c = torch.full((cap,), -1, dtype=torch.int64, device=d)
+            self.mlm_overflow = torch.zeros((1,), dtype=torch.int32, device=d)
         # backward
         self.d_mlm_h, self.d_mlm_g, self.d_mlm_u, self.d_text_out = z(BT, H), z(BT, H), z(BT, H), z(BT, H)
         self.d_text_out_c = z(eng.mlm_cap, H) if eng.mlm_cap is not None else None
@@ -62,6 +73,16 @@ class PretrainF32:
         P = eng.P
         self.ling_table = P.view(P.master, "object_linguistic_embeddings.weight", (2, H), span=2)
         self.g_ling_table = P.view(P.grad, "object_linguistic_embeddings.weight", (2, H), span=2)
+        self.x0, self.xl = eng.encoder.x_in, eng.encoder.x_out
+
+    def transposes(self):
+        return []        # no 16-bit weight copy: refresh() pads / transposes the fp32 master
+
+    def overwritten(self):
+        return None      # every weight gradient is ACCUMULATED (read-modify-write)
+
+    def grads(self):
+        return [self.eng.g32[n] for n in PRETRAIN_FRONT_GRADS if n in self.eng.g32]
 
     def refresh(self):
         """Padded / transposed fp32 copies of the current master weights (exact: data movement only)."""
@@ -82,7 +103,7 @@ class PretrainF32:
 
     # -- forward ------------------------------------------------------------------------------------------------------
     def front_fwd(self, p_h, p_ds):
-        """Input buffers -> enc32.X[0]."""
+        """Input buffers -> the fp32 encoder's X[0]."""
         e = self.eng
         B, T, R, S, H = e.B, e.T, e.R, e.S, e.cfg.hidden_size
         w, seed = e.w32, e.seed
@@ -92,14 +113,14 @@ class PretrainF32:
         pd = "image_feature_extractor.obj_downsample.1."
         ops.gemm_nt_f32(self.a_ds, 2 * VIS_DIM, w[pd + "weight"], 2 * VIS_DIM, self.obj_reps, H, e.BR, H, 2 * VIS_DIM, bias=w[pd + "bias"], epi=2)
         ops.zero_padded_rows_f32(self.obj_reps, e.in_boxes)      # pad_sequence zeros (a padded box 0 feeds the text tokens' visual embedding)
-        ops.layernorm_f32_fwd(self.obj_reps, w["vlbert.visual_ln_object.weight"], w["vlbert.visual_ln_object.bias"], self.objvis, e.st_objvis)
+        ops.layernorm_f32_fwd(self.obj_reps, w["vlbert.visual_ln_object.weight"], w["vlbert.visual_ln_object.bias"], self.objvis, self.st_objvis)
         reps0 = self.obj_reps.view(B, R * H)[:, :H]              # obj_reps[:, 0] (text tags are all 0)
-        ops.layernorm_f32_fwd(reps0, w["vlbert.visual_ln_text.weight"], w["vlbert.visual_ln_text.bias"], self.textvis, e.st_textvis)
+        ops.layernorm_f32_fwd(reps0, w["vlbert.visual_ln_text.weight"], w["vlbert.visual_ln_text.bias"], self.textvis, self.st_textvis)
         ops.select_rows2_f32(self.ling_table, e.in_mvrc_ops.view(-1), self.obj_ling)
         ops.embed_f32_fwd(e.lay, e.in_text, None, w["vlbert.word_embeddings.weight"], w["vlbert.position_embeddings.weight"],
                           w["vlbert.token_type_embeddings.weight"], w["vlbert.end_embedding.weight"], self.textvis, (H, 0), self.objvis,
                           (R * H, H), self.obj_ling, (R * H, H), None, w["vlbert.embedding_LayerNorm.weight"],
-                          w["vlbert.embedding_LayerNorm.bias"], self.emb_pre, e.st_emb, e.enc32.X[0], B, T, R, S, H, drop_p=p_h, seed=seed,
+                          w["vlbert.embedding_LayerNorm.bias"], self.emb_pre, self.st_emb, self.x0, B, T, R, S, H, drop_p=p_h, seed=seed,
                           tag=TAG_EMBED)
 
     def _mlm_rows(self):
@@ -108,15 +129,15 @@ class PretrainF32:
         return compact, (e.mlm_cap if compact else e.BT)
 
     def heads_fwd(self):
-        """enc32.X[L] -> the two logits tensors."""
+        """The fp32 encoder's X[L] -> the two logits tensors."""
         e = self.eng
-        H, V, L = e.cfg.hidden_size, e.cfg.vocab_size, e.cfg.num_hidden_layers
-        w, xl = e.w32, e.enc32.X[L]
+        H, V = e.cfg.hidden_size, e.cfg.vocab_size
+        w, xl = e.w32, self.xl
         compact, nr = self._mlm_rows()
         if compact:
-            ops.mlm_compact(e.in_mlm_labels.view(-1), e.lay["text_rows"].view(-1), e.B * e.T, V, e.sel_pos, e.sel_src, e.labels_c,
-                            e.counts[0:1], e.counts[2:3], e.mlm_overflow)
-            ops.gather_rows_f32(xl, e.sel_src, self.text_out[:nr])
+            ops.mlm_compact(e.in_mlm_labels.view(-1), e.lay["text_rows"].view(-1), e.B * e.T, V, self.sel_pos, self.sel_src, self.labels_c,
+                            e.counts[0:1], e.counts[2:3], self.mlm_overflow)
+            ops.gather_rows_f32(xl, self.sel_src, self.text_out[:nr])
         else:
             ops.gather_rows_f32(xl, e.lay["text_rows"].view(-1), self.text_out)
         ops.gather_rows_f32(xl, e.lay["obj_rows"].view(-1)[:e.BR], self.obj_out)
@@ -124,36 +145,40 @@ class PretrainF32:
         ops.gemm_nt_f32(self.text_out, H, w[pm + "transform.dense.weight"], H, self.mlm_g, H, nr, H, H, bias=w[pm + "transform.dense.bias"],
                         epi=1, pre=self.mlm_dg, ldpre=H)
         ops.layernorm_f32_fwd(self.mlm_g[:nr], w[pm + "transform.LayerNorm.weight"], w[pm + "transform.LayerNorm.bias"], self.mlm_h[:nr],
-                              e.st_mlm[:nr])
-        ops.gemm_nt_f32(self.mlm_h, H, self.Wdec, H, e.mlm_logits, e.Vp, nr, e.Vp, H, bias=self.bdec)
+                              self.st_mlm[:nr])
+        ops.gemm_nt_f32(self.mlm_h, H, self.Wdec, H, self.mlm_logits, e.Vp, nr, e.Vp, H, bias=self.bdec)
         pv = "vlbert.mvrc_head."
         ops.gemm_nt_f32(self.obj_out, H, w[pv + "transform.dense.weight"], H, self.mvrc_g, H, e.BR, H, H, bias=w[pv + "transform.dense.bias"],
                         epi=1, pre=self.mvrc_dg, ldpre=H)
-        ops.gemm_nt_f32(self.mvrc_g, H, self.Wcls, H, e.mvrc_logits, e.Cp, e.BR, e.Cp, H, bias=self.bcls)
+        ops.gemm_nt_f32(self.mvrc_g, H, self.Wcls, H, self.mvrc_logits, e.Cp, e.BR, e.Cp, H, bias=self.bcls)
 
     def losses(self, gscale, keep):
-        """Loss values + d(logits) in place over the fp32 logits (engine._losses_fwd_bwd, its keep=False re-run included)."""
+        """Loss values + d(logits) in place over the fp32 logits (ends_16.Heads16.losses, its keep=False re-run included)."""
         e = self.eng
         V, C = e.cfg.vocab_size, e.cfg.visual_region_classes
         if keep:
-            losses, mcopy, vcopy = e.losses, e.mlm_logits_copy, e.mvrc_logits_copy
+            losses, mcopy, vcopy = e.losses, self.mlm_logits_copy, self.mvrc_logits_copy
         else:
-            e.mlm_logits.copy_(e.mlm_logits_copy)
-            e.mvrc_logits.copy_(e.mvrc_logits_copy)
+            self.mlm_logits.copy_(self.mlm_logits_copy)
+            self.mvrc_logits.copy_(self.mvrc_logits_copy)
             losses, mcopy, vcopy = torch.zeros_like(e.losses), None, None
         compact, nr = self._mlm_rows()
         # train_metrics: the ACC forms add [hits, counted rows] to rows 0 (MLM; row 1 takes the empty second group) and 2 (MVRC) of
-        # train_metric_acc, on the keep=True pass only (engine._losses_fwd_bwd)
+        # train_metric_acc, on the keep=True pass only (as Heads16.losses)
         tm = e.train_metric_acc if keep else None
         acc = (lambda *rows: dict(zip(("acc", "acc1"), (tm[r] for r in rows)))) if tm is not None else (lambda *rows: {})
         if compact:
-            ops.ce_f32_fwd_bwd_compact(e.mlm_logits[:nr], V, e.labels_c, e.counts[0:1], e.counts[2:3], losses[0:1], losses[2:3], gscale=gscale,
+            ops.ce_f32_fwd_bwd_compact(self.mlm_logits[:nr], V, self.labels_c, e.counts[0:1], e.counts[2:3], losses[0:1], losses[2:3], gscale=gscale,
                                        row_loss=self.row_loss, **acc(0, 1))
         else:
-            ops.ce_f32_fwd_bwd(e.mlm_logits, V, e.in_mlm_labels.view(-1), e.counts[0:1], losses[0:1], gscale=gscale, logits_copy=mcopy,
+            ops.ce_f32_fwd_bwd(self.mlm_logits, V, e.in_mlm_labels.view(-1), e.counts[0:1], losses[0:1], gscale=gscale, logits_copy=mcopy,
                                row_loss=self.row_loss, **acc(0))
-        ops.soft_ce_f32_fwd_bwd(e.mvrc_logits, C, e.in_mvrc_labels.view(e.BR, C), e.mvrc_tsum, e.counts[1:2], losses[1:2], gscale=gscale,
+        ops.soft_ce_f32_fwd_bwd(self.mvrc_logits, C, e.in_mvrc_labels.view(e.BR, C), self.mvrc_tsum, e.counts[1:2], losses[1:2], gscale=gscale,
                                 logits_copy=vcopy, row_loss=self.row_loss, **acc(2))
+
+    def eval_check(self):
+        raise ValueError("eval_step: not built for an fp32_full engine (the validation kernels of csrc/metrics.hip read 16-bit logits); "
+                         "validate on an engine without fp32_full")
 
     # -- backward -----------------------------------------------------------------------------------------------------
     def heads_bwd(self):
@@ -163,12 +188,12 @@ class PretrainF32:
         w, g = e.w32, e.g32
         compact, nr = self._mlm_rows()
         pm = "vlbert.mlm_head.predictions."
-        dlog = e.mlm_logits      # [rows, Vp], pad columns zero
+        dlog = self.mlm_logits      # [rows, Vp], pad columns zero
         ops.gemm_tn_f32(dlog, e.Vp, self.mlm_h, H, g["vlbert.word_embeddings.weight"], H, nr, V, H, atomic=True, colsum=g[pm + "bias"])
         nb, kc = self.dec_split, e.Vp // self.dec_split
         ops.gemm_nt_f32(dlog, e.Vp, self.WdecT, e.Vp, self.dec_slabs, nb * H, nr, H, kc, batch=(nb, 1), sA=(kc, 0), sB=(kc, 0), sC=(H, 0))
         ops.group_rowsum_f32(self.dec_slabs[:nr * nb], nb, self.d_mlm_h[:nr])
-        ops.layernorm_f32_bwd(self.d_mlm_h[:nr], self.mlm_g[:nr], e.st_mlm[:nr], w[pm + "transform.LayerNorm.weight"], dx=self.d_mlm_g[:nr],
+        ops.layernorm_f32_bwd(self.d_mlm_h[:nr], self.mlm_g[:nr], self.st_mlm[:nr], w[pm + "transform.LayerNorm.weight"], dx=self.d_mlm_g[:nr],
                               dgamma=g[pm + "transform.LayerNorm.weight"], dbeta=g[pm + "transform.LayerNorm.bias"])
         ops.mul_f32(self.d_mlm_g[:nr], self.mlm_dg[:nr], self.d_mlm_u[:nr])
         ops.gemm_tn_f32(self.d_mlm_u, H, self.text_out, H, g[pm + "transform.dense.weight"], H, nr, H, H, atomic=True,
@@ -176,11 +201,11 @@ class PretrainF32:
         if compact:      # gradient of the labelled rows back to their text positions; every other position gets exactly zero
             ops.gemm_nt_f32(self.d_mlm_u, H, self.WmT, H, self.d_text_out_c, H, nr, H, H)
             self.d_text_out.zero_()
-            ops.scatter_rows_f32(self.d_text_out_c, e.sel_pos, self.d_text_out)
+            ops.scatter_rows_f32(self.d_text_out_c, self.sel_pos, self.d_text_out)
         else:
             ops.gemm_nt_f32(self.d_mlm_u, H, self.WmT, H, self.d_text_out, H, nr, H, H)
         pv = "vlbert.mvrc_head."
-        dlog2 = e.mvrc_logits    # [BR, Cp]
+        dlog2 = self.mvrc_logits    # [BR, Cp]
         ops.gemm_tn_f32(dlog2, e.Cp, self.mvrc_g, H, g[pv + "region_cls_pred.weight"], H, e.BR, C, H, atomic=True,
                         colsum=g[pv + "region_cls_pred.bias"])
         ops.gemm_nt_f32(dlog2, e.Cp, self.WclsT, e.Cp, self.d_mvrc_u, H, e.BR, H, e.Cp, epi=3, aux=self.mvrc_dg, ldaux=H)
@@ -199,7 +224,7 @@ class PretrainF32:
         self.d_objvis.zero_()
         self.d_obj_ling.zero_()
         pe = "vlbert.embedding_LayerNorm."
-        ops.embed_f32_bwd(dx, self.emb_pre, e.st_emb, w[pe + "weight"], e.lay, e.in_text, None, None, g["vlbert.word_embeddings.weight"],
+        ops.embed_f32_bwd(dx, self.emb_pre, self.st_emb, w[pe + "weight"], e.lay, e.in_text, None, None, g["vlbert.word_embeddings.weight"],
                           g["vlbert.position_embeddings.weight"], g["vlbert.token_type_embeddings.weight"], g["vlbert.end_embedding.weight"],
                           g[pe + "weight"], g[pe + "bias"], self.d_tv_tok, (T * H, H), self.d_objvis, (R * H, H), self.d_obj_ling, (R * H, H),
                           B, T, R, S, H, drop_p=p_h, seed=seed, tag=TAG_EMBED)
@@ -207,10 +232,10 @@ class PretrainF32:
         ops.table2_grad_f32(self.d_obj_ling, e.in_mvrc_ops.view(-1), self.g_ling_table)
         if on_layer_done:      # the tied word-embedding gradient (decoder weight gradient + this scatter-add) is complete
             on_layer_done("word_emb")
-        ops.layernorm_f32_bwd(self.d_objvis, self.obj_reps, e.st_objvis, w["vlbert.visual_ln_object.weight"], dx=self.d_obj_reps,
+        ops.layernorm_f32_bwd(self.d_objvis, self.obj_reps, self.st_objvis, w["vlbert.visual_ln_object.weight"], dx=self.d_obj_reps,
                               dgamma=g["vlbert.visual_ln_object.weight"], dbeta=g["vlbert.visual_ln_object.bias"])
         reps0 = self.obj_reps.view(B, R * H)[:, :H]
-        ops.layernorm_f32_bwd(self.d_textvis, reps0, e.st_textvis, w["vlbert.visual_ln_text.weight"], dx=self.d_reps0,
+        ops.layernorm_f32_bwd(self.d_textvis, reps0, self.st_textvis, w["vlbert.visual_ln_text.weight"], dx=self.d_reps0,
                               dgamma=g["vlbert.visual_ln_text.weight"], dbeta=g["vlbert.visual_ln_text.bias"])
         ops.add_rows_f32(self.d_obj_reps.view(B, R * H)[:, :H], self.d_reps0)
         ops.relu_bwd_f32(self.d_obj_reps, self.obj_reps, self.d_yds)
