@@ -34,7 +34,8 @@ typedef struct ihipStream_t* vlb_stream_t; /* == hipStream_t */
 
 const char* vlb_last_error(void);
 /* 200 = 0.2.0: the fused losses and optimizer steps take their optional features (dscale, acc, scaler, g_is_bf16) as arguments of one
- * entry point each; arguments were inserted under names that 0.1.0 already had, so a caller checks the version it was built for */
+ * entry point each; arguments were inserted under names that 0.1.0 already had, so a caller checks the version it was built for.
+ * 300 = 0.3.0: adds vlb_sample_norm_weights and the vlb_*_rowweight_* losses; no signature of 0.2.0 changed */
 int vlb_version(void);
 /* 16-bit storage type of this build: 0 = bfloat16 (libvlbert_hip.so, the default), 1 = IEEE fp16 (libvlbert_hip_f16.so: every
  * "bf16" in the names below then means fp16 -- the reference's own mixed precision, Apex O2 with a static loss scale,
@@ -271,6 +272,37 @@ int vlb_ce_eval(const void* logits, long ld, int rows, int V, const int64_t* lab
                 float* loss_out0, float* loss_out1, int64_t* acc0, int64_t* acc1, int32_t* pred, vlb_stream_t stream);
 int vlb_soft_ce_eval(const void* logits, long ld, int rows, int C, const float* target, long ldt, float* loss_out, int64_t* acc,
                      vlb_stream_t stream);
+
+/* ---- per-sample loss normalisation (NETWORK.MLM_LOSS_NORM_IN_BATCH_FIRST / MVRC_LOSS_NORM_IN_BATCH_FIRST,
+ * resnet_vlbert_for_pretraining.py:168-174, 183-190): loss = sum_b (sum_t l_bt / (n_b + 1e-4)) / (#{b : n_b > 0} + 1e-4), n_b = the
+ * labelled tokens (valid regions) of sample b.  Library version 0.3.0.
+ * vlb_sample_norm_weights: w[b] = 1 / ((n_b + 1e-4) (n_has + 1e-4)) for the B samples (0 where n_b = 0), from EITHER labels ([B, T]
+ *   int64, labelled iff 0 <= label < V; samples [0, B_split) and [B_split, B) are two groups with their own n_has: the caption and
+ *   the text-only samples of the multitask wrapper) OR tsum ([B * T] row sums of the soft targets, valid iff |tsum - 1| < 0.1; one
+ *   group, B_split = B).  count0 / count1 (nullable) are WRITTEN: the labelled rows of the two groups.  One workgroup, integer
+ *   counts: the same inputs give the same bits; no host synchronisation.
+ * vlb_ce_rowweight_fwd_bwd: vlb_ce_fwd_bwd where row r adds w[s(r)] l_r to the loss and leaves gscale w[s(r)] (softmax - onehot) in
+ *   place of its logits; s(r) = pos(r) / T with pos(r) = r, or sel_pos[r] on the rows vlb_mlm_compact listed (labels = its labels_c;
+ *   a negative sel_pos is a skipped row).  Rows of samples < B_split add to loss_out0 / acc0, the others to loss_out1 / acc1 (needed
+ *   when B_split < B).  Without sel_pos rows <= B * T.  dscale / logits_copy / acc0, acc1: nullable, as above; the weights do not
+ *   enter the counters.  ld % 8 == 0, logits 16-byte aligned.
+ * vlb_soft_ce_rowweight_fwd_bwd: the soft-label twin over rows = B * R regions, s(r) = r / R.  tsum [rows] and w [B] are outputs
+ *   (row validity, then the weights from it); counts[0] = valid rows, as vlb_soft_ce_fwd_bwd leaves it.
+ * vlb_ce_rowweight_eval / vlb_soft_ce_rowweight_eval: the forward-only twins (eval_step): the logits are only read, loss_out += the
+ *   weighted mean, acc (required) += [hits, counted rows] as vlb_ce_eval / vlb_soft_ce_eval count them. */
+int vlb_sample_norm_weights(const int64_t* labels, const float* tsum, int B, int T, int V, int B_split, float* w, float* count0,
+                            float* count1, vlb_stream_t stream);
+int vlb_ce_rowweight_fwd_bwd(void* logits, long ld, int rows, int V, const int64_t* labels, const int32_t* sel_pos, int B, int T,
+                             int B_split, const float* w, float gscale, const float* dscale, float* loss_out0, float* loss_out1,
+                             void* logits_copy, long ldcopy, int64_t* acc0, int64_t* acc1, vlb_stream_t stream);
+int vlb_soft_ce_rowweight_fwd_bwd(void* logits, long ld, int rows, int C, const float* target, long ldt, float* tsum, int R, float* w,
+                                  float* counts, float gscale, const float* dscale, float* loss_out, void* logits_copy, long ldcopy,
+                                  int64_t* acc, vlb_stream_t stream);
+int vlb_ce_rowweight_eval(const void* logits, long ld, int rows, int V, const int64_t* labels, const int32_t* sel_pos, int B, int T,
+                          int B_split, const float* w, float* loss_out0, float* loss_out1, int64_t* acc0, int64_t* acc1,
+                          vlb_stream_t stream);
+int vlb_soft_ce_rowweight_eval(const void* logits, long ld, int rows, int C, const float* target, long ldt, float* tsum, int R, float* w,
+                               float* counts, float* loss_out, int64_t* acc, vlb_stream_t stream);
 
 /* ---- fine-tuning evaluation (csrc/finetune_metrics.hip): the metrics of common/metrics/{vqa,vcr,refcoco}_metrics.py and the
  * predictions of the test-set writers on the device.  All three read fp32 data only, synchronise nothing, allocate nothing and

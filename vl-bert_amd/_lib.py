@@ -69,6 +69,12 @@ _SIGS = {
     "vlb_soft_ce_fwd_bwd": "pliiplppfppplps",
     "vlb_ce_eval": "plii" + "p" * 8 + "s",
     "vlb_soft_ce_eval": "pliiplpps",
+    # per-sample loss normalisation (the *_LOSS_NORM_IN_BATCH_FIRST switches): sample weights + the row-weighted losses
+    "vlb_sample_norm_weights": "ppiiiippps",
+    "vlb_ce_rowweight_fwd_bwd": "pliippiiipfpppplpps",
+    "vlb_soft_ce_rowweight_fwd_bwd": "pliiplpippfppplps",
+    "vlb_ce_rowweight_eval": "pliippiiippppps",
+    "vlb_soft_ce_rowweight_eval": "pliiplpipppps",
     "vlb_argmax_eval": "pliiiplppplpps",
     "vlb_binary_cls_eval": "plpliips",
     "vlb_joint_hits": "ppppips",

@@ -15,7 +15,7 @@ void vlb_set_error(const char* fmt, ...) {
 
 extern "C" const char* vlb_last_error(void) { return g_err; }
 
-extern "C" int vlb_version(void) { return 200; }  // 0.2.0
+extern "C" int vlb_version(void) { return 300; }  // 0.3.0
 
 // 16-bit storage type this build of the library computes in (vlb_common.h): 0 = bfloat16 (libvlbert_hip.so), 1 = IEEE fp16
 // (libvlbert_hip_f16.so, -DVLB_ACT_F16).  Same entry points, same layouts; the host allocates its tensors accordingly.

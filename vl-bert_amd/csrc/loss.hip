@@ -549,3 +549,330 @@ extern "C" int vlb_dropout_bf16(const void* x, void* y, long n, float drop_p, co
   VLB_CHECK_LAUNCH("vlb_dropout_bf16");
   return VLB_OK;
 }
+
+// ------------------------------------------------------------------------------------------------------------------
+// Per-sample loss normalisation (NETWORK.MLM_LOSS_NORM_IN_BATCH_FIRST / MVRC_LOSS_NORM_IN_BATCH_FIRST,
+// pretrain/modules/resnet_vlbert_for_pretraining.py:168-174, 183-190; multitask :219-231, 252-259):
+//   loss = sum_b ( sum_t l_bt / (n_b + 1e-4) ) / ( #{b : n_b > 0} + 1e-4 )
+// with n_b the labelled tokens (valid regions) of sample b.  Every row of sample b therefore carries the one weight
+//   w[b] = 1 / ((n_b + 1e-4) (n_has + 1e-4))
+// and the fused loss kernels below are the ones above with `1 / n_valid` replaced by `w[s(r)]`, s(r) the sample of row r: one more
+// scalar load and one fp32 multiply per row.  The kernels above, their instantiations and their entry points are untouched; these
+// are launched only when a norm switch is on.
+//
+// sample_norm_weights_kernel: ONE 1024-thread block (a batch has a few hundred samples of at most 512 positions).  Wave v counts the
+// rows of samples v, v + 16, ... -- integers, so the order of the additions does not matter -- and leaves n_b in w[b]; after a
+// barrier the threads count, per group, the samples with n_b > 0 and the rows (integers again), and every w[b] is formed from
+// n_b and its group's n_has.  Hard labels ([B, T] int64, labelled iff 0 <= label < V): samples [0, B_split) are the caption group,
+// the rest the text-only group of the multitask wrapper, each with its own n_has.  Soft labels: tsum [B * T] of soft_valid_kernel,
+// valid iff |tsum - 1| < 0.1, one group.  count0 / count1 (nullable): the row totals of the two groups, WRITTEN -- the slots the
+// unweighted losses fill.  A sample without rows gets weight 0 (no row reads it).
+// ------------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(1024) void sample_norm_weights_kernel(const int64_t* __restrict__ labels, const float* __restrict__ tsum, int B,
+                                                                   int T, int V, int B_split, float* __restrict__ w,
+                                                                   float* __restrict__ count0, float* __restrict__ count1) {
+  __shared__ int sh[16 * 4];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  for (int b = wave; b < B; b += 16) {
+    int c = 0;
+    for (int t = lane; t < T; t += 64) {
+      const long i = (long)b * T + t;
+      if (labels) {
+        const int64_t l = labels[i];
+        c += (l >= 0 && l < V);
+      } else {
+        c += (fabsf(tsum[i] - 1.f) < 0.1f);
+      }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
+    if (lane == 0) w[b] = (float)c;
+  }
+  __syncthreads();      // (the block's own global writes are visible to it behind the barrier)
+  int has0 = 0, has1 = 0, tot0 = 0, tot1 = 0;
+  for (int b = tid; b < B; b += 1024) {
+    const int n = (int)w[b];
+    if (b < B_split) { has0 += (n > 0); tot0 += n; }
+    else { has1 += (n > 0); tot1 += n; }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    has0 += __shfl_xor(has0, o, 64);
+    has1 += __shfl_xor(has1, o, 64);
+    tot0 += __shfl_xor(tot0, o, 64);
+    tot1 += __shfl_xor(tot1, o, 64);
+  }
+  if (lane == 0) {
+    sh[wave * 4] = has0;
+    sh[wave * 4 + 1] = has1;
+    sh[wave * 4 + 2] = tot0;
+    sh[wave * 4 + 3] = tot1;
+  }
+  __syncthreads();      // (also: every n_b has been read before any w[b] is overwritten below -- each thread rewrites only what it read)
+  has0 = has1 = tot0 = tot1 = 0;
+#pragma unroll
+  for (int v = 0; v < 16; ++v) {
+    has0 += sh[v * 4];
+    has1 += sh[v * 4 + 1];
+    tot0 += sh[v * 4 + 2];
+    tot1 += sh[v * 4 + 3];
+  }
+  for (int b = tid; b < B; b += 1024) {
+    const float n = w[b];
+    const float nh = (float)(b < B_split ? has0 : has1);
+    w[b] = n > 0.f ? 1.f / ((n + 1e-4f) * (nh + 1e-4f)) : 0.f;
+  }
+  if (tid == 0) {
+    if (count0) *count0 = (float)tot0;
+    if (count1) *count1 = (float)tot1;
+  }
+}
+
+extern "C" int vlb_sample_norm_weights(const int64_t* labels, const float* tsum, int B, int T, int V, int B_split, float* w, float* count0,
+                                       float* count1, hipStream_t stream) {
+  if (B <= 0) return VLB_OK;
+  VLB_CHECK_ARG(w && (!labels != !tsum), "vlb_sample_norm_weights: needs w and exactly one of labels / tsum");
+  VLB_CHECK_ARG(T > 0 && B_split >= 0 && B_split <= B && (labels || B_split == B), "vlb_sample_norm_weights: bad sizes (B=%d T=%d B_split=%d)",
+                B, T, B_split);
+  hipLaunchKernelGGL(sample_norm_weights_kernel, dim3(1), dim3(1024), 0, stream, labels, tsum, B, T, V, B_split, w, count0, count1);
+  VLB_CHECK_LAUNCH("vlb_sample_norm_weights");
+  return VLB_OK;
+}
+
+// Row-weighted cross entropy, one block per row: ce_fwd_bwd_kernel with w[s(r)] for 1 / n_valid.  s(r) = pos(r) / T with pos the row
+// itself or, on the compacted MLM rows, sel_pos[r] (-1 behind the labelled rows: skipped like an unlabelled row) -- one kernel serves
+// both forms.  Samples s < B_split add to loss_out0 / acc0, the others to loss_out1 / acc1.  BWD = false is the forward-only twin of
+// eval_step(): the logits are only read, the weighted mean goes to the loss slot and the counters count as vlb_ce_eval does.
+// ACC: [hits, counted rows]; a counted row adds its own 1 (integer atomics: no dependence on arrival order), the weights do not enter.
+// (m, s) always go through block_online_reduce_as_plain: the instantiations of this kernel agree bit for bit among themselves.
+template <bool BWD, bool DS, bool ACC>
+__global__ __launch_bounds__(256) void ce_rowweight_kernel(bf16_t* __restrict__ logits, long ld, int V, const int64_t* __restrict__ labels,
+                                                           const int32_t* __restrict__ sel_pos, int B, int T, int B_split,
+                                                           const float* __restrict__ w, float gscale, float* __restrict__ loss_out0,
+                                                           float* __restrict__ loss_out1, bf16_t* __restrict__ logits_copy, long ldcopy,
+                                                           const float* __restrict__ dscale, vlb_u64* __restrict__ acc0,
+                                                           vlb_u64* __restrict__ acc1) {
+  if (DS) gscale = __fmul_rn(gscale, *dscale);
+  __shared__ float sh[16];
+  const int row = blockIdx.x;
+  bf16_t* x = logits + (long)row * ld;
+  const long label = labels[row];
+  const int ldv = (int)ld;
+  if (BWD && logits_copy) {
+    bf16_t* cp = logits_copy + (long)row * ldcopy;
+    for (int c = threadIdx.x * 8; c < V; c += 2048) {
+      if (c + 8 <= V) *(uint4*)(cp + c) = *(const uint4*)(x + c);
+      else for (int k = c; k < V; ++k) cp[k] = x[k];
+    }
+  }
+  const int pos = sel_pos ? sel_pos[row] : row;
+  const int smp = pos >= 0 ? pos / T : B;
+  if (label < 0 || label >= V || smp >= B) {  // ignore_index / padding of the compacted list: no loss, zero gradient row
+    if (BWD)
+      for (int c = threadIdx.x * 8; c < ldv; c += 2048) *(uint4*)(x + c) = make_uint4(0, 0, 0, 0);
+    return;
+  }
+  const bool second = smp >= B_split;
+  float* loss_out = second ? loss_out1 : loss_out0;
+  vlb_u64* acc = second ? acc1 : acc0;
+  const float wr = w[smp];
+  float m = -INFINITY, s = 0.f;
+  int idx = INT_MAX;      // (ACC) column of m; a thread's columns ascend, so `>` alone keeps its lowest column among equals
+  for (int c = threadIdx.x * 8; c < V; c += 2048) {
+    const uint4 q = *(const uint4*)(x + c);
+    const uint32_t ww[4] = {q.x, q.y, q.z, q.w};
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const float a = bflo(ww[k]), b = bfhi(ww[k]);
+      if (c + 2 * k < V) {
+        if (ACC && a > m) idx = c + 2 * k;
+        online_merge(m, s, a, 1.f);
+      }
+      if (c + 2 * k + 1 < V) {
+        if (ACC && b > m) idx = c + 2 * k + 1;
+        online_merge(m, s, b, 1.f);
+      }
+    }
+  }
+  if (ACC) {
+    float mv = m;
+    block_argmax(mv, idx, sh + 8);
+  }
+  block_online_reduce_as_plain(m, s, sh);
+  const float lse = m + __logf(s);
+  if (threadIdx.x == 0) {
+    atomicAdd(loss_out, (lse - bf2f(x[label])) * wr);
+    if (ACC) {
+      if (idx == (int)label) atomicAdd(acc, (vlb_u64)1);
+      atomicAdd(acc + 1, (vlb_u64)1);
+    }
+  }
+  if (!BWD) return;
+  const float sc = gscale * wr;
+  __syncthreads();  // x[label] read above before anyone overwrites it
+  for (int c = threadIdx.x * 8; c < ldv; c += 2048) {
+    const uint4 q = *(const uint4*)(x + c);
+    const uint32_t ww[4] = {q.x, q.y, q.z, q.w};
+    uint32_t o[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const int c0 = c + 2 * k, c1 = c0 + 1;
+      float g0 = (c0 < V) ? __expf(bflo(ww[k]) - lse) : 0.f;
+      float g1 = (c1 < V) ? __expf(bfhi(ww[k]) - lse) : 0.f;
+      if (c0 == label) g0 -= 1.f;
+      if (c1 == label) g1 -= 1.f;
+      o[k] = pack2bf(g0 * sc, g1 * sc);
+    }
+    *(uint4*)(x + c) = make_uint4(o[0], o[1], o[2], o[3]);
+  }
+}
+
+static int ce_rowweight_check(const char* who, const void* logits, long ld, int rows, int V, const void* labels, const void* sel_pos, int B, int T,
+                              int B_split, const void* w, const void* loss_out0, const void* loss_out1, const void* acc0, const void* acc1) {
+  VLB_CHECK_ARG(logits && labels && w && loss_out0, "%s: null argument", who);
+  VLB_CHECK_ARG(B > 0 && T > 0 && B_split >= 0 && B_split <= B, "%s: bad sizes (B=%d T=%d B_split=%d)", who, B, T, B_split);
+  VLB_CHECK_ARG(sel_pos || (long)rows <= (long)B * T, "%s: %d rows for %d samples of %d positions", who, rows, B, T);
+  VLB_CHECK_ARG(B_split == B || (loss_out1 && (!acc0 || acc1)), "%s: two groups need loss_out1 (and acc1 with acc0)", who);
+  VLB_CHECK_ARG(ld >= V && (ld % 8) == 0 && ((uintptr_t)logits % 16) == 0, "%s: ld=%ld must be >= V=%d and a multiple of 8, logits 16-byte aligned",
+                who, ld, V);
+  return VLB_OK;
+}
+
+// labels: per ROW ([B, T] flattened, or labels_c of vlb_mlm_compact together with its sel_pos); w: vlb_sample_norm_weights' output over
+// the B samples.  dscale, acc0 / acc1, logits_copy: nullable, as in vlb_ce_fwd_bwd.
+extern "C" int vlb_ce_rowweight_fwd_bwd(void* logits, long ld, int rows, int V, const int64_t* labels, const int32_t* sel_pos, int B, int T,
+                                        int B_split, const float* w, float gscale, const float* dscale, float* loss_out0, float* loss_out1,
+                                        void* logits_copy, long ldcopy, int64_t* acc0, int64_t* acc1, hipStream_t stream) {
+  if (rows <= 0) return VLB_OK;
+  if (ce_rowweight_check("vlb_ce_rowweight_fwd_bwd", logits, ld, rows, V, labels, sel_pos, B, T, B_split, w, loss_out0, loss_out1, acc0, acc1) !=
+      VLB_OK)
+    return VLB_ERR_ARG;
+  VLB_CHECK_ARG(!logits_copy || ldcopy >= V, "vlb_ce_rowweight_fwd_bwd: ldcopy too small");
+#define VLB_CE_RW(DS_, ACC_)                                                                                                                  \
+  hipLaunchKernelGGL((ce_rowweight_kernel<true, DS_, ACC_>), dim3(rows), dim3(256), 0, stream, (bf16_t*)logits, ld, V, labels, sel_pos, B, T, \
+                     B_split, w, gscale, loss_out0, loss_out1, (bf16_t*)logits_copy, ldcopy, dscale, (vlb_u64*)acc0, (vlb_u64*)acc1)
+  if (acc0) {
+    if (dscale) VLB_CE_RW(true, true);
+    else VLB_CE_RW(false, true);
+  } else {
+    if (dscale) VLB_CE_RW(true, false);
+    else VLB_CE_RW(false, false);
+  }
+#undef VLB_CE_RW
+  VLB_CHECK_LAUNCH("vlb_ce_rowweight_fwd_bwd");
+  return VLB_OK;
+}
+
+extern "C" int vlb_ce_rowweight_eval(const void* logits, long ld, int rows, int V, const int64_t* labels, const int32_t* sel_pos, int B, int T,
+                                     int B_split, const float* w, float* loss_out0, float* loss_out1, int64_t* acc0, int64_t* acc1,
+                                     hipStream_t stream) {
+  if (rows <= 0) return VLB_OK;
+  if (ce_rowweight_check("vlb_ce_rowweight_eval", logits, ld, rows, V, labels, sel_pos, B, T, B_split, w, loss_out0, loss_out1, acc0, acc1) != VLB_OK)
+    return VLB_ERR_ARG;
+  VLB_CHECK_ARG(acc0, "vlb_ce_rowweight_eval: null counters");
+  hipLaunchKernelGGL((ce_rowweight_kernel<false, false, true>), dim3(rows), dim3(256), 0, stream, (bf16_t*)const_cast<void*>(logits), ld, V, labels,
+                     sel_pos, B, T, B_split, w, 1.f, loss_out0, loss_out1, (bf16_t*)nullptr, 0L, (const float*)nullptr, (vlb_u64*)acc0,
+                     (vlb_u64*)acc1);
+  VLB_CHECK_LAUNCH("vlb_ce_rowweight_eval");
+  return VLB_OK;
+}
+
+// Row-weighted soft-label twin, s(r) = r / R: soft_ce_fwd_bwd_kernel with w[r / R] for 1 / n_valid; BWD = false only reads the logits.
+template <bool BWD, bool DS, bool ACC>
+__global__ __launch_bounds__(256) void soft_ce_rowweight_kernel(bf16_t* __restrict__ logits, long ld, int C, const float* __restrict__ target,
+                                                                long ldt, const float* __restrict__ tsum, int R, const float* __restrict__ w,
+                                                                float gscale, float* __restrict__ loss_out, bf16_t* __restrict__ logits_copy,
+                                                                long ldcopy, const float* __restrict__ dscale, vlb_u64* __restrict__ acc) {
+  __shared__ float sh[28];
+  if (DS) gscale = __fmul_rn(gscale, *dscale);
+  const int row = blockIdx.x;
+  bf16_t* x = logits + (long)row * ld;
+  const float* t = target + (long)row * ldt;
+  const int ldv = (int)ld;
+  if (BWD && logits_copy) {
+    bf16_t* cp = logits_copy + (long)row * ldcopy;
+    for (int c = threadIdx.x; c < C; c += 256) cp[c] = x[c];
+  }
+  const float ts = tsum[row];
+  if (!(fabsf(ts - 1.f) < 0.1f)) {
+    if (BWD)
+      for (int c = threadIdx.x; c < ldv; c += 256) x[c] = 0;
+    return;
+  }
+  const float wr = w[row / R];
+  float m = -INFINITY, s = 0.f, dot = 0.f, tm = -INFINITY;
+  int xi = INT_MAX, ti = INT_MAX;      // (ACC) ascending columns per thread: `>` keeps the lowest among equals
+  for (int c = threadIdx.x; c < C; c += 256) {
+    const float v = bf2f(x[c]), tv = t[c];
+    if (ACC) {
+      if (v > m) xi = c;
+      if (tv > tm) { tm = tv; ti = c; }
+    }
+    online_merge(m, s, v, 1.f);
+    dot += tv * v;
+  }
+  if (ACC) {
+    float mv = m;
+    block_argmax(mv, xi, sh + 12);
+    block_argmax(tm, ti, sh + 20);
+    if (threadIdx.x == 0) {
+      if (xi == ti) atomicAdd(acc, (vlb_u64)1);
+      atomicAdd(acc + 1, (vlb_u64)1);
+    }
+  }
+  block_online_reduce_as_plain(m, s, sh);
+  dot = block_sum(dot, sh + 8);
+  const float lse = m + __logf(s);
+  if (threadIdx.x == 0) atomicAdd(loss_out, (lse * ts - dot) * wr);
+  if (!BWD) return;
+  const float sc = gscale * wr;
+  for (int c = threadIdx.x; c < ldv; c += 256) {
+    float g = 0.f;
+    if (c < C) g = (__expf(bf2f(x[c]) - lse) * ts - t[c]) * sc;
+    x[c] = f2bf(g);
+  }
+}
+
+// rows = B * R regions; tsum [rows] and w [B] are written here (row validity, then vlb_sample_norm_weights' arithmetic on it), counts[0]
+// = the valid rows as vlb_soft_ce_fwd_bwd leaves it.  dscale, acc, logits_copy: nullable, as in vlb_soft_ce_fwd_bwd.
+extern "C" int vlb_soft_ce_rowweight_fwd_bwd(void* logits, long ld, int rows, int C, const float* target, long ldt, float* tsum, int R, float* w,
+                                             float* counts, float gscale, const float* dscale, float* loss_out, void* logits_copy, long ldcopy,
+                                             int64_t* acc, hipStream_t stream) {
+  if (rows <= 0) return VLB_OK;
+  VLB_CHECK_ARG(logits && target && tsum && w && counts && loss_out, "vlb_soft_ce_rowweight_fwd_bwd: null argument");
+  VLB_CHECK_ARG(ld >= C && ldt >= C && R > 0 && rows % R == 0, "vlb_soft_ce_rowweight_fwd_bwd: bad leading dimensions or rows %% R != 0");
+  VLB_CHECK_ARG(!logits_copy || ldcopy >= C, "vlb_soft_ce_rowweight_fwd_bwd: ldcopy too small");
+  (void)hipMemsetAsync(counts, 0, sizeof(float), stream);
+  hipLaunchKernelGGL(soft_valid_kernel, dim3(vlb_cdiv(rows, 4)), dim3(256), 0, stream, target, ldt, C, rows, tsum, counts);
+  hipLaunchKernelGGL(sample_norm_weights_kernel, dim3(1), dim3(1024), 0, stream, (const int64_t*)nullptr, (const float*)tsum, rows / R, R, 0,
+                     rows / R, w, (float*)nullptr, (float*)nullptr);
+#define VLB_SOFT_RW(DS_, ACC_)                                                                                                             \
+  hipLaunchKernelGGL((soft_ce_rowweight_kernel<true, DS_, ACC_>), dim3(rows), dim3(256), 0, stream, (bf16_t*)logits, ld, C, target, ldt,  \
+                     (const float*)tsum, R, (const float*)w, gscale, loss_out, (bf16_t*)logits_copy, ldcopy, dscale, (vlb_u64*)acc)
+  if (acc) {
+    if (dscale) VLB_SOFT_RW(true, true);
+    else VLB_SOFT_RW(false, true);
+  } else {
+    if (dscale) VLB_SOFT_RW(true, false);
+    else VLB_SOFT_RW(false, false);
+  }
+#undef VLB_SOFT_RW
+  VLB_CHECK_LAUNCH("vlb_soft_ce_rowweight_fwd_bwd");
+  return VLB_OK;
+}
+
+extern "C" int vlb_soft_ce_rowweight_eval(const void* logits, long ld, int rows, int C, const float* target, long ldt, float* tsum, int R, float* w,
+                                          float* counts, float* loss_out, int64_t* acc, hipStream_t stream) {
+  if (rows <= 0) return VLB_OK;
+  VLB_CHECK_ARG(logits && target && tsum && w && counts && loss_out && acc, "vlb_soft_ce_rowweight_eval: null argument");
+  VLB_CHECK_ARG(ld >= C && ldt >= C && R > 0 && rows % R == 0, "vlb_soft_ce_rowweight_eval: bad leading dimensions or rows %% R != 0");
+  (void)hipMemsetAsync(counts, 0, sizeof(float), stream);
+  hipLaunchKernelGGL(soft_valid_kernel, dim3(vlb_cdiv(rows, 4)), dim3(256), 0, stream, target, ldt, C, rows, tsum, counts);
+  hipLaunchKernelGGL(sample_norm_weights_kernel, dim3(1), dim3(1024), 0, stream, (const int64_t*)nullptr, (const float*)tsum, rows / R, R, 0,
+                     rows / R, w, (float*)nullptr, (float*)nullptr);
+  hipLaunchKernelGGL((soft_ce_rowweight_kernel<false, false, true>), dim3(rows), dim3(256), 0, stream, (bf16_t*)const_cast<void*>(logits), ld, C,
+                     target, ldt, (const float*)tsum, R, (const float*)w, 1.f, loss_out, (bf16_t*)nullptr, 0L, (const float*)nullptr,
+                     (vlb_u64*)acc);
+  VLB_CHECK_LAUNCH("vlb_soft_ce_rowweight_eval");
+  return VLB_OK;
+}

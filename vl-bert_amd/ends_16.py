@@ -49,7 +49,16 @@ class PretrainFront16:
         self.d_yds = zb(BR, H)
         self.d_afeat = zb(BR, VIS_DIM)
         self.x0 = eng.encoder.x_in
-        self.g_ling_table = eng.P.view(eng.P.grad, "object_linguistic_embeddings.weight", (2, H), span=2)
+        if cfg.with_mvrc_loss:
+            self.ling_idx = eng.in_mvrc_ops
+            self.g_ling_table = eng.P.view(eng.P.grad, "object_linguistic_embeddings.weight", (2, H), span=2)
+        else:
+            # without the MVRC loss there is no object_mask_word_embedding (resnet_vlbert_for_pretraining.py:26-27, 140-141): every
+            # region reads row 0 of the table, through an all-zero selector in place of mvrc_ops.  embed_bwd writes a two-row table
+            # gradient whatever the selector holds, and the flat gradient has one row here: it gets a two-row scratch table of its own,
+            # whose row 0 front_bwd adds to the parameter's gradient (row 1 takes nothing and is never read)
+            self.ling_idx = torch.zeros_like(eng.in_mvrc_ops)
+            self.g_ling_scratch = self.g_ling_table = zf(2, H)
 
     def transposes(self):
         n = "image_feature_extractor.obj_downsample.1.weight"
@@ -91,7 +100,7 @@ class PretrainFront16:
                               w32["vlbert.visual_ln_text.bias"], self.textvis[B:], self.st_textvis[B:], rows=Ba, ldx=0)
         ops.embed_fwd(e.lay, e.in_text, None, w16["vlbert.word_embeddings.weight"], w16["vlbert.position_embeddings.weight"],
                       w16["vlbert.token_type_embeddings.weight"], w16["vlbert.end_embedding.weight"], self.textvis, (H, 0),
-                      self.objvis, (R * H, H), w16["object_linguistic_embeddings.weight"], (0, 0), e.in_mvrc_ops,
+                      self.objvis, (R * H, H), w16["object_linguistic_embeddings.weight"], (0, 0), self.ling_idx,
                       w32["vlbert.embedding_LayerNorm.weight"], w32["vlbert.embedding_LayerNorm.bias"], self.emb_pre, self.st_emb,
                       self.x0, Bt, T, R, S, H, drop_p=p_h, seed=seed, tag=TAG_EMBED)
 
@@ -104,11 +113,16 @@ class PretrainFront16:
         self.d_obj_reps.zero_()
         self.d_textvis.zero_()
         pe = "vlbert.embedding_LayerNorm."
-        ops.embed_bwd(dx, self.emb_pre, self.st_emb, w32[pe + "weight"], e.lay, e.in_text, None, e.in_mvrc_ops,
+        scratch = getattr(self, "g_ling_scratch", None)
+        if scratch is not None:
+            scratch.zero_()
+        ops.embed_bwd(dx, self.emb_pre, self.st_emb, w32[pe + "weight"], e.lay, e.in_text, None, self.ling_idx,
                       g32["vlbert.word_embeddings.weight"], g32["vlbert.position_embeddings.weight"],
                       g32["vlbert.token_type_embeddings.weight"], g32["vlbert.end_embedding.weight"], g32[pe + "weight"],
                       g32[pe + "bias"], self.d_textvis, (H, 0), self.d_objvis, (R * H, H), self.g_ling_table, (0, 0), Bt, T, R, S, H,
                       drop_p=p_h, seed=seed, tag=TAG_EMBED, text_vis_zeroed=True)
+        if scratch is not None:
+            ops.add_rows_f32(g32["object_linguistic_embeddings.weight"], scratch[:1])
         if on_layer_done:      # the tied word-embedding gradient (decoder wgrad + this scatter-add) is complete: its 94 MB go out first
             on_layer_done("word_emb")
         ops.layernorm_bwd(self.d_objvis, self.obj_reps, self.st_objvis, w32["vlbert.visual_ln_object.weight"],

@@ -56,6 +56,16 @@ class ModelConfig:
     e2e: bool = False            # IMAGE_FEAT_PRECOMPUTED false: ResNet trunk -> ROIAlign -> layer4 head on the device (vision.py)
     image_num_layers: int = 101  # NETWORK.IMAGE_NUM_LAYERS (50 / 101 / 152)
     image_frozen_stages: tuple = (1, 2)   # NETWORK.IMAGE_FROZEN_BACKBONE_STAGES (BatchNorm is always frozen: IMAGE_FROZEN_BN)
+    # objective switches (NETWORK.WITH_MLM_LOSS / WITH_MVRC_LOSS / *_LOSS_NORM_IN_BATCH_FIRST): an absent loss takes its head and the
+    # parameters only it reads out of the model; norm in batch first = per-sample means (objectives_16.py).  The defaults change nothing
+    with_mlm_loss: bool = True
+    with_mvrc_loss: bool = True
+    mlm_norm_in_batch_first: bool = False
+    mvrc_norm_in_batch_first: bool = False
+
+    @property
+    def default_objective(self):
+        return self.with_mlm_loss and self.with_mvrc_loss and not (self.mlm_norm_in_batch_first or self.mvrc_norm_in_batch_first)
 
     def validate(self):
         H, nh = self.hidden_size, self.num_attention_heads
@@ -65,6 +75,8 @@ class ModelConfig:
             raise ValueError("intermediate_size must be a multiple of 64")
         if self.with_rel_loss and not self.with_pooler:
             raise ValueError("with_rel_loss needs with_pooler (the relationship head reads the pooled output)")
+        if not (self.with_mlm_loss or self.with_mvrc_loss or self.with_rel_loss):
+            raise ValueError("with_mlm_loss=False and with_mvrc_loss=False need with_rel_loss: there would be no loss to train on")
 
 
 def param_layout(cfg):
@@ -78,7 +90,8 @@ def param_layout(cfg):
     s["vlbert.token_type_embeddings.weight"] = (cfg.type_vocab_size, H)
     s["vlbert.end_embedding.weight"] = (1, H)
     s["object_linguistic_embeddings.weight"] = (1, H)
-    s["object_mask_word_embedding.weight"] = (1, H)
+    if cfg.with_mvrc_loss:     # resnet_vlbert_for_pretraining.py:26-27
+        s["object_mask_word_embedding.weight"] = (1, H)
     if cfg.multitask:
         s["aux_text_visual_embedding.weight"] = (1, H)     # resnet_vlbert_for_pretraining_multitask.py:28
     s["object_mask_visual_embedding.weight"] = (1, VIS_DIM)
@@ -109,16 +122,18 @@ def param_layout(cfg):
     if cfg.with_rel_loss:       # [sic] the typo is part of the reference's key (common/visual_linguistic_bert.py:322)
         s["vlbert.relationsip_head.caption_image_relationship.weight"] = (2, H)
         s["vlbert.relationsip_head.caption_image_relationship.bias"] = (2,)
-    p = "vlbert.mlm_head.predictions."
-    s[p + "transform.dense.weight"] = (H, H)
-    s[p + "transform.dense.bias"] = (H,)
-    s[p + "transform.LayerNorm.weight"] = (H,)
-    s[p + "transform.LayerNorm.bias"] = (H,)
-    s[p + "bias"] = (V,)
-    s["vlbert.mvrc_head.transform.dense.weight"] = (H, H)
-    s["vlbert.mvrc_head.transform.dense.bias"] = (H,)
-    s["vlbert.mvrc_head.region_cls_pred.weight"] = (C, H)
-    s["vlbert.mvrc_head.region_cls_pred.bias"] = (C,)
+    if cfg.with_mlm_loss:      # common/visual_linguistic_bert.py:323-326: a head exists only with its loss
+        p = "vlbert.mlm_head.predictions."
+        s[p + "transform.dense.weight"] = (H, H)
+        s[p + "transform.dense.bias"] = (H,)
+        s[p + "transform.LayerNorm.weight"] = (H,)
+        s[p + "transform.LayerNorm.bias"] = (H,)
+        s[p + "bias"] = (V,)
+    if cfg.with_mvrc_loss:
+        s["vlbert.mvrc_head.transform.dense.weight"] = (H, H)
+        s["vlbert.mvrc_head.transform.dense.bias"] = (H,)
+        s["vlbert.mvrc_head.region_cls_pred.weight"] = (C, H)
+        s["vlbert.mvrc_head.region_cls_pred.bias"] = (C,)
     if cfg.e2e:      # trainable convolution weights of the vision path, LAST (their gradients complete last; parallel.GradBuckets)
         from .vision import vision_param_layout
         s.update(vision_param_layout(cfg.image_num_layers, cfg.image_frozen_stages))
@@ -196,6 +211,9 @@ class PretrainEngine:
         if not (isinstance(max_seq, int) and 256 <= max_seq <= MAX_SEQ):
             raise ValueError("max_seq must be an integer in 256..%d (got %r)" % (MAX_SEQ, max_seq))
         self.max_seq = max_seq
+        if core and not cfg.default_objective:
+            raise ValueError("the objective switches (with_mlm_loss / with_mvrc_loss / *_norm_in_batch_first) belong to the pre-training "
+                             "engine: core=True (the module-API engine) computes no loss and always carries both heads")
         if cfg.e2e and (core or image_size is None):
             raise ValueError("e2e needs image_size=(H, W) and a pretraining wrapper (plain or multitask; not the core module mode)")
         # lr_schedule: None (host sets lr) | "constant" | "warmup_constant" | "triangle" (WarmupLinearSchedule,
@@ -321,7 +339,7 @@ class PretrainEngine:
         # the engine (set_batch decides per batch); the heads -- 16-bit or fp32 -- own the buffers that go with it
         BT = self.BT
         cap = min(self.BTp, max(256, _ru(int(math.ceil(0.20 * BT)), 256)))
-        want = os.environ.get("VLB_MLM_COMPACT", "1") != "0" and not keep_logits and not core and cap < BT
+        want = os.environ.get("VLB_MLM_COMPACT", "1") != "0" and not keep_logits and not core and cap < BT and cfg.with_mlm_loss
         self.mlm_cap = cap if want else None
         self._mlm_compact_now = want
 
@@ -395,7 +413,11 @@ class PretrainEngine:
         else:
             from .ends_16 import CoreFront16, Heads16, PretrainFront16
             self.front = CoreFront16(self) if core else PretrainFront16(self, image_size)
-            self.back = Heads16(self)
+            if cfg.default_objective:
+                self.back = Heads16(self)
+            else:      # a head left out, or per-sample loss means: the heads as a part of their own
+                from .objectives_16 import ObjectiveHeads16
+                self.back = ObjectiveHeads16(self)
             self.vision = None if core else self.front.vision
             self.wT.update(self.back.wT)
             self.wT.update(self.front.wT)
@@ -458,6 +480,8 @@ class PretrainEngine:
             bad.append("B_aux > 0 (multitask text-only samples)")
         if cfg.with_pooler or cfg.with_rel_loss:
             bad.append("with_pooler / with_rel_loss (the pooler and the relationship head and loss)")
+        if not cfg.default_objective:
+            bad.append("with_mlm_loss / with_mvrc_loss off or a *_norm_in_batch_first switch (the objective switches)")
         if dp_mode == "sharded":
             bad.append("dp_mode='sharded' (the sharded optimizer)")
         if loss_scale is not None and (LS.resolve(loss_scale) is not None or float(loss_scale) != 1.0):
@@ -504,7 +528,8 @@ class PretrainEngine:
             self.buckets.gather_master(self.P.master)
         vis = self._vision_names()
         sd = OrderedDict((k, v.detach().clone()) for k, v in self.w32.items() if k not in vis)
-        sd[TIED_DECODER_KEY] = sd["vlbert.word_embeddings.weight"]
+        if self.cfg.with_mlm_loss:      # (the decoder lives in the MLM head)
+            sd[TIED_DECODER_KEY] = sd["vlbert.word_embeddings.weight"]
         if self.vision is not None:
             sd.update(self.vision.state_dict())
         return sd

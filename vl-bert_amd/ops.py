@@ -447,6 +447,53 @@ def soft_ce_eval(logits, C, target, loss_out, acc):
               _p(loss_out, torch.float32), _p(acc, torch.int64), _stream())
 
 
+def sample_norm_weights(w, T, labels=None, tsum=None, V=0, B_split=None, count0=None, count1=None):
+    """w [B] = 1 / ((n_b + 1e-4) (n_has + 1e-4)), the per-sample weights of the *_LOSS_NORM_IN_BATCH_FIRST losses, from hard labels
+    ([B * T] int64, labelled iff 0 <= label < V; samples from B_split on are a group of their own) or from tsum ([B * T] fp32, valid iff
+    |tsum - 1| < 0.1).  count0 / count1 (optional) receive the labelled rows of the two groups (vlb_sample_norm_weights)."""
+    B = w.numel()
+    if (labels is None) == (tsum is None):
+        raise ValueError("sample_norm_weights: exactly one of labels / tsum")
+    if (labels if labels is not None else tsum).numel() != B * T:
+        raise ValueError("sample_norm_weights: %d samples of %d rows need %d entries" % (B, T, B * T))
+    _lib.call("vlb_sample_norm_weights", _p(labels, torch.int64), _p(tsum, torch.float32), B, int(T), int(V),
+              B if B_split is None else int(B_split), _p(w, torch.float32), _p(count0, torch.float32), _p(count1, torch.float32), _stream())
+    return w
+
+
+def ce_rowweight_fwd_bwd(logits, V, labels, w, T, loss_out, B_split=None, loss_out1=None, sel_pos=None, gscale=1.0, logits_copy=None,
+                         dscale=None, acc=None, acc1=None):
+    """ce_fwd_bwd with the per-sample weights w [B] in place of 1 / n_valid: row r belongs to sample pos(r) // T, pos(r) = r or
+    sel_pos[r] (the compacted rows of mlm_compact).  Samples from B_split on add to loss_out1 / acc1 (vlb_ce_rowweight_fwd_bwd)."""
+    B = w.numel()
+    _lib.call("vlb_ce_rowweight_fwd_bwd", _p(logits, BF16), _ld(logits), logits.shape[0], int(V), _p(labels, torch.int64),
+              _p(sel_pos, torch.int32), B, int(T), B if B_split is None else int(B_split), _p(w, torch.float32), float(gscale),
+              _p(dscale, torch.float32), _p(loss_out, torch.float32), _p(loss_out1, torch.float32), _p(logits_copy, BF16), _ld(logits_copy),
+              _p(acc, torch.int64), _p(acc1, torch.int64), _stream())
+
+
+def soft_ce_rowweight_fwd_bwd(logits, C, target, tsum, w, R, counts, loss_out, gscale=1.0, logits_copy=None, dscale=None, acc=None):
+    """soft_ce_fwd_bwd with per-sample weights: tsum [rows] and w [rows / R] are written on the way (vlb_soft_ce_rowweight_fwd_bwd)."""
+    _lib.call("vlb_soft_ce_rowweight_fwd_bwd", _p(logits, BF16), _ld(logits), logits.shape[0], int(C), _p(target, torch.float32), _ld(target),
+              _p(tsum, torch.float32), int(R), _p(w, torch.float32), _p(counts, torch.float32), float(gscale), _p(dscale, torch.float32),
+              _p(loss_out, torch.float32), _p(logits_copy, BF16), _ld(logits_copy), _p(acc, torch.int64), _stream())
+
+
+def ce_rowweight_eval(logits, V, labels, w, T, loss_out, acc, B_split=None, loss_out1=None, acc1=None, sel_pos=None):
+    """Forward-only twin of ce_rowweight_fwd_bwd: the logits are only read (vlb_ce_rowweight_eval)."""
+    B = w.numel()
+    _lib.call("vlb_ce_rowweight_eval", _p(logits, BF16), _ld(logits), logits.shape[0], int(V), _p(labels, torch.int64), _p(sel_pos, torch.int32),
+              B, int(T), B if B_split is None else int(B_split), _p(w, torch.float32), _p(loss_out, torch.float32),
+              _p(loss_out1, torch.float32), _p(acc, torch.int64), _p(acc1, torch.int64), _stream())
+
+
+def soft_ce_rowweight_eval(logits, C, target, tsum, w, R, counts, loss_out, acc):
+    """Forward-only twin of soft_ce_rowweight_fwd_bwd (vlb_soft_ce_rowweight_eval)."""
+    _lib.call("vlb_soft_ce_rowweight_eval", _p(logits, BF16), _ld(logits), logits.shape[0], int(C), _p(target, torch.float32), _ld(target),
+              _p(tsum, torch.float32), int(R), _p(w, torch.float32), _p(counts, torch.float32), _p(loss_out, torch.float32),
+              _p(acc, torch.int64), _stream())
+
+
 ARGMAX_PREDICT, ARGMAX_HARD, ARGMAX_GATHER, ARGMAX_GATHER_GT = 0, 1, 2, 3
 
 

@@ -116,7 +116,9 @@ class GradBuckets:
         self.wire = torch.zeros(numel, dtype=self.wire_dtype, device=flat_grad.device) if self.wire_dtype is not None else None
         names = list(offsets)
         layer_start = [offsets["vlbert.encoder.layer.%d.attention.self.query.weight" % l] for l in range(num_layers)]
-        head_start = offsets["vlbert.mlm_head.predictions.transform.dense.weight"]
+        # the first loss head the model has (an objective variant may lack the MLM or the MVRC head; validate() leaves at least one loss)
+        head_start = next(offsets[n] for n in ("vlbert.mlm_head.predictions.transform.dense.weight", "vlbert.mvrc_head.transform.dense.weight",
+                                               "vlbert.relationsip_head.caption_image_relationship.weight") if n in offsets)
         tail = numel if vision_start is None else vision_start
         front_end = layer_start[0] if num_layers else head_start
         we_end = offsets["vlbert.position_embeddings.weight"]      # the word-embedding table is first in the layout

@@ -78,8 +78,13 @@ class ResNetVLBERTForPretraining(nn.Module):
             raise ValueError("WITH_REL_LOSS needs VLBERT.with_pooler (the relationship head reads the pooled output)")
         if self.with_rel and self.MULTITASK:
             raise NotImplementedError("relationship loss in the multitask wrapper is not supported")
-        if not (_get(net, "WITH_MLM_LOSS", True) and _get(net, "WITH_MVRC_LOSS", True) and _get(vl, "visual_ln", True)):
-            raise NotImplementedError("accelerated path needs WITH_MLM_LOSS, WITH_MVRC_LOSS and visual_ln")
+        if not _get(vl, "visual_ln", True):
+            raise NotImplementedError("accelerated path needs visual_ln")
+        # the objective switches (:26-27, 140-141, 164-200): a loss that is off takes its head and its parameters out of the model
+        self.with_mlm, self.with_mvrc = bool(_get(net, "WITH_MLM_LOSS", True)), bool(_get(net, "WITH_MVRC_LOSS", True))
+        if self.MULTITASK and not self.with_mlm:
+            raise NotImplementedError("the multitask wrapper without WITH_MLM_LOSS: the text-only samples feed the MLM loss alone (the "
+                                      "reference's forward fails there too, resnet_vlbert_for_pretraining_multitask.py:205,283)")
         if _get(net, "IMAGE_SEMANTIC", False) or _get(vl, "word_embedding_frozen", False) or _get(vl, "pos_embedding_frozen", False):
             raise NotImplementedError("IMAGE_SEMANTIC / frozen embeddings are not supported")
         if _get(vl, "visual_size", _get(vl, "hidden_size")) != _get(vl, "hidden_size"):
@@ -93,7 +98,10 @@ class ResNetVLBERTForPretraining(nn.Module):
             attention_probs_dropout_prob=_get(vl, "attention_probs_dropout_prob", 0.1), multitask=self.MULTITASK,
             with_pooler=bool(_get(vl, "with_pooler", False)), with_rel_loss=self.with_rel, e2e=self.e2e,
             image_num_layers=int(_get(net, "IMAGE_NUM_LAYERS", 101)),
-            image_frozen_stages=tuple(_get(net, "IMAGE_FROZEN_BACKBONE_STAGES", (1, 2))))
+            image_frozen_stages=tuple(_get(net, "IMAGE_FROZEN_BACKBONE_STAGES", (1, 2))),
+            with_mlm_loss=self.with_mlm, with_mvrc_loss=self.with_mvrc,
+            mlm_norm_in_batch_first=self.with_mlm and bool(_get(net, "MLM_LOSS_NORM_IN_BATCH_FIRST", False)),
+            mvrc_norm_in_batch_first=self.with_mvrc and bool(_get(net, "MVRC_LOSS_NORM_IN_BATCH_FIRST", False)))
         self.cfg.validate()
         self.fp32_full = bool(_get(vl, "fp32_full", False)) or os.environ.get("VLB_FP32_FULL", "0") == "1"
         if self.fp32_full:
@@ -106,6 +114,8 @@ class ResNetVLBERTForPretraining(nn.Module):
                 bad.append("the multitask wrapper (text-only samples)")
             if self.cfg.with_pooler or self.with_rel:
                 bad.append("with_pooler / WITH_REL_LOSS")
+            if not self.cfg.default_objective:
+                bad.append("the objective switches (WITH_MLM_LOSS / WITH_MVRC_LOSS false, *_LOSS_NORM_IN_BATCH_FIRST)")
             if bad:
                 raise NotImplementedError("fp32_full is built for the precomputed-feature MLM + MVRC configuration on the fp32 encoder; "
                                           "unsupported here: " + "; ".join(bad))
@@ -147,8 +157,8 @@ class ResNetVLBERTForPretraining(nn.Module):
         from ...common import language_pretrained as _lp
         sd = torch.load(language_pretrained_model_path, map_location=lambda storage, loc: storage)
         own = {n[len("vlbert."):]: p for n, p in self._pnames.items() if n.startswith("vlbert.")}
-        assign, unexpected = _lp.plan(sd, list(own) + ["mlm_head.predictions.decoder.weight"], self.cfg.with_pooler, pretraining=True,
-                                      with_rel_head=self.with_rel, with_mlm_head=True)
+        assign, unexpected = _lp.plan(sd, list(own) + (["mlm_head.predictions.decoder.weight"] if self.with_mlm else []), self.cfg.with_pooler,
+                                      pretraining=True, with_rel_head=self.with_rel, with_mlm_head=self.with_mlm)
         if len(unexpected) > 0:
             print("Warnings: Unexpected keys: {}.".format(unexpected))
         _lp.apply(assign, own)
@@ -201,7 +211,8 @@ class ResNetVLBERTForPretraining(nn.Module):
     def state_dict(self, *args, **kwargs):
         sd = super().state_dict(*args, **kwargs)
         prefix = kwargs.get("prefix", args[1] if len(args) > 1 else "")
-        sd[prefix + _engine.TIED_DECODER_KEY] = sd[prefix + "vlbert.word_embeddings.weight"]   # tied (modeling.py:463-466)
+        if self.with_mlm:
+            sd[prefix + _engine.TIED_DECODER_KEY] = sd[prefix + "vlbert.word_embeddings.weight"]   # tied (modeling.py:463-466)
         if self.e2e:      # trainable convolutions: engine layout [O,KH,KW,I] -> reference layout [O,I,KH,KW]
             for name in self._vision_names:
                 sd[prefix + name] = sd[prefix + name].permute(0, 3, 1, 2).contiguous()
@@ -247,6 +258,8 @@ class ResNetVLBERTForPretraining(nn.Module):
     def _padded_logits(self, eng, Bt):
         """fp32 logits re-padded like the reference (:165-167, :195-200) -- needs max_len (host sync)."""
         V, C = self.cfg.vocab_size, self.cfg.visual_region_classes
+        if not (self.with_mlm and self.with_mvrc):      # an absent head has no logits: None, as the reference returns (:203-208)
+            return self._padded_present_logits(eng, Bt)
         if self.fp32_full:      # the engine's kept copies are fp32: no cast
             mlm_logits = eng.mlm_logits_copy[:, :V].reshape(Bt, eng.T, V).clone()
             mvrc = eng.mvrc_logits_copy[:, :C].reshape(eng.B, eng.R, C).clone()
@@ -261,6 +274,22 @@ class ResNetVLBERTForPretraining(nn.Module):
         seq_max = int((eng.lay["text_len"][:Bt] + eng.lay["nobj"][:Bt]).max()) + 1
         if seq_max < eng.T:
             mlm_logits[:, seq_max:] = -10000.0
+        return mlm_logits, mvrc
+
+    def _padded_present_logits(self, eng, Bt):
+        """_padded_logits with one head absent (16-bit engines only): None in its place."""
+        V, C = self.cfg.vocab_size, self.cfg.visual_region_classes
+        mlm_logits = mvrc = None
+        if self.with_mlm:
+            mlm_logits = torch.empty((Bt, eng.T, V), dtype=torch.float32, device=self.device_)
+            ops.cast_bf16_f32(eng.mlm_logits_copy[:, :V].contiguous(), mlm_logits)
+            seq_max = int((eng.lay["text_len"][:Bt] + eng.lay["nobj"][:Bt]).max()) + 1
+            if seq_max < eng.T:
+                mlm_logits[:, seq_max:] = -10000.0
+        if self.with_mvrc:
+            mvrc = torch.empty((eng.B, eng.R, C), dtype=torch.float32, device=self.device_)
+            ops.cast_bf16_f32(eng.mvrc_logits_copy[:, :C].contiguous(), mvrc)
+            mvrc[:, int(eng.lay["nobj"][:eng.B].max()):] = -10000.0
         return mlm_logits, mvrc
 
     @staticmethod
@@ -289,12 +318,12 @@ class ResNetVLBERTForPretraining(nn.Module):
         eng.forward(train=self.training)
         loss = _HipLoss.apply(self._pnames["vlbert.word_embeddings.weight"], self, eng)
         mlm_logits, mvrc = self._padded_logits(eng, B)
-        mlm_logits, mvrc = mlm_logits[:, :T], mvrc[:, :R]
+        mlm_logits, mvrc = (mlm_logits[:, :T] if self.with_mlm else None), (mvrc[:, :R] if self.with_mvrc else None)
         outputs = {
             "relationship_logits": eng.rel_logits_copy[:, :2].float() if self.with_rel else None,
             "relationship_label": relationship_label if self.with_rel else None,
-            "mlm_logits": mlm_logits, "mlm_label": mlm_labels,
-            "mvrc_logits": mvrc, "mvrc_label": mvrc_labels,
+            "mlm_logits": mlm_logits, "mlm_label": mlm_labels if self.with_mlm else None,
+            "mvrc_logits": mvrc, "mvrc_label": mvrc_labels if self.with_mvrc else None,
             "relationship_loss": eng.losses[3].clone() if self.with_rel else im_info.new_zeros(()),
             "mlm_loss": eng.losses[0].clone(), "mvrc_loss": eng.losses[1].clone(),
         }
@@ -336,13 +365,13 @@ class ResNetVLBERTForPretrainingMultitask(ResNetVLBERTForPretraining):
         eng.forward(train=self.training)
         loss = _HipLoss.apply(self._pnames["vlbert.word_embeddings.weight"], self, eng)
         mlm_logits, mvrc = self._padded_logits(eng, B + Ba)
-        mlm_logits, mvrc = mlm_logits[:, :T], mvrc[:, :R]
+        mlm_logits, mvrc = mlm_logits[:, :T], (mvrc[:, :R] if self.with_mvrc else None)
         lab = eng.in_mlm_labels[:, :T]
         outputs = {
             "relationship_logits": None, "relationship_label": None,
             "mlm_logits_wvc": mlm_logits[:B], "mlm_label_wvc": lab[:B].clone(),
             "mlm_logits_aux": mlm_logits[B:], "mlm_label_aux": lab[B:].clone(),
-            "mvrc_logits": mvrc, "mvrc_label": mvrc_labels,
+            "mvrc_logits": mvrc, "mvrc_label": mvrc_labels if self.with_mvrc else None,
             "relationship_loss": im_info.new_zeros(()), "mlm_loss_wvc": eng.losses[0].clone(),
             "mlm_loss_aux": eng.losses[2].clone(), "mvrc_loss": eng.losses[1].clone(),
         }

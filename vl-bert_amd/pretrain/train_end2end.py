@@ -52,7 +52,8 @@ DEFAULTS = {
     "OUTPUT_PATH": "", "MODEL_PREFIX": "", "CHECKPOINT_FREQUENT": 1,
     "NETWORK": {"IMAGE_FEAT_PRECOMPUTED": True, "IMAGE_NUM_LAYERS": 101, "IMAGE_C5_DILATED": True, "IMAGE_STRIDE_IN_1x1": True,
                 "IMAGE_FROZEN_BACKBONE_STAGES": [1, 2], "IMAGE_FROZEN_BN": True, "IMAGE_SEMANTIC": False, "OUTPUT_CONV5": False,
-                "WITH_REL_LOSS": False, "WITH_MLM_LOSS": True, "WITH_MVRC_LOSS": True, "VLBERT": {}},
+                "WITH_REL_LOSS": False, "WITH_MLM_LOSS": True, "WITH_MVRC_LOSS": True, "MLM_LOSS_NORM_IN_BATCH_FIRST": False,
+                "MVRC_LOSS_NORM_IN_BATCH_FIRST": False, "VLBERT": {}},
     "TRAIN": {"BATCH_IMAGES": 64, "LR": 1.0e-7, "WD": 1.0e-4, "CLIP_GRAD_NORM": 10, "LR_SCHEDULE": "triangle", "WARMUP": True,
               "WARMUP_STEPS": 8000, "BEGIN_EPOCH": 0, "END_EPOCH": 10, "GRAD_ACCUMULATE_STEPS": 1, "OPTIMIZER": "AdamW", "FP16": False,
               "RESUME": False, "AUTO_RESUME": True},
@@ -116,6 +117,25 @@ def resolve(config, world, args):
                 fp16_requested=bool(tr.FP16), seed=int(config.RNG_SEED),
                 compute=(("fp16" if tr.FP16 else "fp32") if args.compute == "cfg" else args.compute),
                 loss_scale=_loss_scale_of(tr.get("FP16_LOSS_SCALE", None)))
+
+
+def objective_of(config):
+    """The four objective switches of NETWORK (pretrain/function/config.py) as the engine's ModelConfig fields."""
+    net = config.NETWORK
+    return dict(with_mlm_loss=bool(net.WITH_MLM_LOSS), with_mvrc_loss=bool(net.WITH_MVRC_LOSS),
+                mlm_norm_in_batch_first=bool(net.WITH_MLM_LOSS) and bool(net.MLM_LOSS_NORM_IN_BATCH_FIRST),
+                mvrc_norm_in_batch_first=bool(net.WITH_MVRC_LOSS) and bool(net.MVRC_LOSS_NORM_IN_BATCH_FIRST))
+
+
+def describe_objective(obj, with_rel_loss=False):
+    """`mlm (norm in batch first) + mvrc`: the start-up line's account of the losses the run trains on."""
+    parts = []
+    if with_rel_loss:
+        parts.append("relationship")
+    for head in ("mlm", "mvrc"):
+        if obj["with_%s_loss" % head]:
+            parts.append(head + (" (norm in batch first)" if obj["%s_norm_in_batch_first" % head] else ""))
+    return " + ".join(parts)
 
 
 def _loss_scale_of(value):
@@ -244,6 +264,10 @@ def main(argv=None):
                          "validation kernels read 16-bit logits; validate with --compute fp32")
     if args.train_metrics:      # (reported only when asked for: without the flag the resolved dict is what it was)
         r["train_metrics"] = True
+    obj = r["objective"] = objective_of(config)
+    if r["multitask"] and not obj["with_mlm_loss"]:
+        raise NotImplementedError("the multitask wrapper without WITH_MLM_LOSS: the text-only samples feed the MLM loss alone (the "
+                                  "reference's forward fails there too, resnet_vlbert_for_pretraining_multitask.py:205,283)")
     if args.dry_run:
         if rank == 0:
             print(json.dumps({"resolved": r, "NETWORK.VLBERT": dict(config.NETWORK.VLBERT)}, indent=1, default=str))
@@ -276,7 +300,7 @@ def main(argv=None):
                             attention_probs_dropout_prob=g("attention_probs_dropout_prob", 0.1), multitask=r["multitask"],
                             with_pooler=bool(g("with_pooler", False)), with_rel_loss=bool(config.NETWORK.WITH_REL_LOSS), e2e=r["e2e"],
                             image_num_layers=int(config.NETWORK.IMAGE_NUM_LAYERS),
-                            image_frozen_stages=tuple(config.NETWORK.IMAGE_FROZEN_BACKBONE_STAGES))
+                            image_frozen_stages=tuple(config.NETWORK.IMAGE_FROZEN_BACKBONE_STAGES), **obj)
     B, T, R = r["per_gpu_batch"], args.text_len, args.regions
     B_aux = r["per_gpu_aux_batch"]
     eng = engine.PretrainEngine(mc, B, T, R, device="cuda:%d" % local_rank, train=True, lr=r["lr"], weight_decay=r["weight_decay"],
@@ -306,6 +330,7 @@ def main(argv=None):
         eng.sync_weights()
     eng.broadcast_parameters(src=0)       # rank 0's parameters / optimizer state everywhere (pretrain/function/train.py:331-334)
     if rank == 0:
+        print("objective: %s" % describe_objective(obj, bool(config.NETWORK.WITH_REL_LOSS)), flush=True)
         print("train_end2end: %s | %d GPU(s) x batch %d | lr %.3e wd %.1e clip %.1f | schedule %s warmup %d t_total %d%s" %
               (config.MODULE, world, B + B_aux, r["lr"], r["weight_decay"], r["clip_grad_norm"], r["lr_schedule"], r["warmup_steps"], r["t_total"],
                " | compute %s%s" % (r["compute"], (" (loss scale dynamic (%s))" % eng.scaler.spec.describe()) if eng.scaler is not None
@@ -369,6 +394,8 @@ def main(argv=None):
         if loader is not None:
             return load_real_batch()
         batch = list(syn.make_batch(B, T, R, seed=1000 * rank + seed_off))
+        if obj["mlm_norm_in_batch_first"] or obj["mvrc_norm_in_batch_first"]:
+            batch[4][seed_off % B] = -1      # per-sample means: every batch holds a sample without an MLM label (n_b = 0)
         kw = {}
         if r["multitask"]:
             aux_text, aux_lab = syn.make_aux_text(B_aux, T, seed=5000 * (rank + 1) + seed_off)
