@@ -148,3 +148,82 @@ def test_step_functions_name_no_precision_flag():
         src = inspect.getsource(importlib.import_module("vl-bert_amd." + mod))
         for flag in ("eng.fp32_ends", "e.fp32_ends", "eng.fp32_full", "e.fp32_full", "e.enc32", "e.pre32", "eng.enc32", "eng.pre32", "getattr(e,"):
             assert flag not in src, (mod, flag)
+
+
+# -- the objective switches: one Heads16 for every setting ------------------------------------------------------------------------------
+VARIANTS = {
+    "mlm_only": dict(with_mvrc_loss=False),
+    "mvrc_only": dict(with_mlm_loss=False),
+    "mlm_norm": dict(mlm_norm_in_batch_first=True),
+    "mvrc_norm": dict(mvrc_norm_in_batch_first=True),
+    "both_norm": dict(mlm_norm_in_batch_first=True, mvrc_norm_in_batch_first=True),
+    "mlm_only_rel": dict(with_mvrc_loss=False, with_pooler=True, with_rel_loss=True),
+}
+# library calls at 2 layers, B=2, T=160 (so that the compaction capacity of 256 rows is below B*T), R=4, as the separate variant part
+# launched them before it was folded into Heads16: (train_step, eval_step) compacted, then with VLB_MLM_COMPACT=0
+VARIANT_CALLS = {"mlm_only": (73, 29, 71, 28), "mvrc_only": (66, 27, 66, 27), "mlm_norm": (81, 34, 79, 33), "mvrc_norm": (80, 33, 78, 32),
+                 "both_norm": (81, 34, 79, 33), "mlm_only_rel": (81, 32, 79, 31)}
+MLM_ONLY = ("text_out", "mlm_u", "mlm_g", "mlm_h", "st_mlm", "mlm_logits", "mlm_logits_copy", "d_mlm_h", "d_mlm_g", "d_mlm_u", "sel_pos",
+            "sel_src", "labels_c", "mlm_overflow", "d_text_out_c", "mlm_w")
+MVRC_ONLY = ("obj_out", "mvrc_u", "mvrc_g", "mvrc_logits", "mvrc_logits_copy", "mvrc_tsum", "d_mvrc_u", "mvrc_w")
+PLAIN_LOSS = {"vlb_ce_rowweight_eval": "vlb_ce_eval", "vlb_soft_ce_rowweight_fwd_bwd": "vlb_soft_ce_fwd_bwd",
+              "vlb_soft_ce_rowweight_eval": "vlb_soft_ce_eval"}
+
+
+def eval_step(eng):
+    eng.eval_step()
+
+
+def head_order(calls, compact):
+    """Entry points of a step with the row-weighted losses named as the plain ones whose place they take."""
+    plain = dict(PLAIN_LOSS, vlb_ce_rowweight_fwd_bwd="vlb_ce_fwd_bwd_compact" if compact else "vlb_ce_fwd_bwd")
+    return [plain.get(n, n) for n in ST.names(calls) if n != "vlb_sample_norm_weights"]
+
+
+def is_subsequence(short, full):
+    it = iter(full)
+    return all(n in it for n in short)
+
+
+@pytest.mark.parametrize("compact", [True, False])
+@pytest.mark.parametrize("variant", sorted(VARIANTS))
+def test_objective_variants_run_the_one_heads_part_in_its_order(monkeypatch, variant, compact):
+    monkeypatch.setenv("VLB_MLM_COMPACT", "1" if compact else "0")
+    kw = VARIANTS[variant]
+    base_kw = {k: v for k, v in kw.items() if k in ("with_pooler", "with_rel_loss")}
+    for i, step in enumerate((ST.train_step, eval_step)):
+        eng, calls = ST.run(cfg_kw=kw, T=160, step=step)
+        back = eng.back
+        assert len(ST.names(calls)) == VARIANT_CALLS[variant][(0 if compact else 2) + i], (variant, compact, step.__name__)
+        assert type(back).__name__ == "Heads16" and type(back).__module__ == "vl-bert_amd.ends_16"
+        assert eng._mlm_compact_now == (compact and eng.cfg.with_mlm_loss)
+        # an absent head owns nothing; d(text_out) / d(obj_out) exist whatever the heads
+        for present, names, wts in ((back.mlm, MLM_ONLY, ("vlbert.mlm_head.predictions.transform.dense.weight", "vlbert.word_embeddings.weight")),
+                                    (back.mvrc, MVRC_ONLY, ("vlbert.mvrc_head.transform.dense.weight", "vlbert.mvrc_head.region_cls_pred.weight"))):
+            assert all((n in back.wT) == present for n in wts)
+            if not present:
+                assert not [n for n in names if hasattr(back, n)]
+        assert tuple(back.d_text_out.shape) == (eng.BT, H) and tuple(back.d_obj_out.shape) == (eng.BR, H)
+        assert hasattr(back, "mlm_w") == bool(kw.get("mlm_norm_in_batch_first")) and hasattr(back, "mvrc_w") == bool(kw.get("mvrc_norm_in_batch_first"))
+        # the order is the default part's: with both heads the very sequence of the default objective (each row-weighted loss where
+        # the plain one stands, after the weights of its samples), with one head that sequence less the absent head's launches
+        _, base = ST.run(cfg_kw=base_kw, T=160, step=step)
+        got, want = head_order(calls, eng._mlm_compact_now), ST.names(base)
+        if back.mlm and back.mvrc:
+            assert got == want
+        else:
+            # (the front of a model without MVRC adds its one-row table gradient in a launch of its own: PretrainFront16.front_bwd)
+            got = [n for n in got if n != "vlb_add_rows_f32"]
+            assert len(got) < len(want) and is_subsequence(got, want)
+
+
+def test_every_16_bit_engine_has_the_one_heads_part(traced):
+    for mode in ("default", "encoder_fp32", "core"):
+        assert type(traced[mode][0].back).__name__ == "Heads16"
+    with pytest.raises(ImportError):
+        importlib.import_module("vl-bert_amd.objectives_16")
+    eng, _ = ST.run(cfg_kw=dict(with_mlm_loss=False))
+    with pytest.raises(RuntimeError, match="no module-API outputs"):
+        eng.back.outputs()
+    with pytest.raises(ValueError):
+        ST.run(cfg_kw=dict(mlm_norm_in_batch_first=True), core=True)

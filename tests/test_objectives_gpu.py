@@ -1,5 +1,5 @@
 """The pre-training objective switches on the GPU (-m gpu): the per-sample weight kernel and the row-weighted losses of csrc/loss.hip
-against tests/objectives_ref.py, then the engine's objective variants (objectives_16.py) at the dimensions of
+against tests/objectives_ref.py, then the engine's objective variants (ends_16.Heads16) at the dimensions of
 tests/golden/objectives/objectives_small.npz against the same restatement and against what the real reference recorded.
 
 Bars: the kernel tests take those of tests/test_ops_gpu.py::test_ce_fwd_bwd / test_soft_ce_fwd_bwd (loss 1e-4 + 1e-3 |ref|, d(logits)

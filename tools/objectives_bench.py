@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""What the objective switches cost (NETWORK.WITH_MLM_LOSS / WITH_MVRC_LOSS / *_LOSS_NORM_IN_BATCH_FIRST; objectives_16.py).
+"""What the objective switches cost (NETWORK.WITH_MLM_LOSS / WITH_MVRC_LOSS / *_LOSS_NORM_IN_BATCH_FIRST; ends_16.Heads16).
 
 (a) The row-weighted loss launches against the unweighted ones on the same tensors, at the headline sizes: MLM on 1024 compacted rows x
     30522 (vlb_ce_fwd_bwd_compact against vlb_ce_rowweight_fwd_bwd through sel_pos, and the per-sample weight kernel alone), MVRC on

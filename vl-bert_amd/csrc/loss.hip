@@ -8,6 +8,8 @@
 // A copy of the logits is only kept when the caller asks for one (API parity / metrics).
 // n_valid is produced on the device by the count kernels -> no host synchronisation
 // (the reference does `.item()` at misc.py:140).
+#include <type_traits>
+
 #include "arg_reduce.h"
 
 __device__ __forceinline__ void online_merge(float& m, float& s, float m2, float s2) {
@@ -17,33 +19,14 @@ __device__ __forceinline__ void online_merge(float& m, float& s, float m2, float
   m = mn;
 }
 
-// block-wide (256 threads) reduction of an online-softmax (max,sum) pair; result broadcast
-__device__ __forceinline__ void block_online_reduce(float& m, float& s, float* sh) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const float m2 = __shfl_xor(m, o, 64), s2 = __shfl_xor(s, o, 64);
-    online_merge(m, s, m2, s2);
-  }
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  __syncthreads();
-  if (lane == 0) {
-    sh[wave * 2] = m;
-    sh[wave * 2 + 1] = s;
-  }
-  __syncthreads();
-  m = sh[0];
-  s = sh[1];
-#pragma unroll
-  for (int w = 1; w < 4; ++w) online_merge(m, s, sh[w * 2], sh[w * 2 + 1]);
-}
-
-// block_online_reduce for the ACC kernels, with the roundings written out.  online_merge's s * e + s2 * e2 holds two products and the
-// build contracts one of them into the add (-ffp-contract=fast); WHICH one is the compiler's choice per inlined copy, and it chose
-// differently inside an ACC kernel than inside the plain one (the ACC forms' last butterfly step but one), which moved the last bit of
-// a row's sum-exp and with it single 16-bit gradients.  The plain kernels -- hard and soft labels, static and dynamic scale, both
-// builds -- round the thread's own product s * e in every step except the last butterfly step (o == 1), where they round the
-// partner's: this function states exactly that with __fmul_rn / fmaf, so that an ACC kernel computes the bits of its plain twin
-// whatever surrounds the reduction.  tests/test_train_metrics_gpu.py compares the two bit for bit on logits off the 1/8 grid.
+// Block-wide (256 threads) reduction of an online-softmax (max, sum) pair, result broadcast, with the roundings written out.
+// online_merge's s * e + s2 * e2 holds two products and the build contracts one of them into the add (-ffp-contract=fast); WHICH one
+// is the compiler's choice per inlined copy.  When this reduction was a loop over online_merge, the compiler chose differently
+// inside an ACC kernel than inside the plain one (the ACC forms' last butterfly step but one), which moved the last bit of a row's
+// sum-exp and with it single 16-bit gradients.  What the plain kernels -- hard and soft labels, static and dynamic scale, both
+// builds -- were compiled to is the contract: the thread's own product s * e rounded in every step except the last butterfly step
+// (o == 1), where the partner's is.  This function states exactly that with __fmul_rn / fmaf, so that every kernel of this file
+// computes those bits whatever surrounds the reduction (tests/test_loss_bits_gpu.py holds them to a recording of that build).
 template <bool OWN>
 __device__ __forceinline__ void online_merge_as_plain(float& m, float& s, float m2, float s2) {
   const float mn = fmaxf(m, m2);
@@ -111,55 +94,102 @@ __global__ void count_labels_acc_kernel(const int64_t* __restrict__ labels, int 
   }
 }
 
-// One block per row.  logits: bf16 [rows, ld] (columns >= V are padding and are zeroed).
-// out: loss_sum += row_loss / n_valid ;  logits <- dlogits * (gscale / n_valid).
-// Two-group form (compacted MLM rows of the multitask wrapper): rows [0, *n_valid) belong to group 0 (mean over n_valid ->
-// loss_out), the rows behind them to group 1 (mean over *n_valid2 -> loss_out2); n_valid2 == nullptr: one group.
-// DS (dynamic loss scale): the gradient scale is gscale * *dscale, a device value formed once per block and used exactly where gscale
-// is -- the same bits as a launch given the product from the host, and no second pass over the logits.  The static instantiation
-// never reads the trailing argument.
-// ACC (training-time metrics): the per-thread online (m, s) pair also carries the column of m, merged with the tie rule of arg_reduce.h,
-// and a row whose argmax is its label adds 1 to acc[0] (acc2[0] for a row of group 1) -- an integer atomic, so the counters do not
-// depend on arrival order.  The columns meet in block_argmax (arg_reduce.h); (m, s) go through block_online_reduce_as_plain, the
-// reduction of the plain form with its roundings written out, so loss and gradient are the plain form's bits.
-// The counted rows are known before the launch: in the two-group form thread 0 of block 0 adds *n_valid / *n_valid2 to acc[1] /
-// acc2[1], before any early return (its own row may be unlabelled); in the one-group form count_labels_acc_kernel has added them.
-template <bool DS = false, bool ACC = false>
-__global__ __launch_bounds__(256) void ce_fwd_bwd_kernel(bf16_t* __restrict__ logits, long ld, int V, const int64_t* __restrict__ labels,
-                                                         const float* __restrict__ n_valid, float gscale, float* __restrict__ loss_out,
-                                                         bf16_t* __restrict__ logits_copy, long ldcopy,
-                                                         const float* __restrict__ n_valid2 = nullptr, float* __restrict__ loss_out2 = nullptr,
-                                                         const float* __restrict__ dscale = nullptr, vlb_u64* __restrict__ acc = nullptr,
-                                                         vlb_u64* __restrict__ acc2 = nullptr) {
-  if (DS) gscale = __fmul_rn(gscale, *dscale);
-  __shared__ float sh[16];
-  const int row = blockIdx.x;
-  if (ACC && n_valid2 && row == 0 && threadIdx.x == 0) {
-    const vlb_u64 n0 = (vlb_u64)*n_valid, n1 = (vlb_u64)*n_valid2;
-    if (n0) atomicAdd(acc + 1, n0);
-    if (n1) atomicAdd(acc2 + 1, n1);
-  }
-  if (n_valid2 && (float)row >= *n_valid) {
-    n_valid = n_valid2;
-    loss_out = loss_out2;
-    if (ACC) acc = acc2;
-  }
-  bf16_t* x = logits + (long)row * ld;
-  const long label = labels[row];
-  const int ldv = (int)ld;
-  if (logits_copy) {
-    bf16_t* cp = logits_copy + (long)row * ldcopy;
-    for (int c = threadIdx.x * 8; c < V; c += 2048) {
-      if (c + 8 <= V) *(uint4*)(cp + c) = *(const uint4*)(x + c);
-      else for (int k = c; k < V; ++k) cp[k] = x[k];
+// ------------------------------------------------------------------------------------------------------------------
+// The two row kernels (hard labels, soft labels), one block per row, each in a plain and a row-weighted form.  The forms differ in
+// where a row's scale, loss slot and counters come from -- the NORM argument, one of the two structs below -- and in nothing else.
+//   select(row, k): false = the row belongs to no sample (skipped like an unlabelled row); otherwise picks the row's loss slot and
+//                   counters and loads k, its divisor or its weight
+//   mean(v, k):     the row's share of v.  The arithmetic is the form's own and stays so: v / nv here, v * wr there
+//   count_up_front(row) / PER_ROW: who adds the counted rows to acc[1] (ACC forms)
+// ------------------------------------------------------------------------------------------------------------------
+// Batch mean: 1 / max(*n_valid, 1).  Two-group form (compacted MLM rows of the multitask wrapper): rows [0, *n_valid) belong to group
+// 0 (mean over n_valid -> loss_out), the rows behind them to group 1 (mean over *n_valid2 -> loss_out2); n_valid2 == nullptr: one
+// group.  The counted rows are known before the launch: with up_front thread 0 of block 0 adds *n_valid / *n_valid2 to acc[1] /
+// acc2[1], before any early return (its own row may be unlabelled); without, a count kernel has added them (count_labels_acc_kernel).
+struct MeanNorm {
+  static constexpr bool PER_ROW = false;
+  const float* n_valid;
+  float* loss_out;
+  vlb_u64* acc;
+  const float* n_valid2;
+  float* loss_out2;
+  vlb_u64* acc2;
+  bool up_front;
+  __device__ __forceinline__ void count_up_front(int row) const {
+    if (up_front && row == 0 && threadIdx.x == 0) {
+      const vlb_u64 n0 = (vlb_u64)*n_valid;
+      if (n0) atomicAdd(acc + 1, n0);
+      if (n_valid2) {
+        const vlb_u64 n1 = (vlb_u64)*n_valid2;
+        if (n1) atomicAdd(acc2 + 1, n1);
+      }
     }
   }
-  if (label < 0 || label >= V) {  // ignore_index: no loss, zero gradient row
-    for (int c = threadIdx.x * 8; c < ldv; c += 2048) *(uint4*)(x + c) = make_uint4(0, 0, 0, 0);
-    return;
+  __device__ __forceinline__ bool select(int row, float& nv) {
+    if (n_valid2 && (float)row >= *n_valid) {
+      n_valid = n_valid2;
+      loss_out = loss_out2;
+      acc = acc2;
+    }
+    nv = fmaxf(*n_valid, 1.f);
+    return true;
   }
-  float m = -INFINITY, s = 0.f;
-  int idx = INT_MAX;      // (ACC) column of m; a thread's columns ascend, so `>` alone keeps its lowest column among equals
+  static __device__ __forceinline__ float mean(float v, float nv) { return v / nv; }
+};
+
+// Per-sample weights (vlb_sample_norm_weights, below): w[s(r)] for 1 / n_valid, s(r) = pos(r) / T with pos the row itself or, on the
+// compacted MLM rows, sel_pos[r] (-1 behind the labelled rows).  Samples s < B_split add to loss_out / acc, the others to loss_out2 /
+// acc2.  A counted row adds its own 1 to acc[1] (integer atomics: no dependence on arrival order); the weights do not enter.
+struct RowWeightNorm {
+  static constexpr bool PER_ROW = true;
+  const int32_t* sel_pos;
+  int B, T, B_split;
+  const float* w;
+  float* loss_out;
+  vlb_u64* acc;
+  float* loss_out2;
+  vlb_u64* acc2;
+  __device__ __forceinline__ void count_up_front(int) const {}
+  __device__ __forceinline__ bool select(int row, float& wr) {
+    const int pos = sel_pos ? sel_pos[row] : row;
+    const int smp = pos >= 0 ? pos / T : B;
+    if (smp >= B) return false;
+    if (smp >= B_split) {
+      loss_out = loss_out2;
+      acc = acc2;
+    }
+    wr = w[smp];
+    return true;
+  }
+  static __device__ __forceinline__ float mean(float v, float wr) { return v * wr; }
+};
+
+// ---- the row code of the hard-label kernel: 8 columns per thread and step, 16-byte accesses ----
+__device__ __forceinline__ void hard_copy_row(const bf16_t* __restrict__ x, bf16_t* __restrict__ cp, int V) {
+  for (int c = threadIdx.x * 8; c < V; c += 2048) {
+    if (c + 8 <= V) *(uint4*)(cp + c) = *(const uint4*)(x + c);
+    else for (int k = c; k < V; ++k) cp[k] = x[k];
+  }
+}
+
+__device__ __forceinline__ void hard_zero_row(bf16_t* __restrict__ x, int ldv) {
+  for (int c = threadIdx.x * 8; c < ldv; c += 2048) *(uint4*)(x + c) = make_uint4(0, 0, 0, 0);
+}
+
+// online_merge(m, s, v, 1.f) for the scan below, its early return (both empty: nothing changes) as a select: inside a function the
+// compiler kept that return as a second branch per element, which cost the wide rows 2 %
+__device__ __forceinline__ void online_add(float& m, float& s, float v) {
+  const float mn = fmaxf(m, v);
+  const float sn = s * __expf(m - mn) + __expf(v - mn);
+  s = (mn == -INFINITY) ? s : sn;
+  m = mn;
+}
+
+// the thread's online (m, s) over its columns of [0, V) and (ACC) idx, the column of m: a thread's columns ascend, so `>` alone keeps
+// its lowest column among equals
+template <bool ACC>
+__device__ __forceinline__ void hard_scan_row(const bf16_t* __restrict__ x, int V, float& m, float& s, int& idx) {
+  m = -INFINITY, s = 0.f, idx = INT_MAX;
   for (int c = threadIdx.x * 8; c < V; c += 2048) {
     const uint4 w = *(const uint4*)(x + c);
     const uint32_t ww[4] = {w.x, w.y, w.z, w.w};
@@ -168,27 +198,18 @@ __global__ __launch_bounds__(256) void ce_fwd_bwd_kernel(bf16_t* __restrict__ lo
       const float a = bflo(ww[k]), b = bfhi(ww[k]);
       if (c + 2 * k < V) {
         if (ACC && a > m) idx = c + 2 * k;
-        online_merge(m, s, a, 1.f);
+        online_add(m, s, a);
       }
       if (c + 2 * k + 1 < V) {
         if (ACC && b > m) idx = c + 2 * k + 1;
-        online_merge(m, s, b, 1.f);
+        online_add(m, s, b);
       }
     }
   }
-  if (ACC) {      // the thread's (maximum, its column) -> the row's, before (m, s) become the row's
-    float mv = m;
-    block_argmax(mv, idx, sh + 8);
-    block_online_reduce_as_plain(m, s, sh);
-  } else {
-    block_online_reduce(m, s, sh);
-  }
-  const float lse = m + __logf(s);
-  const float nv = fmaxf(*n_valid, 1.f);
-  if (threadIdx.x == 0) atomicAdd(loss_out, (lse - bf2f(x[label])) / nv);
-  if (ACC && threadIdx.x == 0 && idx == (int)label) atomicAdd(acc, (vlb_u64)1);
-  const float sc = gscale / nv;
-  __syncthreads();  // x[label] read above before anyone overwrites it
+}
+
+// x <- (softmax(x) - onehot(label)) * sc over [0, V), zero over the padding [V, ldv)
+__device__ __forceinline__ void hard_grad_row(bf16_t* __restrict__ x, int ldv, int V, long label, float lse, float sc) {
   for (int c = threadIdx.x * 8; c < ldv; c += 2048) {
     const uint4 w = *(const uint4*)(x + c);
     const uint32_t ww[4] = {w.x, w.y, w.z, w.w};
@@ -203,6 +224,68 @@ __global__ __launch_bounds__(256) void ce_fwd_bwd_kernel(bf16_t* __restrict__ lo
       o[k] = pack2bf(g0 * sc, g1 * sc);
     }
     *(uint4*)(x + c) = make_uint4(o[0], o[1], o[2], o[3]);
+  }
+}
+
+// logits: bf16 [rows, ld] (columns >= V are padding and are zeroed).
+// out: loss slot += mean(row_loss);  logits <- dlogits * mean(gscale).  A row whose label is outside [0, V) (ignore_index) or that
+// NORM does not select adds no loss and gets a zero gradient row.
+// BWD = false is the forward-only twin of eval_step(): the logits are only read.
+// DS (dynamic loss scale): the gradient scale is gscale * *dscale, a device value formed once per block and used exactly where gscale
+// is -- the same bits as a launch given the product from the host, and no second pass over the logits.  The static instantiation
+// never reads the trailing argument.
+// ACC (training-time metrics): the per-thread online (m, s) pair also carries the column of m, merged with the tie rule of arg_reduce.h,
+// and a row whose argmax is its label adds 1 to acc[0] of its group -- an integer atomic, so the counters do not depend on arrival
+// order.  The columns meet in block_argmax (arg_reduce.h) before (m, s) become the row's.
+template <class NORM, bool BWD, bool DS, bool ACC>
+__global__ __launch_bounds__(256) void ce_row_kernel(bf16_t* __restrict__ logits, long ld, int V, const int64_t* __restrict__ labels, NORM norm,
+                                                     float gscale, bf16_t* __restrict__ logits_copy, long ldcopy,
+                                                     const float* __restrict__ dscale) {
+  if (DS) gscale = __fmul_rn(gscale, *dscale);
+  __shared__ float sh[16];
+  const int row = blockIdx.x;
+  if (ACC) norm.count_up_front(row);
+  bf16_t* x = logits + (long)row * ld;
+  const long label = labels[row];
+  const int ldv = (int)ld;
+  if (BWD && logits_copy) hard_copy_row(x, logits_copy + (long)row * ldcopy, V);
+  float k;
+  if (label < 0 || label >= V || !norm.select(row, k)) {
+    if (BWD) hard_zero_row(x, ldv);
+    return;
+  }
+  float m, s;
+  int idx;
+  hard_scan_row<ACC>(x, V, m, s, idx);
+  if (ACC) {
+    float mv = m;
+    block_argmax(mv, idx, sh + 8);
+  }
+  block_online_reduce_as_plain(m, s, sh);
+  const float lse = m + __logf(s);
+  if (threadIdx.x == 0) {
+    atomicAdd(norm.loss_out, NORM::mean(lse - bf2f(x[label]), k));
+    if (ACC) {
+      if (idx == (int)label) atomicAdd(norm.acc, (vlb_u64)1);
+      if (NORM::PER_ROW) atomicAdd(norm.acc + 1, (vlb_u64)1);
+    }
+  }
+  if (!BWD) return;
+  const float sc = NORM::mean(gscale, k);
+  __syncthreads();  // x[label] read above before anyone overwrites it
+  hard_grad_row(x, ldv, V, label, lse, sc);
+}
+
+// The runtime (dscale != nullptr, acc != nullptr) of an entry point as the <DS, ACC> of its launch:
+//   with_ds_acc(dscale, acc, [&](auto DS, auto ACC) { hipLaunchKernelGGL((kernel<..., DS(), ACC()>), ...); });
+template <class F>
+static void with_ds_acc(const void* dscale, const void* acc, F&& launch) {
+  if (dscale) {
+    if (acc) launch(std::true_type(), std::true_type());
+    else launch(std::true_type(), std::false_type());
+  } else {
+    if (acc) launch(std::false_type(), std::true_type());
+    else launch(std::false_type(), std::false_type());
   }
 }
 
@@ -310,22 +393,11 @@ extern "C" int vlb_ce_fwd_bwd_compact(void* logits, long ld, int rows, int V, co
   if (rows <= 0) return VLB_OK;
   VLB_CHECK_ARG(logits && labels_c && count0 && count1 && loss_out0 && loss_out1, "vlb_ce_fwd_bwd_compact: null argument");
   VLB_CHECK_ARG(ld >= V && (ld % 8) == 0, "vlb_ce_fwd_bwd_compact: ld=%ld must be >= V=%d and a multiple of 8", ld, V);
-  if (acc0) {      // the ACC form: its own instantiations, the launches below are the ones they were
-    if (dscale)
-      hipLaunchKernelGGL((ce_fwd_bwd_kernel<true, true>), dim3(rows), dim3(256), 0, stream, (bf16_t*)logits, ld, V, labels_c, count0, gscale,
-                         loss_out0, (bf16_t*)nullptr, 0L, count1, loss_out1, dscale, (vlb_u64*)acc0, (vlb_u64*)acc1);
-    else
-      hipLaunchKernelGGL((ce_fwd_bwd_kernel<false, true>), dim3(rows), dim3(256), 0, stream, (bf16_t*)logits, ld, V, labels_c, count0, gscale,
-                         loss_out0, (bf16_t*)nullptr, 0L, count1, loss_out1, (const float*)nullptr, (vlb_u64*)acc0, (vlb_u64*)acc1);
-    VLB_CHECK_LAUNCH("vlb_ce_fwd_bwd_compact");
-    return VLB_OK;
-  }
-  if (dscale)
-    hipLaunchKernelGGL(ce_fwd_bwd_kernel<true>, dim3(rows), dim3(256), 0, stream, (bf16_t*)logits, ld, V, labels_c, count0, gscale, loss_out0,
-                       (bf16_t*)nullptr, 0L, count1, loss_out1, dscale);
-  else
-    hipLaunchKernelGGL(ce_fwd_bwd_kernel<false>, dim3(rows), dim3(256), 0, stream, (bf16_t*)logits, ld, V, labels_c, count0, gscale, loss_out0,
-                       (bf16_t*)nullptr, 0L, count1, loss_out1, (const float*)nullptr);
+  const MeanNorm norm = {count0, loss_out0, (vlb_u64*)acc0, count1, loss_out1, (vlb_u64*)acc1, true};
+  with_ds_acc(dscale, acc0, [&](auto DS, auto ACC) {
+    hipLaunchKernelGGL((ce_row_kernel<MeanNorm, true, DS(), ACC()>), dim3(rows), dim3(256), 0, stream, (bf16_t*)logits, ld, V, labels_c, norm, gscale,
+                       (bf16_t*)nullptr, 0L, dscale);
+  });
   VLB_CHECK_LAUNCH("vlb_ce_fwd_bwd_compact");
   return VLB_OK;
 }
@@ -354,37 +426,13 @@ __global__ __launch_bounds__(256) void soft_valid_kernel(const float* __restrict
   }
 }
 
-// One block per row.  logits bf16 [rows, ld] -> in place d(logits); target fp32 [rows, ldt].
-//   loss_row = lse * sum(t) - sum(t * x);  dlogit_c = (softmax_c * sum(t) - t_c) / n_valid
-// ACC: the pass that reads x and t also takes argmax(x) and argmax(t) over [0, C) (lowest column among equals); a valid row where they
-// agree adds 1 to acc[0]; thread 0 of block 0 adds the valid rows (*n_valid, from soft_valid_kernel) to acc[1] before its early return.
-template <bool DS = false, bool ACC = false>
-__global__ __launch_bounds__(256) void soft_ce_fwd_bwd_kernel(bf16_t* __restrict__ logits, long ld, int C, const float* __restrict__ target,
-                                                              long ldt, const float* __restrict__ tsum, const float* __restrict__ n_valid,
-                                                              float gscale, float* __restrict__ loss_out, bf16_t* __restrict__ logits_copy,
-                                                              long ldcopy, const float* __restrict__ dscale = nullptr,
-                                                              vlb_u64* __restrict__ acc = nullptr) {
-  __shared__ float sh[ACC ? 28 : 16];
-  if (DS) gscale = __fmul_rn(gscale, *dscale);
-  const int row = blockIdx.x;
-  if (ACC && row == 0 && threadIdx.x == 0) {
-    const vlb_u64 n = (vlb_u64)*n_valid;
-    if (n) atomicAdd(acc + 1, n);
-  }
-  bf16_t* x = logits + (long)row * ld;
-  const float* t = target + (long)row * ldt;
-  const int ldv = (int)ld;
-  if (logits_copy) {
-    bf16_t* cp = logits_copy + (long)row * ldcopy;
-    for (int c = threadIdx.x; c < C; c += 256) cp[c] = x[c];
-  }
-  const float ts = tsum[row];
-  if (!(fabsf(ts - 1.f) < 0.1f)) {
-    for (int c = threadIdx.x; c < ldv; c += 256) x[c] = 0;
-    return;
-  }
-  float m = -INFINITY, s = 0.f, dot = 0.f, tm = -INFINITY;
-  int xi = INT_MAX, ti = INT_MAX;      // (ACC) ascending columns per thread: `>` keeps the lowest among equals
+// ---- the row code of the soft-label kernel: one column per thread and step ----
+// the thread's online (m, s) and its share of sum(t * x) over [0, C); (ACC) xi / ti, the columns of the largest x and the largest t (tm):
+// ascending columns per thread, so `>` keeps the lowest among equals
+template <bool ACC>
+__device__ __forceinline__ void soft_scan_row(const bf16_t* __restrict__ x, const float* __restrict__ t, int C, float& m, float& s, float& dot,
+                                              int& xi, float& tm, int& ti) {
+  m = -INFINITY, s = 0.f, dot = 0.f, tm = -INFINITY, xi = INT_MAX, ti = INT_MAX;
   for (int c = threadIdx.x; c < C; c += 256) {
     const float v = bf2f(x[c]), tv = t[c];
     if (ACC) {
@@ -394,25 +442,61 @@ __global__ __launch_bounds__(256) void soft_ce_fwd_bwd_kernel(bf16_t* __restrict
     online_merge(m, s, v, 1.f);
     dot += tv * v;
   }
-  if (ACC) {      // the threads' (maximum, its column) pairs -> the row's two argmaxes; (m, s) and dot reduce to the plain form's bits
-    float mv = m;
-    block_argmax(mv, xi, sh + 12);
-    block_argmax(tm, ti, sh + 20);
-    if (threadIdx.x == 0 && xi == ti) atomicAdd(acc, (vlb_u64)1);
-    block_online_reduce_as_plain(m, s, sh);
-  } else {
-    block_online_reduce(m, s, sh);
-  }
-  dot = block_sum(dot, sh + 8);
-  const float lse = m + __logf(s);
-  const float nv = fmaxf(*n_valid, 1.f);
-  if (threadIdx.x == 0) atomicAdd(loss_out, (lse * ts - dot) / nv);
-  const float sc = gscale / nv;
+}
+
+// x <- (softmax(x) * sum(t) - t) * sc over [0, C), zero over the padding [C, ldv)
+__device__ __forceinline__ void soft_grad_row(bf16_t* __restrict__ x, const float* __restrict__ t, int ldv, int C, float lse, float ts, float sc) {
   for (int c = threadIdx.x; c < ldv; c += 256) {
     float g = 0.f;
     if (c < C) g = (__expf(bf2f(x[c]) - lse) * ts - t[c]) * sc;
     x[c] = f2bf(g);
   }
+}
+
+// logits bf16 [rows, ld] -> in place d(logits); target fp32 [rows, ldt]; a row is valid iff |tsum[row] - 1| < 0.1 (soft_valid_kernel).
+//   loss_row = lse * sum(t) - sum(t * x);  dlogit_c = mean((softmax_c * sum(t) - t_c) * gscale)
+// NORM, BWD, DS: as in ce_row_kernel.  ACC: the pass that reads x and t also takes argmax(x) and argmax(t) over [0, C) (lowest column
+// among equals); a valid row where they agree adds 1 to acc[0].
+template <class NORM, bool BWD, bool DS, bool ACC>
+__global__ __launch_bounds__(256) void soft_ce_row_kernel(bf16_t* __restrict__ logits, long ld, int C, const float* __restrict__ target, long ldt,
+                                                          const float* __restrict__ tsum, NORM norm, float gscale,
+                                                          bf16_t* __restrict__ logits_copy, long ldcopy, const float* __restrict__ dscale) {
+  __shared__ float sh[ACC ? 28 : 16];
+  if (DS) gscale = __fmul_rn(gscale, *dscale);
+  const int row = blockIdx.x;
+  if (ACC) norm.count_up_front(row);
+  bf16_t* x = logits + (long)row * ld;
+  const float* t = target + (long)row * ldt;
+  const int ldv = (int)ld;
+  if (BWD && logits_copy) {
+    bf16_t* cp = logits_copy + (long)row * ldcopy;
+    for (int c = threadIdx.x; c < C; c += 256) cp[c] = x[c];
+  }
+  const float ts = tsum[row];
+  float k;
+  if (!(fabsf(ts - 1.f) < 0.1f) || !norm.select(row, k)) {
+    if (BWD)
+      for (int c = threadIdx.x; c < ldv; c += 256) x[c] = 0;
+    return;
+  }
+  float m, s, dot, tm;
+  int xi, ti;
+  soft_scan_row<ACC>(x, t, C, m, s, dot, xi, tm, ti);
+  if (ACC) {      // the threads' (maximum, its column) pairs -> the row's two argmaxes
+    float mv = m;
+    block_argmax(mv, xi, sh + 12);
+    block_argmax(tm, ti, sh + 20);
+    if (threadIdx.x == 0) {
+      if (xi == ti) atomicAdd(norm.acc, (vlb_u64)1);
+      if (NORM::PER_ROW) atomicAdd(norm.acc + 1, (vlb_u64)1);
+    }
+  }
+  block_online_reduce_as_plain(m, s, sh);
+  dot = block_sum(dot, sh + 8);
+  const float lse = m + __logf(s);
+  if (threadIdx.x == 0) atomicAdd(norm.loss_out, NORM::mean(lse * ts - dot, k));
+  if (!BWD) return;
+  soft_grad_row(x, t, ldv, C, lse, ts, NORM::mean(gscale, k));
 }
 
 // dscale, acc: nullable, as in vlb_ce_fwd_bwd_compact (one group, one int64[2])
@@ -422,27 +506,14 @@ extern "C" int vlb_ce_fwd_bwd(void* logits, long ld, int rows, int V, const int6
   VLB_CHECK_ARG(logits && labels && counts && loss_out, "vlb_ce_fwd_bwd: null argument");
   VLB_CHECK_ARG(ld >= V && (ld % 8) == 0, "vlb_ce_fwd_bwd: ld=%ld must be >= V=%d and a multiple of 8", ld, V);
   (void)hipMemsetAsync(counts, 0, sizeof(float), stream);
-  if (acc) {      // the ACC form: its own count kernel and instantiations, the launches below are the ones they were
-    hipLaunchKernelGGL(count_labels_acc_kernel, dim3(vlb_cdiv(rows, 256) > 64 ? 64 : vlb_cdiv(rows, 256)), dim3(256), 0, stream, labels, rows, V,
-                       counts, (vlb_u64*)acc);
-    if (dscale)
-      hipLaunchKernelGGL((ce_fwd_bwd_kernel<true, true>), dim3(rows), dim3(256), 0, stream, (bf16_t*)logits, ld, V, labels, counts, gscale, loss_out,
-                         (bf16_t*)logits_copy, ldcopy, (const float*)nullptr, (float*)nullptr, dscale, (vlb_u64*)acc, (vlb_u64*)nullptr);
-    else
-      hipLaunchKernelGGL((ce_fwd_bwd_kernel<false, true>), dim3(rows), dim3(256), 0, stream, (bf16_t*)logits, ld, V, labels, counts, gscale,
-                         loss_out, (bf16_t*)logits_copy, ldcopy, (const float*)nullptr, (float*)nullptr, (const float*)nullptr, (vlb_u64*)acc,
-                         (vlb_u64*)nullptr);
-    VLB_CHECK_LAUNCH("vlb_ce_fwd_bwd");
-    return VLB_OK;
-  }
-  hipLaunchKernelGGL(count_labels_kernel, dim3(vlb_cdiv(rows, 256) > 64 ? 64 : vlb_cdiv(rows, 256)), dim3(256), 0, stream, labels, rows,
-                     counts);
-  if (dscale)
-    hipLaunchKernelGGL(ce_fwd_bwd_kernel<true>, dim3(rows), dim3(256), 0, stream, (bf16_t*)logits, ld, V, labels, counts, gscale, loss_out,
-                       (bf16_t*)logits_copy, ldcopy, (const float*)nullptr, (float*)nullptr, dscale);
-  else
-    hipLaunchKernelGGL(ce_fwd_bwd_kernel<false>, dim3(rows), dim3(256), 0, stream, (bf16_t*)logits, ld, V, labels, counts, gscale, loss_out,
-                       (bf16_t*)logits_copy, ldcopy, (const float*)nullptr, (float*)nullptr, (const float*)nullptr);
+  const int cblocks = vlb_cdiv(rows, 256) > 64 ? 64 : vlb_cdiv(rows, 256);
+  if (acc) hipLaunchKernelGGL(count_labels_acc_kernel, dim3(cblocks), dim3(256), 0, stream, labels, rows, V, counts, (vlb_u64*)acc);
+  else hipLaunchKernelGGL(count_labels_kernel, dim3(cblocks), dim3(256), 0, stream, labels, rows, counts);
+  const MeanNorm norm = {counts, loss_out, (vlb_u64*)acc, nullptr, nullptr, nullptr, false};
+  with_ds_acc(dscale, acc, [&](auto DS, auto ACC) {
+    hipLaunchKernelGGL((ce_row_kernel<MeanNorm, true, DS(), ACC()>), dim3(rows), dim3(256), 0, stream, (bf16_t*)logits, ld, V, labels, norm, gscale,
+                       (bf16_t*)logits_copy, ldcopy, dscale);
+  });
   VLB_CHECK_LAUNCH("vlb_ce_fwd_bwd");
   return VLB_OK;
 }
@@ -455,22 +526,11 @@ extern "C" int vlb_soft_ce_fwd_bwd(void* logits, long ld, int rows, int C, const
   VLB_CHECK_ARG(ld >= C && ldt >= C, "vlb_soft_ce_fwd_bwd: bad leading dimensions");
   (void)hipMemsetAsync(counts, 0, sizeof(float), stream);
   hipLaunchKernelGGL(soft_valid_kernel, dim3(vlb_cdiv(rows, 4)), dim3(256), 0, stream, target, ldt, C, rows, tsum, counts);
-  if (acc) {
-    if (dscale)
-      hipLaunchKernelGGL((soft_ce_fwd_bwd_kernel<true, true>), dim3(rows), dim3(256), 0, stream, (bf16_t*)logits, ld, C, target, ldt, tsum, counts,
-                         gscale, loss_out, (bf16_t*)logits_copy, ldcopy, dscale, (vlb_u64*)acc);
-    else
-      hipLaunchKernelGGL((soft_ce_fwd_bwd_kernel<false, true>), dim3(rows), dim3(256), 0, stream, (bf16_t*)logits, ld, C, target, ldt, tsum, counts,
-                         gscale, loss_out, (bf16_t*)logits_copy, ldcopy, (const float*)nullptr, (vlb_u64*)acc);
-    VLB_CHECK_LAUNCH("vlb_soft_ce_fwd_bwd");
-    return VLB_OK;
-  }
-  if (dscale)
-    hipLaunchKernelGGL(soft_ce_fwd_bwd_kernel<true>, dim3(rows), dim3(256), 0, stream, (bf16_t*)logits, ld, C, target, ldt, tsum, counts,
-                       gscale, loss_out, (bf16_t*)logits_copy, ldcopy, dscale);
-  else
-    hipLaunchKernelGGL(soft_ce_fwd_bwd_kernel<false>, dim3(rows), dim3(256), 0, stream, (bf16_t*)logits, ld, C, target, ldt, tsum, counts,
-                       gscale, loss_out, (bf16_t*)logits_copy, ldcopy, (const float*)nullptr);
+  const MeanNorm norm = {counts, loss_out, (vlb_u64*)acc, nullptr, nullptr, nullptr, true};
+  with_ds_acc(dscale, acc, [&](auto DS, auto ACC) {
+    hipLaunchKernelGGL((soft_ce_row_kernel<MeanNorm, true, DS(), ACC()>), dim3(rows), dim3(256), 0, stream, (bf16_t*)logits, ld, C, target, ldt,
+                       (const float*)tsum, norm, gscale, (bf16_t*)logits_copy, ldcopy, dscale);
+  });
   VLB_CHECK_LAUNCH("vlb_soft_ce_fwd_bwd");
   return VLB_OK;
 }
@@ -556,9 +616,8 @@ extern "C" int vlb_dropout_bf16(const void* x, void* y, long n, float drop_p, co
 //   loss = sum_b ( sum_t l_bt / (n_b + 1e-4) ) / ( #{b : n_b > 0} + 1e-4 )
 // with n_b the labelled tokens (valid regions) of sample b.  Every row of sample b therefore carries the one weight
 //   w[b] = 1 / ((n_b + 1e-4) (n_has + 1e-4))
-// and the fused loss kernels below are the ones above with `1 / n_valid` replaced by `w[s(r)]`, s(r) the sample of row r: one more
-// scalar load and one fp32 multiply per row.  The kernels above, their instantiations and their entry points are untouched; these
-// are launched only when a norm switch is on.
+// and the entry points below launch the row kernels above with RowWeightNorm: `1 / n_valid` replaced by `w[s(r)]`, s(r) the sample
+// of row r -- one more scalar load and one fp32 multiply per row.
 //
 // sample_norm_weights_kernel: ONE 1024-thread block (a batch has a few hundred samples of at most 512 positions).  Wave v counts the
 // rows of samples v, v + 16, ... -- integers, so the order of the additions does not matter -- and leaves n_b in w[b]; after a
@@ -639,94 +698,6 @@ extern "C" int vlb_sample_norm_weights(const int64_t* labels, const float* tsum,
   return VLB_OK;
 }
 
-// Row-weighted cross entropy, one block per row: ce_fwd_bwd_kernel with w[s(r)] for 1 / n_valid.  s(r) = pos(r) / T with pos the row
-// itself or, on the compacted MLM rows, sel_pos[r] (-1 behind the labelled rows: skipped like an unlabelled row) -- one kernel serves
-// both forms.  Samples s < B_split add to loss_out0 / acc0, the others to loss_out1 / acc1.  BWD = false is the forward-only twin of
-// eval_step(): the logits are only read, the weighted mean goes to the loss slot and the counters count as vlb_ce_eval does.
-// ACC: [hits, counted rows]; a counted row adds its own 1 (integer atomics: no dependence on arrival order), the weights do not enter.
-// (m, s) always go through block_online_reduce_as_plain: the instantiations of this kernel agree bit for bit among themselves.
-template <bool BWD, bool DS, bool ACC>
-__global__ __launch_bounds__(256) void ce_rowweight_kernel(bf16_t* __restrict__ logits, long ld, int V, const int64_t* __restrict__ labels,
-                                                           const int32_t* __restrict__ sel_pos, int B, int T, int B_split,
-                                                           const float* __restrict__ w, float gscale, float* __restrict__ loss_out0,
-                                                           float* __restrict__ loss_out1, bf16_t* __restrict__ logits_copy, long ldcopy,
-                                                           const float* __restrict__ dscale, vlb_u64* __restrict__ acc0,
-                                                           vlb_u64* __restrict__ acc1) {
-  if (DS) gscale = __fmul_rn(gscale, *dscale);
-  __shared__ float sh[16];
-  const int row = blockIdx.x;
-  bf16_t* x = logits + (long)row * ld;
-  const long label = labels[row];
-  const int ldv = (int)ld;
-  if (BWD && logits_copy) {
-    bf16_t* cp = logits_copy + (long)row * ldcopy;
-    for (int c = threadIdx.x * 8; c < V; c += 2048) {
-      if (c + 8 <= V) *(uint4*)(cp + c) = *(const uint4*)(x + c);
-      else for (int k = c; k < V; ++k) cp[k] = x[k];
-    }
-  }
-  const int pos = sel_pos ? sel_pos[row] : row;
-  const int smp = pos >= 0 ? pos / T : B;
-  if (label < 0 || label >= V || smp >= B) {  // ignore_index / padding of the compacted list: no loss, zero gradient row
-    if (BWD)
-      for (int c = threadIdx.x * 8; c < ldv; c += 2048) *(uint4*)(x + c) = make_uint4(0, 0, 0, 0);
-    return;
-  }
-  const bool second = smp >= B_split;
-  float* loss_out = second ? loss_out1 : loss_out0;
-  vlb_u64* acc = second ? acc1 : acc0;
-  const float wr = w[smp];
-  float m = -INFINITY, s = 0.f;
-  int idx = INT_MAX;      // (ACC) column of m; a thread's columns ascend, so `>` alone keeps its lowest column among equals
-  for (int c = threadIdx.x * 8; c < V; c += 2048) {
-    const uint4 q = *(const uint4*)(x + c);
-    const uint32_t ww[4] = {q.x, q.y, q.z, q.w};
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const float a = bflo(ww[k]), b = bfhi(ww[k]);
-      if (c + 2 * k < V) {
-        if (ACC && a > m) idx = c + 2 * k;
-        online_merge(m, s, a, 1.f);
-      }
-      if (c + 2 * k + 1 < V) {
-        if (ACC && b > m) idx = c + 2 * k + 1;
-        online_merge(m, s, b, 1.f);
-      }
-    }
-  }
-  if (ACC) {
-    float mv = m;
-    block_argmax(mv, idx, sh + 8);
-  }
-  block_online_reduce_as_plain(m, s, sh);
-  const float lse = m + __logf(s);
-  if (threadIdx.x == 0) {
-    atomicAdd(loss_out, (lse - bf2f(x[label])) * wr);
-    if (ACC) {
-      if (idx == (int)label) atomicAdd(acc, (vlb_u64)1);
-      atomicAdd(acc + 1, (vlb_u64)1);
-    }
-  }
-  if (!BWD) return;
-  const float sc = gscale * wr;
-  __syncthreads();  // x[label] read above before anyone overwrites it
-  for (int c = threadIdx.x * 8; c < ldv; c += 2048) {
-    const uint4 q = *(const uint4*)(x + c);
-    const uint32_t ww[4] = {q.x, q.y, q.z, q.w};
-    uint32_t o[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const int c0 = c + 2 * k, c1 = c0 + 1;
-      float g0 = (c0 < V) ? __expf(bflo(ww[k]) - lse) : 0.f;
-      float g1 = (c1 < V) ? __expf(bfhi(ww[k]) - lse) : 0.f;
-      if (c0 == label) g0 -= 1.f;
-      if (c1 == label) g1 -= 1.f;
-      o[k] = pack2bf(g0 * sc, g1 * sc);
-    }
-    *(uint4*)(x + c) = make_uint4(o[0], o[1], o[2], o[3]);
-  }
-}
-
 static int ce_rowweight_check(const char* who, const void* logits, long ld, int rows, int V, const void* labels, const void* sel_pos, int B, int T,
                               int B_split, const void* w, const void* loss_out0, const void* loss_out1, const void* acc0, const void* acc1) {
   VLB_CHECK_ARG(logits && labels && w && loss_out0, "%s: null argument", who);
@@ -748,17 +719,11 @@ extern "C" int vlb_ce_rowweight_fwd_bwd(void* logits, long ld, int rows, int V, 
       VLB_OK)
     return VLB_ERR_ARG;
   VLB_CHECK_ARG(!logits_copy || ldcopy >= V, "vlb_ce_rowweight_fwd_bwd: ldcopy too small");
-#define VLB_CE_RW(DS_, ACC_)                                                                                                                  \
-  hipLaunchKernelGGL((ce_rowweight_kernel<true, DS_, ACC_>), dim3(rows), dim3(256), 0, stream, (bf16_t*)logits, ld, V, labels, sel_pos, B, T, \
-                     B_split, w, gscale, loss_out0, loss_out1, (bf16_t*)logits_copy, ldcopy, dscale, (vlb_u64*)acc0, (vlb_u64*)acc1)
-  if (acc0) {
-    if (dscale) VLB_CE_RW(true, true);
-    else VLB_CE_RW(false, true);
-  } else {
-    if (dscale) VLB_CE_RW(true, false);
-    else VLB_CE_RW(false, false);
-  }
-#undef VLB_CE_RW
+  const RowWeightNorm norm = {sel_pos, B, T, B_split, w, loss_out0, (vlb_u64*)acc0, loss_out1, (vlb_u64*)acc1};
+  with_ds_acc(dscale, acc0, [&](auto DS, auto ACC) {
+    hipLaunchKernelGGL((ce_row_kernel<RowWeightNorm, true, DS(), ACC()>), dim3(rows), dim3(256), 0, stream, (bf16_t*)logits, ld, V, labels, norm,
+                       gscale, (bf16_t*)logits_copy, ldcopy, dscale);
+  });
   VLB_CHECK_LAUNCH("vlb_ce_rowweight_fwd_bwd");
   return VLB_OK;
 }
@@ -770,67 +735,11 @@ extern "C" int vlb_ce_rowweight_eval(const void* logits, long ld, int rows, int 
   if (ce_rowweight_check("vlb_ce_rowweight_eval", logits, ld, rows, V, labels, sel_pos, B, T, B_split, w, loss_out0, loss_out1, acc0, acc1) != VLB_OK)
     return VLB_ERR_ARG;
   VLB_CHECK_ARG(acc0, "vlb_ce_rowweight_eval: null counters");
-  hipLaunchKernelGGL((ce_rowweight_kernel<false, false, true>), dim3(rows), dim3(256), 0, stream, (bf16_t*)const_cast<void*>(logits), ld, V, labels,
-                     sel_pos, B, T, B_split, w, 1.f, loss_out0, loss_out1, (bf16_t*)nullptr, 0L, (const float*)nullptr, (vlb_u64*)acc0,
-                     (vlb_u64*)acc1);
+  const RowWeightNorm norm = {sel_pos, B, T, B_split, w, loss_out0, (vlb_u64*)acc0, loss_out1, (vlb_u64*)acc1};
+  hipLaunchKernelGGL((ce_row_kernel<RowWeightNorm, false, false, true>), dim3(rows), dim3(256), 0, stream, (bf16_t*)const_cast<void*>(logits), ld, V,
+                     labels, norm, 1.f, (bf16_t*)nullptr, 0L, (const float*)nullptr);
   VLB_CHECK_LAUNCH("vlb_ce_rowweight_eval");
   return VLB_OK;
-}
-
-// Row-weighted soft-label twin, s(r) = r / R: soft_ce_fwd_bwd_kernel with w[r / R] for 1 / n_valid; BWD = false only reads the logits.
-template <bool BWD, bool DS, bool ACC>
-__global__ __launch_bounds__(256) void soft_ce_rowweight_kernel(bf16_t* __restrict__ logits, long ld, int C, const float* __restrict__ target,
-                                                                long ldt, const float* __restrict__ tsum, int R, const float* __restrict__ w,
-                                                                float gscale, float* __restrict__ loss_out, bf16_t* __restrict__ logits_copy,
-                                                                long ldcopy, const float* __restrict__ dscale, vlb_u64* __restrict__ acc) {
-  __shared__ float sh[28];
-  if (DS) gscale = __fmul_rn(gscale, *dscale);
-  const int row = blockIdx.x;
-  bf16_t* x = logits + (long)row * ld;
-  const float* t = target + (long)row * ldt;
-  const int ldv = (int)ld;
-  if (BWD && logits_copy) {
-    bf16_t* cp = logits_copy + (long)row * ldcopy;
-    for (int c = threadIdx.x; c < C; c += 256) cp[c] = x[c];
-  }
-  const float ts = tsum[row];
-  if (!(fabsf(ts - 1.f) < 0.1f)) {
-    if (BWD)
-      for (int c = threadIdx.x; c < ldv; c += 256) x[c] = 0;
-    return;
-  }
-  const float wr = w[row / R];
-  float m = -INFINITY, s = 0.f, dot = 0.f, tm = -INFINITY;
-  int xi = INT_MAX, ti = INT_MAX;      // (ACC) ascending columns per thread: `>` keeps the lowest among equals
-  for (int c = threadIdx.x; c < C; c += 256) {
-    const float v = bf2f(x[c]), tv = t[c];
-    if (ACC) {
-      if (v > m) xi = c;
-      if (tv > tm) { tm = tv; ti = c; }
-    }
-    online_merge(m, s, v, 1.f);
-    dot += tv * v;
-  }
-  if (ACC) {
-    float mv = m;
-    block_argmax(mv, xi, sh + 12);
-    block_argmax(tm, ti, sh + 20);
-    if (threadIdx.x == 0) {
-      if (xi == ti) atomicAdd(acc, (vlb_u64)1);
-      atomicAdd(acc + 1, (vlb_u64)1);
-    }
-  }
-  block_online_reduce_as_plain(m, s, sh);
-  dot = block_sum(dot, sh + 8);
-  const float lse = m + __logf(s);
-  if (threadIdx.x == 0) atomicAdd(loss_out, (lse * ts - dot) * wr);
-  if (!BWD) return;
-  const float sc = gscale * wr;
-  for (int c = threadIdx.x; c < ldv; c += 256) {
-    float g = 0.f;
-    if (c < C) g = (__expf(bf2f(x[c]) - lse) * ts - t[c]) * sc;
-    x[c] = f2bf(g);
-  }
 }
 
 // rows = B * R regions; tsum [rows] and w [B] are written here (row validity, then vlb_sample_norm_weights' arithmetic on it), counts[0]
@@ -846,17 +755,11 @@ extern "C" int vlb_soft_ce_rowweight_fwd_bwd(void* logits, long ld, int rows, in
   hipLaunchKernelGGL(soft_valid_kernel, dim3(vlb_cdiv(rows, 4)), dim3(256), 0, stream, target, ldt, C, rows, tsum, counts);
   hipLaunchKernelGGL(sample_norm_weights_kernel, dim3(1), dim3(1024), 0, stream, (const int64_t*)nullptr, (const float*)tsum, rows / R, R, 0,
                      rows / R, w, (float*)nullptr, (float*)nullptr);
-#define VLB_SOFT_RW(DS_, ACC_)                                                                                                             \
-  hipLaunchKernelGGL((soft_ce_rowweight_kernel<true, DS_, ACC_>), dim3(rows), dim3(256), 0, stream, (bf16_t*)logits, ld, C, target, ldt,  \
-                     (const float*)tsum, R, (const float*)w, gscale, loss_out, (bf16_t*)logits_copy, ldcopy, dscale, (vlb_u64*)acc)
-  if (acc) {
-    if (dscale) VLB_SOFT_RW(true, true);
-    else VLB_SOFT_RW(false, true);
-  } else {
-    if (dscale) VLB_SOFT_RW(true, false);
-    else VLB_SOFT_RW(false, false);
-  }
-#undef VLB_SOFT_RW
+  const RowWeightNorm norm = {nullptr, rows / R, R, rows / R, w, loss_out, (vlb_u64*)acc, nullptr, nullptr};
+  with_ds_acc(dscale, acc, [&](auto DS, auto ACC) {
+    hipLaunchKernelGGL((soft_ce_row_kernel<RowWeightNorm, true, DS(), ACC()>), dim3(rows), dim3(256), 0, stream, (bf16_t*)logits, ld, C, target, ldt,
+                       (const float*)tsum, norm, gscale, (bf16_t*)logits_copy, ldcopy, dscale);
+  });
   VLB_CHECK_LAUNCH("vlb_soft_ce_rowweight_fwd_bwd");
   return VLB_OK;
 }
@@ -870,9 +773,9 @@ extern "C" int vlb_soft_ce_rowweight_eval(const void* logits, long ld, int rows,
   hipLaunchKernelGGL(soft_valid_kernel, dim3(vlb_cdiv(rows, 4)), dim3(256), 0, stream, target, ldt, C, rows, tsum, counts);
   hipLaunchKernelGGL(sample_norm_weights_kernel, dim3(1), dim3(1024), 0, stream, (const int64_t*)nullptr, (const float*)tsum, rows / R, R, 0,
                      rows / R, w, (float*)nullptr, (float*)nullptr);
-  hipLaunchKernelGGL((soft_ce_rowweight_kernel<false, false, true>), dim3(rows), dim3(256), 0, stream, (bf16_t*)const_cast<void*>(logits), ld, C,
-                     target, ldt, (const float*)tsum, R, (const float*)w, 1.f, loss_out, (bf16_t*)nullptr, 0L, (const float*)nullptr,
-                     (vlb_u64*)acc);
+  const RowWeightNorm norm = {nullptr, rows / R, R, rows / R, w, loss_out, (vlb_u64*)acc, nullptr, nullptr};
+  hipLaunchKernelGGL((soft_ce_row_kernel<RowWeightNorm, false, false, true>), dim3(rows), dim3(256), 0, stream, (bf16_t*)const_cast<void*>(logits), ld,
+                     C, target, ldt, (const float*)tsum, norm, 1.f, (bf16_t*)nullptr, 0L, (const float*)nullptr);
   VLB_CHECK_LAUNCH("vlb_soft_ce_rowweight_eval");
   return VLB_OK;
 }

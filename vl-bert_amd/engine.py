@@ -57,7 +57,7 @@ class ModelConfig:
     image_num_layers: int = 101  # NETWORK.IMAGE_NUM_LAYERS (50 / 101 / 152)
     image_frozen_stages: tuple = (1, 2)   # NETWORK.IMAGE_FROZEN_BACKBONE_STAGES (BatchNorm is always frozen: IMAGE_FROZEN_BN)
     # objective switches (NETWORK.WITH_MLM_LOSS / WITH_MVRC_LOSS / *_LOSS_NORM_IN_BATCH_FIRST): an absent loss takes its head and the
-    # parameters only it reads out of the model; norm in batch first = per-sample means (objectives_16.py).  The defaults change nothing
+    # parameters only it reads out of the model; norm in batch first = per-sample means (ends_16.Heads16).  The defaults change nothing
     with_mlm_loss: bool = True
     with_mvrc_loss: bool = True
     mlm_norm_in_batch_first: bool = False
@@ -413,11 +413,7 @@ class PretrainEngine:
         else:
             from .ends_16 import CoreFront16, Heads16, PretrainFront16
             self.front = CoreFront16(self) if core else PretrainFront16(self, image_size)
-            if cfg.default_objective:
-                self.back = Heads16(self)
-            else:      # a head left out, or per-sample loss means: the heads as a part of their own
-                from .objectives_16 import ObjectiveHeads16
-                self.back = ObjectiveHeads16(self)
+            self.back = Heads16(self)
             self.vision = None if core else self.front.vision
             self.wT.update(self.back.wT)
             self.wT.update(self.front.wT)
